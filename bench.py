@@ -12,8 +12,9 @@ weights) are resident in HBM before the timed region; nothing is skipped inside 
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` for the dominant kernel (HIP
 events recorded on the engine's stream during the timed region; the other output-layer kernel under
 `roofline_other`) and `cpu_baseline` (the oracle's reference-shaped dense step, timed on this box's host cores,
-N=1 only).  Timed regions of --steps steps are repeated until 2 s have been timed: `ms_per_step` is the median region / steps,
-`ms_per_step_spread` = (max - min) / median over the regions.
+N=1 only).  Exactly --steps steps are timed, in two consecutive regions (one train_epoch call each): `ms_per_step` is their total / steps,
+`ms_per_step_spread` = (max - min) / mean of the two regions' time per step.  --dump-outputs DIR writes what those steps hand their caller (the
+phase's mean loss, the trained parameters) as .npy files; the inputs are seeded, so two builds run with the same arguments compare file for file.
 
 N > 1 (`--parallel auto`, the default) times, in the same processes, the three ways a node shares a step:
   headline `value`  data parallel, b = 1000 teams per GPU (weak scaling) - rows split over the GPUs, gradients reduce-scattered / parameters
@@ -76,7 +77,28 @@ def parse():
                     help="N = 1 only: run what ONE rank of G runs under --parallel dp (north_star's form): its --batch rows of a global minibatch of G * --batch teams through the "
                          "deferred, chunked dW path (no Adam in the dW epilogue, stand-alone operand producer), Adam on the 1/G shard it would own - WITHOUT the reduce-scatter / "
                          "all-gather (their bytes are reported): the per-rank compute time of the data-parallel form; not the headline")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the headline's timed steps, write what the last of them handed its caller as DIR/<name>.npy: mean_loss (float64) and every parameter "
+                         "(float32, state_dict names); an array over its share of 64 MiB is a fixed, seeded sample of its elements")
+    a = ap.parse_args()
+    if a.steps < 1: ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, mean_loss, sd):
+    """--dump-outputs: `mean_loss` and the state_dict `sd` as float64 / float32 .npy files under `path`, at most DUMP_BYTES in all.  An array larger than its
+    even share is replaced by the elements at sorted flat indices drawn from a generator seeded with 0: the same indices for the same shapes, run after run."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "mean_loss.npy"), np.array(mean_loss, dtype=np.float64))
+    cap = (DUMP_BYTES - 4096 * (len(sd) + 1)) // 4 // max(len(sd), 1)      # (4096: room for each file's .npy header)
+    for k, v in sd.items():
+        v = np.asarray(v, dtype=np.float32)
+        if v.size > cap:
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, v.size, cap))]
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def cpu_baseline(ds, dims, bayesian, cfg, sample_rows=1000, steps=10):
@@ -375,9 +397,10 @@ def main():
     n_params = int(sum(v.size for v in sd0.values()))
     rng = np.random.default_rng(7)
 
-    def run_mode(par, gB, steps, warmup, reps_allowed=True, breakdown=True, data=ds, model_dims=dims, params=sd0, leg=None, agree=None):
+    def run_mode(par, gB, steps, warmup, n_regions=2, breakdown=True, data=ds, model_dims=dims, params=sd0, leg=None, agree=None, dump=None):
         """build an engine for this way of sharing a step (par = dp | ep, gB = the global minibatch), warm up, time `steps` steps between barriers; returns a dict.
-        agree (extra legs at N > 1): called with this rank's "my engine is built" - the leg goes on only when every rank's is (no rank enters a collective alone)"""
+        agree (extra legs at N > 1): called with this rank's "my engine is built" - the leg goes on only when every rank's is (no rank enters a collective alone).
+        dump: directory for dump_outputs() of the state the timed steps leave behind"""
         ep = par == "ep"
         shard = expert_shards(model_dims[-1], G)[0 if a.ep_emulate else rank] if ep else None
         eB = gB if ep else -(-gB // (a.dp_emulate or (1 if a.ep_emulate else world)))     # rows one engine steps: under ep every rank steps the whole global minibatch
@@ -401,10 +424,10 @@ def main():
                 if e is not None: e.close()
                 raise LegSkipped(built_err or "another rank could not build its engine")
             if leg: inject_failure(leg, "run")
-            # timed regions of `steps` steps are repeated until >= 2 s of GPU time have been timed (the driver's --steps 20 is a 30 ms region: 5 of them were 0.15 s
-            # of a 90 s process - too short for an outside sampler to see the GPU busy); ms_per_step = the median region / steps
-            reps_max = 96 if reps_allowed else 1
-            order = rng.integers(0, data["N"], (warmup + steps * reps_max) * gB).astype(np.int64)   # the loader's shuffled row order
+            # exactly `steps` steps are timed, split into `n_regions` consecutive regions (one train_epoch call each, so that a spread can be stated); the state they
+            # leave is then the same from run to run.  The untimed passes further down reuse the order's first batches (up to 40 of them).
+            sizes = [steps // n_regions + (i < steps % n_regions) for i in range(min(n_regions, steps))]
+            order = rng.integers(0, data["N"], max(warmup + steps, 40) * gB).astype(np.int64)   # the loader's shuffled row order
             if warmup: dp.train_epoch(order[: warmup * gB], gB)
             # HIP events inside the timed regions, around the roofline's kernels only - and around ONE of the two per region, alternating (an event pair costs the step
             # ~8 us: with both pairs in every region the headline carried 17 us = 1.2 % of measurement overhead; each kernel is still timed live, in every second region)
@@ -420,19 +443,21 @@ def main():
                         evt_steps[fam] = evt_steps.get(fam, 0) + nsteps
             e.kernel_times(enable=0 if no_events else 3)
             regions, mean_loss, off, losses = [], None, warmup * gB, []
-            while len(regions) < reps_max:
+            for k in sizes:
                 e.synchronize(); torch.cuda.synchronize()
                 if world > 1: dist.barrier()
                 t0 = time.perf_counter()
-                mean_loss = dp.train_epoch(order[off: off + steps * gB], gB)
+                mean_loss = dp.train_epoch(order[off: off + k * gB], gB)
                 e.synchronize(); torch.cuda.synchronize()
                 if world > 1: dist.barrier()
                 t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device="cuda")
-                if world > 1: dist.all_reduce(t, op=dist.ReduceOp.MAX)      # every rank sees the same region time, hence takes the same decision below
-                regions.append(float(t.item())); off += steps * gB; losses.append(float(mean_loss))
-                collect(0 if no_events else (4 if len(regions) % 2 else 3), steps)      # (a single region: the forward kernel only - its partner comes from the breakdown pass below)
-                if sum(regions) >= float(os.environ.get("NTF_BENCH_MIN_TIMED_S", "2.0")): break                                # every rank sees the same (max-reduced) times, hence takes the same decision
+                if world > 1: dist.all_reduce(t, op=dist.ReduceOp.MAX)      # every rank reports the same region time
+                regions.append(float(t.item())); off += k * gB; losses.append(float(mean_loss))
+                collect(0 if no_events else (4 if len(regions) % 2 else 3), k)      # (a single region: the forward kernel only - its partner comes from the breakdown pass below)
             collect(0)
+            if dump:      # before the untimed passes below step the engine further
+                sd = dp.state_dict() if ep else (e.state_dict() if rank == 0 else None)      # (ep: the shards gathered, a collective of every rank)
+                if rank == 0: dump_outputs(dump, mean_loss, sd)
             bd, k3 = None, 0
             if breakdown:   # per-family breakdown from a SEPARATE short pass (events around every family perturb the step by a few per cent)
                 k3 = max(5, min(10, steps))
@@ -457,7 +482,9 @@ def main():
                 tr.measure_waits = False
                 waits = {"steps": kw, "ms_per_step_of_this_pass": tw, "exposed_wait_ms_per_step": ex, "rank_compute_ms_per_step": tw - sum(ex.values()),
                          "note": "rank 0's figures; the pass carries two events per collective wait (not the timed regions)"}
-            dt = float(np.median(regions))
+            dt = float(sum(regions))      # the `steps` timed steps
+            per_step = [t / k for t, k in zip(regions, sizes)]
+            spread = (max(per_step) - min(per_step)) / (dt / steps) if len(per_step) > 1 else None
             # the validation phase's step (src/mdl/fnn.py:143-151: forward + loss on fresh eps, no backward): 566 of a fold-epoch's 1 697 batches at config 2
             ev = None
             if breakdown and world == 1 and not a.ep_emulate and not a.dp_emulate:
@@ -466,7 +493,7 @@ def main():
                 ev_run(order[: 3 * gB], gB); e.synchronize()
                 t0 = time.perf_counter(); ev_loss = ev_run(order[: kev * gB], gB); e.synchronize()
                 ev = {"ms_per_step": (time.perf_counter() - t0) / kev * 1e3, "steps": kev, "mean_loss": ev_loss}
-            res = {"par": par, "eval": ev, "collective_waits": waits, "ep": ep, "gB": gB, "eB": eB, "dt": dt, "regions": regions, "mean_loss": mean_loss, "region_losses": losses, "times": times, "evt_steps": evt_steps, "adam_in_dw": bool((world == 1 and not a.dp_emulate) or ep), "breakdown": bd, "k3": k3,
+            res = {"par": par, "eval": ev, "collective_waits": waits, "ep": ep, "gB": gB, "eB": eB, "dt": dt, "regions": regions, "spread": spread, "mean_loss": mean_loss, "region_losses": losses, "times": times, "evt_steps": evt_steps, "adam_in_dw": bool((world == 1 and not a.dp_emulate) or ep), "breakdown": bd, "k3": k3,
                    "Mloc": (shard[1] - shard[0]) if ep else model_dims[-1], "engine": e,
                    "rccl_payload_bytes_per_step": (4 * gB * a.hidden) if ep else (8 * n_params if world > 1 else 0),
                    "emulated_bytes": getattr(dp, "emulated_bytes", None)}
@@ -478,7 +505,7 @@ def main():
     elif (G > 1 or a.force_dist) and a.parallel != "dp" and shardable: head_par = "ep"
     else: head_par = "dp"
     gB = a.batch * G                                       # weak scaling: B teams per GPU
-    head = run_mode(head_par, gB, a.steps, a.warmup)
+    head = run_mode(head_par, gB, a.steps, a.warmup, dump=a.dump_outputs)
     e = head["engine"]
     if a.gather_only:
         with torch.cuda.stream(stream):
@@ -533,13 +560,12 @@ def main():
         B, H, M = a.batch, a.hidden, ds["M"]
         ep = head["ep"]; dt = head["dt"]
         roof, roof_other = rooflines(head["times"], a, bayesian, head["eB"], H, head["Mloc"], ds, ep, head.get("evt_steps"), head.get("adam_in_dw", True))
-        spread = (max(head["regions"]) - min(head["regions"])) / dt if len(head["regions"]) > 1 else None
         state["loss_finite"] = bool(np.all(np.isfinite(head["region_losses"]))) and all(
             np.isfinite(v.get("mean_loss", 0.0) or 0.0) for v in list((state["extra_configs"] or {}).values()) + list(extra_modes.values()) if isinstance(v, dict))
         devices = [torch.cuda.get_device_name(local)]
         out = {
             "metric": "teams/sec (train) bnn_emb d=128 on DBLP", "value": a.steps * gB / dt, "unit": "teams/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "ms_per_step_spread": spread, "timed_regions": len(head["regions"]),
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "ms_per_step_spread": head["spread"], "timed_regions": len(head["regions"]),
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": {"f32": "f32"}.get(a.mfma, "f32 (fp16x3 split products, f32 accumulate)"), "data": "synthetic",
             "config": {"workload": workload_label(a, ds, bayesian, multihot), "global_batch": gB,
@@ -657,7 +683,7 @@ def main():
         dsf = make_dataset("dblp_full", d=a.d, seed=0, n_rows=200_000)
         dimsf = [a.d, a.hidden, dsf["M"]]
         a.dataset = "dblp_full"
-        r = run_mode("dp", a.batch, 10, 2, reps_allowed=False, breakdown=True, data=dsf, model_dims=dimsf, params=init_params(dimsf, bayesian, 0)); r["engine"].close()
+        r = run_mode("dp", a.batch, 10, 2, n_regions=1, breakdown=True, data=dsf, model_dims=dimsf, params=init_params(dimsf, bayesian, 0)); r["engine"].close()
         rf, rfo = rooflines(r["times"], a, bayesian, r["eB"], a.hidden, r["Mloc"], dsf, False, r.get("evt_steps"), r.get("adam_in_dw", True))      # (traffic: no PMC pass at this size - null)
         extra_configs = {"dblp_full": {"workload": workload_label(a, dsf, bayesian, False), "steps": 10, "ms_per_step": r["dt"] / 10 * 1e3, "value": 10 * a.batch / r["dt"], "unit": "teams/s",
                                        "mean_loss": r["mean_loss"], "roofline": rf, "roofline_other": rfo}}

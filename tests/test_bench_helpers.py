@@ -45,3 +45,22 @@ def test_pmc_traffic_is_refused_for_another_kernel(monkeypatch):
     monkeypatch.delenv("NTF_FWD_KERNEL")
     assert bench.pmc_traffic("out_fused_fwd_loss_dh", _args(hidden=64), None) == (None, None)      # another shape than the profiled one
     assert bench.pmc_traffic("out_fused_fwd_loss_dh", _args(input="multihot"), None) == (None, None)
+
+
+def test_dump_outputs_fit_the_budget_and_sample_the_same_elements_every_time(tmp_path):
+    big = np.arange(16_000_000, dtype=np.float32).reshape(-1, 128 * 125)        # 64 MB, every element its own index (exact in float32): over its share of the budget
+    sd = {"layers.0.mu_weight": np.full((128, 128), 0.5, np.float32), "layers.1.mu_weight": big, "layers.1.mu_bias": np.ones(1000, np.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 1.25, sd)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["layers.0.mu_weight.npy", "layers.1.mu_bias.npy", "layers.1.mu_weight.npy", "mean_loss.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    loss = np.load(tmp_path / "a" / "mean_loss.npy")
+    assert loss.dtype == np.float64 and loss == 1.25
+    w0, b1 = np.load(tmp_path / "a" / "layers.0.mu_weight.npy"), np.load(tmp_path / "a" / "layers.1.mu_bias.npy")
+    assert w0.dtype == np.float32 and w0.shape == (128, 128) and (w0 == 0.5).all()            # under the budget: stored whole, shape kept
+    assert b1.dtype == np.float32 and b1.shape == (1000,) and (b1 == 1).all()
+    s = np.load(tmp_path / "a" / "layers.1.mu_weight.npy")
+    assert s.dtype == np.float32 and 1_000_000 < s.size < big.size and (np.diff(s) >= 0).all() and s.min() >= 0 and s.max() < big.size      # elements of the array, in index order
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n

@@ -484,7 +484,7 @@ def test_bench_multi_rank_launch_on_one_gpu(parallel):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--validate-on-one-gpu", "--parallel", parallel,
            "--rows", "20000", "--experts", "4096"]
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root, env={**os.environ, "NTF_BENCH_MIN_TIMED_S": "0.05"})
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root, env=os.environ)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -516,7 +516,7 @@ def test_bench_headline_survives_a_failing_extra_leg(fail):
         s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--validate-on-one-gpu", "--parallel", "auto", "--rows", "20000", "--experts", "4096"]
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root, env={**os.environ, "NTF_BENCH_MIN_TIMED_S": "0.05", "NTF_BENCH_FAIL_LEG": fail})
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root, env={**os.environ, "NTF_BENCH_FAIL_LEG": fail})
     if fail.startswith("ep_weak:build"): assert p.returncode == 0, p.stderr.decode()[-3000:]
     else: assert p.returncode != 0, "a leg that failed while running must not look like success"
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
@@ -528,3 +528,31 @@ def test_bench_headline_survives_a_failing_extra_leg(fail):
         assert "skipped before any collective" in d["ep_weak"]["error"] and d["strong_b1000"]["value"] > 0
     else:
         assert "injected failure" in d["ep_weak"]["error"] and "error" in d["strong_b1000"]
+
+
+def test_bench_dump_outputs_are_the_state_after_exactly_the_timed_steps(tmp_path):
+    """bench.py --dump-outputs: the same arguments give the same files (the inputs are seeded and exactly --steps steps are timed), one more step gives another
+    state, and the dumped loss is the one the JSON line reports"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(steps, out):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--rows", "20000", "--experts", "4096",
+               "--no-cpu-baseline", "--no-f32-line", "--no-extra-configs", "--no-gather-bench", "--dump-outputs", str(tmp_path / out)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+    d = run(3, "a"); run(3, "b"); run(4, "c")
+    assert d["steps"] == 3 and d["timed_regions"] == 2
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["mean_loss.npy"] + [f"layers.{l}.{k}.npy" for l in (0, 1) for k in ("mu_weight", "rho_weight", "mu_bias", "rho_bias")])
+    loss = np.load(tmp_path / "a" / "mean_loss.npy")
+    assert loss.dtype == np.float64 and float(loss) == d["mean_loss"]
+    w = np.load(tmp_path / "a" / "layers.1.mu_weight.npy")
+    assert w.dtype == np.float32 and w.shape == (4096, 128)
+    for n in names:
+        np.testing.assert_allclose(np.load(tmp_path / "b" / n), np.load(tmp_path / "a" / n), rtol=1e-5, atol=1e-6, err_msg=n)
+    assert np.abs(np.load(tmp_path / "c" / "layers.1.mu_weight.npy") - w).max() > 1e-5      # a fourth Adam step (lr 1e-3) moved the weights
