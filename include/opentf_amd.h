@@ -70,7 +70,7 @@ typedef struct ntf_config {
        output layer of `experts_global` experts that is split over `ep_world` engines (one per GPU); hidden layers are replicated.  Every engine
        steps the WHOLE minibatch: labels (member CSR) and sampled negatives keep global expert ids, the device generators are keyed by global
        ids, and the only exchange of a train step is the sum over engines of d(hidden) [B, h[-1]] between ntf_step_staged_ep phases 1 and 3.
-       expert_lo must be a multiple of 256; needs the fused output-layer path (h[-1] in {32, 64, 128}). */
+       expert_lo must be a multiple of 256; needs the fused output-layer path (h[-1] in {32, 64, 128, 256}). */
     int32_t expert_lo;
     int32_t experts_global;
     int32_t ep_world;

@@ -295,7 +295,7 @@ extern "C" int ntf_engine_create(const ntf_config* cfg, ntf_engine** out) {
     if (cfg->fused && !fused_supported(e->layers[e->L - 1].in) && (int64_t)cfg->dims[e->L] >= 4096 && !getenv("NTF_QUIET")) {
         // (a hidden width outside {32, 64, 128} fell to the generic chain - k_gemm + dense [B, M] loss - without a word: 59 k teams/s against ~740 k at config 2's size)
         static bool warned = false;
-        if (!warned) fprintf(stderr, "opentf_amd: h[-1] = %d has no fused output-layer kernels (32, 64 and 128 have; 128 also the split-product ones): this model runs on the "
+        if (!warned) fprintf(stderr, "opentf_amd: h[-1] = %d has no fused output-layer kernels (32, 64, 128 and 256 have; 128 also the split-product ones): this model runs on the "
                                      "generic GEMM + dense-loss chain, an order of magnitude slower at %d experts (INTEGRATION.md, limits)\n", e->layers[e->L - 1].in, cfg->dims[e->L]);
         warned = true;
     }
@@ -304,7 +304,7 @@ extern "C" int ntf_engine_create(const ntf_config* cfg, ntf_engine** out) {
     e->ep = cfg->experts_global > 0 || e->ep_lo != 0 || e->ep_world > 1;   // a shard may also be the whole layer (ep_world = 1)
     if (e->ep) {
         const char* bad = nullptr;
-        if (!fused_ok(e)) bad = "an expert-sharded output layer needs the fused output-layer path (fused = 1, h[-1] in {32, 64, 128})";
+        if (!fused_ok(e)) bad = "an expert-sharded output layer needs the fused output-layer path (fused = 1, h[-1] in {32, 64, 128, 256})";
         else if (e->ep_lo < 0 || (e->ep_lo & 255)) bad = "expert_lo must be a non-negative multiple of 256";
         else if ((int64_t)e->ep_lo + cfg->dims[e->L] > e->Mg) bad = "expert_lo + dims[n_layers] exceeds experts_global";
         if (bad) { g_create_error = bad; if (e->own_stream) hipStreamDestroy(e->st); delete e; return NTF_EINVAL; }
@@ -613,9 +613,11 @@ static inline float dz_scale16(const ntf_engine* e, int global_B) {   // |dz| <=
     return std::exp2(std::floor(std::log2(16384.f / dzmax)));
 }
 
+// the fused output layer has split-product (fp16x3) kernels: h[-1] <= 128 (256 runs on the exact-f32 kernels in every mfma mode)
+static bool split_products(const ntf_engine* e) { return e->layers[e->L - 1].in <= 128; }
 // the range flag of the fp16x3 arithmetic, or null when this engine never multiplies in fp16x3
 static int32_t* range_ptr(const ntf_engine* e) {
-    return (fused_ok(e) && (e->cfg.mfma == NTF_MFMA_DEFAULT || e->cfg.mfma == NTF_MFMA_FP16X3)) ? e->d_range : nullptr;
+    return (fused_ok(e) && split_products(e) && (e->cfg.mfma == NTF_MFMA_DEFAULT || e->cfg.mfma == NTF_MFMA_FP16X3)) ? e->d_range : nullptr;
 }
 
 static int check_ready(ntf_engine* e, bool need_labels) {
@@ -1112,13 +1114,13 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
             if (!hp_hit) head_launch(e, e->st, c, e->fws, c.train && e->cfg.mfma != NTF_MFMA_F32, hp_stale ? nullptr : e->d_kl, !hp_stale, f.rflag, true, skip_w0);
             f.h_ready = 1;
             if (!f.planes_ready) launch_fused_out_fwd(e->st, f, 1);   // (Fnn: the split planes of mu are made per step)
-            if (c.train && e->cfg.mfma != NTF_MFMA_F32 && !swt_aux && !hp_hit) {   // (one stream: the s_out words were not made beside the head)
+            if (c.train && e->cfg.mfma != NTF_MFMA_F32 && split_products(e) && !swt_aux && !hp_hit) {   // (one stream: the s_out words were not made beside the head)
                 const bool dz_packed = f.np == 2 && lo.in == 128 && e->pl_mu != nullptr;
                 launch_fused_prep_planes(e->st, B, lo.in, M, e->cfg.bayesian, e->fws, f.np, f.h_scale, dz_packed ? &f.s_out : nullptr, 0, 1);
             }
         } else {
         { Scope t(e, F_OUT_FUSED_AUX); launch_fused_out_fwd(e->st, f, 1); }
-            if (c.train && e->cfg.mfma != NTF_MFMA_F32) {
+            if (c.train && e->cfg.mfma != NTF_MFMA_F32 && split_products(e)) {
                 // operands of the dW kernel that depend on h and on the sign keys only (split planes of h / h*s_in, transposed s_out words): prepared here, in the
                 // step's head (beside the side-stream producer), not between the forward and the dW kernel
                 Scope t(e, F_OUT_FUSED_AUX);
@@ -1228,7 +1230,7 @@ backward:
             f.dzT = e->dZout; f.h = in; f.g_mu = gW; f.g_rho = gRW; f.g_b = gb; f.g_bp = gRb; f.ws = e->fws;
             f.mu = e->P + li.off[NTF_P_WEIGHT];
             f.s_out = sout_; f.s_out_inj = e->cfg.bayesian && (sout_.inj != nullptr || sin_.inj != nullptr);
-            f.bf16x6 = e->cfg.mfma != NTF_MFMA_F32;   // default: bf16x6
+            f.bf16x6 = e->cfg.mfma != NTF_MFMA_F32 && split_products(e);   // default: the split products (fp16x3) where the width has them
             f.np = mfma_np(e); f.a_scale = dz_scale16(e, c.global_B); f.h_scale = kH16Scale; f.rflag = range_ptr(e);
             f.dz_packed = f.bf16x6 && f.np == 2 && li.in == 128 && e->pl_mu != nullptr;   // the fp16x3 forward kernels (H = 128) store packed plane pairs
             e->last_dz_packed_scale = f.dz_packed ? f.a_scale : 0.f;

@@ -22,7 +22,7 @@ int fused_ldb(int B) { return rup(B, BM); }
 int fused_dw_tile() { return DW_TC; }
 int64_t fused_dw_part_floats(int M, int H, int ksplit) { return (int64_t)ksplit * 2 * ((int64_t)rup(M, DW_TC) * (H + 1)); }
 int64_t fused_planes_elems(int M, int H) { return ((int64_t)M + 63) / 64 * 64 * H * 3; }   // rows padded to the 64-expert tile of k_out_fwd_h3x
-bool fused_supported(int H) { return H == 32 || H == 64 || H == 128; }
+bool fused_supported(int H) { return H == 32 || H == 64 || H == 128 || H == 256; }   // 256: exact-f32 kernels only (no split-product form)
 int fused_loss_slots(int) { return 0; }
 
 int64_t fused_dh_slab_floats(int, int H, int) { return (int64_t)4 * NCG_MAX * BM * H; }   // (x 4: up to four range launches of the forward kernel, each with its own column groups)
@@ -74,14 +74,21 @@ __global__ void k_prep_h(SignSpec si, int bayes, const float* __restrict__ h, in
     }
 }
 
+// H = 256: a 64-expert tile of both matrices (128 KiB) does not fit twice into LDS.  It is staged as NKH = 2 hidden halves of HS = 128 units, one after the
+// other through the same two buffers (each stage has H = 128's layout), the zT accumulators running on over both halves; the epilogue follows the last half.
+// d(hidden) does not fit into the registers beside the h operand at 256: DH is H <= 128 only (k_out_dh computes it at 256).
 template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ>
 __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem) {
-    constexpr int ROWB = 4 * H;              // bytes per weight row
-    constexpr int TB = BN * ROWB;            // bytes per weight tile
+    constexpr int HS = H > 128 ? 128 : H;    // hidden units per stage
+    constexpr int NKH = H / HS;              // stages per tile
+    static_assert(!DH || NKH == 1, "the forward kernel's d(hidden) products are H <= 128 only");
+    constexpr int ROWB = 4 * HS;             // bytes per weight row of a stage
+    constexpr int TB = BN * ROWB;            // bytes per weight tile of a stage
     constexpr int NMAT = BAYES ? 2 : 1;
     constexpr int STAGE = NMAT * TB + 512;   // + two 64-float bias tiles
     constexpr int NE = H / 2;                // operand elements per lane (k split over the two lane halves)
     constexpr int NJT = H / 32;
+    constexpr int NJY = DH ? NJT : 1;        // d(hidden) accumulators
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, half = lane >> 5;
     if (range_guard_skip(p.rflag, p.rmode, true)) return;
 
@@ -114,11 +121,11 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
     // LDS byte offsets (relative to the stage base) that depend on the lane; everything else is an immediate.
     //   A fragment of zT: row u*32 + il, logical 16-byte chunk q = 2*tq + half, physical chunk q ^ swz(row)
     //   B operand of dh : row u*32 + rowmap(s, half), float j = jt*32 + il
-    constexpr int QM = (H >= 64) ? 8 : 4;   // distinct values of the swizzled low chunk bits over tq
+    constexpr int QM = (HS >= 64) ? 8 : 4;   // distinct values of the swizzled low chunk bits over tq
     int aoff[QM];
 #pragma unroll
     for (int k = 0; k < QM; ++k) {
-        if (H >= 64) aoff[k] = il * ROWB + 16 * (((2 * k + half) & 15) ^ (il & 15));
+        if (HS >= 64) aoff[k] = il * ROWB + 16 * (((2 * k + half) & 15) ^ (il & 15));
         else aoff[k] = il * ROWB + 16 * ((2 * k + half) ^ ((il >> 1) & 7));
     }
     // dh B operand: ONE wide read per (row, matrix) feeds all NJT column tiles: lane il owns hidden units j = NJT*il + jt,
@@ -134,16 +141,16 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
             else boff[k][b8] = 0;  // H == 32: computed per step (few registers at stake there)
         }
 
-    f32x16 Y1[NJT], Y2[NJT];
+    f32x16 Y1[NJY], Y2[NJY];
 #pragma unroll
-    for (int j = 0; j < NJT; ++j)
+    for (int j = 0; j < NJY; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { Y1[j][r] = 0.f; Y2[j][r] = 0.f; }
     LossAcc lacc;
 
     const uint32_t smem_base = lds_addr(smem);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    auto stage_tile = [&](int t, int buf) {
+    auto stage_tile = [&](int t, int kh, int buf) {   // hidden units [kh HS, (kh + 1) HS) of tile t; the bias tiles come with the last part
         const uint32_t sb = smem_base + buf * STAGE;
         const int c0 = t * BN;
         constexpr int PER_WAVE = TB / 4096;  // 1 KiB wave-instructions per wave per matrix
@@ -152,11 +159,12 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
             const int inst = wave_u * PER_WAVE + n;
             const int off = inst * 1024 + lane * 16;
             const int row = off / ROWB, pch = (off % ROWB) >> 4;
-            const int q = pch ^ swz<H>(row);
+            const int q = pch ^ swz<HS>(row);
             const int64_t grow = min(c0 + row, p.M - 1);
-            glds16(p.mu + grow * H + 4 * q, sb + inst * 1024);
-            if (BAYES) glds16(p.wp + grow * H + 4 * q, sb + TB + inst * 1024);
+            glds16(p.mu + grow * H + kh * HS + 4 * q, sb + inst * 1024);
+            if (BAYES) glds16(p.wp + grow * H + kh * HS + 4 * q, sb + TB + inst * 1024);
         }
+        if (kh != NKH - 1) return;
         if (wave_u == 0) glds4(p.mu_b + min(c0 + lane, p.M - 1), sb + NMAT * TB);
         if (BAYES && wave_u == 1) glds4(p.bp + min(c0 + lane, p.M - 1), sb + NMAT * TB + 256);
     };
@@ -168,29 +176,33 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
         if (INJ) return *reinterpret_cast<const uint2*>(p.sbits + (int64_t)i * p.nCB + 2 * t);  // injected signs (tests): packed image
         return make_uint2(sign_word(p.so_k0, p.so_k1, (uint32_t)i, (uint32_t)(2 * t)), sign_word(p.so_k0, p.so_k1, (uint32_t)i, (uint32_t)(2 * t + 1)));
     };
-    if (t_beg < t_end) stage_tile(t_beg, 0);
+    if (t_beg < t_end) stage_tile(t_beg, 0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
     for (int t = t_beg; t < t_end; ++t) {
-        const int buf = (t - t_beg) & 1;
         const uint2 w2 = sign_words(t);
-        if (t + 1 < t_end) stage_tile(t + 1, buf ^ 1);
-        char* sb = smem + buf * STAGE;
         const int c0 = t * BN;
-        if (c0 + BN > p.M) {  // ragged last tile (workgroup-uniform): mask the experts past M through their bias
-            if (tid < BN && c0 + tid >= p.M) reinterpret_cast<float*>(sb + NMAT * TB)[tid] = -1e30f;
-            __syncthreads();
-        }
-
         // ---- zT tile: rows = experts (two 32-row sub-tiles u), cols = this wave's 32 batch rows.
         // Issue order (one basic block, software-interleaved so that the VALU epilogue runs under the MFMA pipe):
         //   X(u=0) | X(u=1) with epilogue(u=0) spread over its k-steps | dh(u=0) with epilogue(u=1) spread | dh(u=1)
+        // (NKH > 1: the stages of the first hidden parts run X(u=0) | X(u=1) alone)
         f32x16 X1[2], X2[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int r = 0; r < 16; ++r) { X1[u][r] = 0.f; X2[u][r] = 0.f; }
+      static_for<0, NKH>([&](auto khc) {
+        constexpr int kh = decltype(khc)::value;
+        constexpr bool LAST = kh == NKH - 1;
+        const int buf = ((t - t_beg) * NKH + kh) & 1;
+        if (!LAST) stage_tile(t, kh + 1, buf ^ 1);
+        else if (t + 1 < t_end) stage_tile(t + 1, 0, buf ^ 1);
+        char* sb = smem + buf * STAGE;
+        if (LAST && c0 + BN > p.M) {  // ragged last tile (workgroup-uniform): mask the experts past M through their bias
+            if (tid < BN && c0 + tid >= p.M) reinterpret_cast<float*>(sb + NMAT * TB)[tid] = -1e30f;
+            __syncthreads();
+        }
         uint32_t sw[2] = {0u, 0u};
         if (BAYES) { sw[0] = w2.x >> (4 * half); sw[1] = w2.y >> (4 * half); }
         // buffer descriptor over this tile's 64 rows of dzT (the tile base is wave-uniform; rows are Bpad floats)
@@ -204,7 +216,7 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
         // operand fetch and MFMA issue are separate so that the fetch for group g+1 can be issued before the MFMAs of group g
         // (one wave per SIMD: nobody else hides the LDS latency)
         auto x_load = [&](int u, int tq, float4& a, float4& aw) {
-            const int imm = u * 32 * ROWB + ((H >= 64) ? ((2 * tq) & ~15) * 16 : 0);
+            const int imm = u * 32 * ROWB + ((HS >= 64) ? ((2 * tq) & ~15) * 16 : 0);
             const char* ap = sb + aoff[tq % QM] + imm;
             a = *reinterpret_cast<const float4*>(ap);
             if (BAYES) aw = *reinterpret_cast<const float4*>(ap + TB);
@@ -214,10 +226,10 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
             const float awv[4] = {aw.x, aw.y, aw.z, aw.w};
 #pragma unroll
             for (int e4 = 0; e4 < 4; ++e4) {
-                const int e = 4 * tq + e4;
+                const int e = kh * (HS / 2) + 4 * tq + e4;
                 X1[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e4], hf[e], X1[u], 0, 0, 0);
                 if (BAYES) {
-                    const int kb = 8 * tq + e4;  // k without the lane half
+                    const int kb = kh * HS + 8 * tq + e4;  // k without the lane half
                     const uint32_t m = (sinw[kb >> 5] << (31 - (kb & 31))) & 0x80000000u;
                     X2[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(awv[e4], __uint_as_float(__float_as_uint(hf[e]) ^ m), X2[u], 0, 0, 0);
                 }
@@ -258,8 +270,8 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
                 bp_ = sb + row * ROWB + 16 * (((NJT * il) >> 2) ^ swz<H>(row)) + 4 * ((NJT * il) & 3);
             }
             if (NJT == 4) {
-                const float4 b4 = *reinterpret_cast<const float4*>(bp_); o.v[0] = b4.x; o.v[1] = b4.y; o.v[NJT > 2 ? 2 : 0] = b4.z; o.v[NJT > 3 ? 3 : 0] = b4.w;
-                if (BAYES) { const float4 w4 = *reinterpret_cast<const float4*>(bp_ + TB); o.w[0] = w4.x; o.w[1] = w4.y; o.w[NJT > 2 ? 2 : 0] = w4.z; o.w[NJT > 3 ? 3 : 0] = w4.w; }
+                const float4 b4 = *reinterpret_cast<const float4*>(bp_); o.v[0] = b4.x; o.v[NJT > 1 ? 1 : 0] = b4.y; o.v[NJT > 2 ? 2 : 0] = b4.z; o.v[NJT > 3 ? 3 : 0] = b4.w;
+                if (BAYES) { const float4 w4 = *reinterpret_cast<const float4*>(bp_ + TB); o.w[0] = w4.x; o.w[NJT > 1 ? 1 : 0] = w4.y; o.w[NJT > 2 ? 2 : 0] = w4.z; o.w[NJT > 3 ? 3 : 0] = w4.w; }
             } else if (NJT == 2) {
                 const float2 b2 = *reinterpret_cast<const float2*>(bp_); o.v[0] = b2.x; o.v[NJT > 1 ? 1 : 0] = b2.y;
                 if (BAYES) { const float2 w2_ = *reinterpret_cast<const float2*>(bp_ + TB); o.w[0] = w2_.x; o.w[NJT > 1 ? 1 : 0] = w2_.y; }
@@ -270,13 +282,13 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
         };
         auto dh_mma = [&](int u, int s, const BOp& o) {   // dh += dz[:, c] * W[c, :]: A operand = accumulator register s as it stands
 #pragma unroll
-            for (int jt = 0; jt < NJT; ++jt) {
+            for (int jt = 0; jt < NJY; ++jt) {
                 Y1[jt] = __builtin_amdgcn_mfma_f32_32x32x2f32(X1[u][s], o.v[jt], Y1[jt], 0, 0, 0);
                 if (BAYES) Y2[jt] = __builtin_amdgcn_mfma_f32_32x32x2f32(X2[u][s], o.w[jt], Y2[jt], 0, 0, 0);
             }
         };
 
-        constexpr int NTQ = H / 8, RPT = 16 / NTQ;  // epilogue registers handled per k-step of the other sub-tile
+        constexpr int NTQ = HS / 8, RPT = 16 / NTQ;  // epilogue registers handled per k-step of the other sub-tile
         {
             float4 xa[2], xw[2];
             xw[0] = xw[1] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -286,13 +298,18 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
                 const int u = g / NTQ, tq = g % NTQ;
                 if (g + 1 < 2 * NTQ) x_load((g + 1) / NTQ, (g + 1) % NTQ, xa[(g + 1) & 1], xw[(g + 1) & 1]);
                 x_mma(u, tq, xa[g & 1], xw[g & 1]);
-                if (u == 1) {
+                if (LAST && u == 1) {
 #pragma unroll
                     for (int rr = 0; rr < RPT; ++rr) epilogue(0, tq * RPT + rr);
                 }
             }
         }
-        if (TRAIN && DH) {
+        if constexpr (!LAST) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next hidden part landed (this stage stored no dz)
+            __builtin_amdgcn_s_barrier();
+            return;
+        }
+        if constexpr (TRAIN && DH) {
             BOp bo[2];
             dh_load(0, 0, bo[0]);
 #pragma unroll
@@ -313,6 +330,7 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
         if (TRAIN) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
+      });
     }
 
     // per-row loss partial of this column group
@@ -320,13 +338,13 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
     lsum += __shfl_xor(lsum, 32, 64);
     if (half == 0) p.lossp[(int64_t)i * p.NCG + cg] = p.tnw * lsum;
 
-    if (TRAIN && DH) {
+    if constexpr (TRAIN && DH) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int irow = i0 + rowmap(r, half);
             float v[NJT];
 #pragma unroll
-            for (int jt = 0; jt < NJT; ++jt) {
+            for (int jt = 0; jt < NJY; ++jt) {
                 const int j = NJT * il + jt;  // this lane's hidden units are consecutive: one 4*NJT-byte store per register
                 v[jt] = Y1[jt][r];
                 if (BAYES) {
@@ -347,6 +365,125 @@ template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ>
 __global__ __launch_bounds__(256, 1) void k_out_fwd(OutFwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     out_fwd_f32_body<H, BAYES, TRAIN, DH, INJ>(p, smem);
+}
+
+// ------------------------------------------------------------------------------------------------
+// d(hidden) of the output layer at H = 256 (the forward kernel's registers hold the h operand and the zT accumulators there, not the dh ones):
+//   dh[i, j] = sum_c dz[i, c] mu[c, j] + s_in[i, j] sum_c (dz[i, c] s_out[i, c]) Wp[c, j]
+// over the experts of a column group, as per-group slabs slab[cg][Bpad][H] that k_out_special sums - the same grid, column groups and slabs as
+// k_out_fwd's DH form.  dz comes from dzT as the forward kernel left it, i.e. BEFORE k_out_special patches the special entries (it adds their dh
+// corrections itself).  Workgroup = 4 waves x 32 batch rows; the experts of the group in 32-expert stages of both matrices' full rows (2 x 32 KiB),
+// double buffered by LDS-DMA.  MFMA k = expert: lane (il, half) feeds dz[i0 + il][c0 + 2k + half] (A) and W[c0 + 2k + half][8 il .. 8 il + 7] (B, one
+// 32-byte read per row and matrix for all eight column tiles); its accumulators hold 8 consecutive hidden units of the rows rowmap(r, half).
+// ------------------------------------------------------------------------------------------------
+template <bool BAYES, bool INJ>
+__global__ __launch_bounds__(256, 1) void k_out_dh(OutFwdArgs p) {
+    constexpr int H = 256, NJT = H / 32;
+    constexpr int KE = 32;                   // experts per stage
+    constexpr int KS = KE / 2;               // MFMA k-steps per stage
+    constexpr int ROWB = 4 * H;
+    constexpr int TB = KE * ROWB;            // bytes of one matrix's stage
+    constexpr int NMAT = BAYES ? 2 : 1;
+    constexpr int STAGE = NMAT * TB;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, half = lane >> 5;
+
+    int bid = blockIdx.x;                    // the forward kernel's block -> (column group, row block) map
+    const int nblk = gridDim.x;
+    if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
+    const int cg = bid / p.NRB, rb = bid % p.NRB;
+    const int t_beg = (int)((int64_t)cg * p.T / p.NCG), t_end = (int)((int64_t)(cg + 1) * p.T / p.NCG);
+    const int s_beg = 2 * t_beg, s_end = min(2 * t_end, (p.M + KE - 1) / KE);
+    const int i0 = rb * BM + wave * 32;
+    const int i = i0 + il;
+    const bool row_ok = i < p.B;
+
+    f32x16 acc1[NJT], acc2[NJT];
+#pragma unroll
+    for (int j = 0; j < NJT; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc1[j][r] = 0.f; acc2[j][r] = 0.f; }
+
+    const uint32_t smem_base = lds_addr(smem);
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    auto stage = [&](int s, int buf) {       // rows are 1 KiB: one wave-instruction per row and matrix, KE / 4 rows per wave
+        const uint32_t sb = smem_base + buf * STAGE;
+#pragma unroll
+        for (int n = 0; n < KE / 4; ++n) {
+            const int row = wave_u * (KE / 4) + n;
+            const int64_t grow = min(s * KE + row, p.M - 1);
+            glds16(p.mu + grow * H + 4 * lane, sb + row * ROWB);
+            if (BAYES) glds16(p.wp + grow * H + 4 * lane, sb + TB + row * ROWB);
+        }
+    };
+    // A operands of stage s (issued one stage ahead, before that stage's DMA, and consumed behind the wait that publishes it): dz[i][c0 + 2k + half]
+    // (0 past M) and the s_out word of (i, c0 / 32), shifted by the lane half
+    const int64_t dz_lane = (int64_t)(i >> 5) * 8192 + (i & 31) + half * 32;
+    auto load_a = [&](int s, float (&d)[KS], uint32_t& w) {
+        const int c0 = s * KE;
+        const float* base = p.dzT + (int64_t)(c0 >> 8) * (p.Bpad >> 5) * 8192 + ((c0 & 255) << 5) + dz_lane;
+#pragma unroll
+        for (int k = 0; k < KS; ++k) d[k] = (c0 + 2 * k + half < p.M) ? base[k * 64] : 0.f;
+        w = 0u;
+        if (BAYES && row_ok) w = (INJ ? p.sbits[(int64_t)i * p.nCB + s] : sign_word(p.so_k0, p.so_k1, (uint32_t)i, (uint32_t)s)) >> half;
+    };
+
+    float dz[KS], dzn[KS];
+    uint32_t w = 0u, wn = 0u;
+#pragma unroll
+    for (int k = 0; k < KS; ++k) { dz[k] = 0.f; dzn[k] = 0.f; }
+    if (s_beg < s_end) { load_a(s_beg, dz, w); stage(s_beg, 0); }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int s = s_beg; s < s_end; ++s) {
+        const int buf = (s - s_beg) & 1;
+        if (s + 1 < s_end) { load_a(s + 1, dzn, wn); stage(s + 1, buf ^ 1); }
+        const char* sb = smem + buf * STAGE + half * ROWB + 32 * il;     // row 2k + half, hidden units 8 il ..
+        float4 b[2][2], bw[2][2];
+        auto b_load = [&](int k, float4 (&o)[2], float4 (&ow)[2]) {
+            const char* q = sb + 2 * k * ROWB;
+            o[0] = *reinterpret_cast<const float4*>(q); o[1] = *reinterpret_cast<const float4*>(q + 16);
+            if (BAYES) { ow[0] = *reinterpret_cast<const float4*>(q + TB); ow[1] = *reinterpret_cast<const float4*>(q + TB + 16); }
+        };
+        b_load(0, b[0], bw[0]);
+#pragma unroll
+        for (int k = 0; k < KS; ++k) {
+            if (k + 1 < KS) b_load(k + 1, b[(k + 1) & 1], bw[(k + 1) & 1]);
+            const float4* o = b[k & 1];
+            const float4* ow = bw[k & 1];
+            const float bv[NJT] = {o[0].x, o[0].y, o[0].z, o[0].w, o[1].x, o[1].y, o[1].z, o[1].w};
+            const float a1 = dz[k];
+            const float a2 = __uint_as_float(__float_as_uint(a1) ^ ((w << (31 - 2 * k)) & 0x80000000u));
+#pragma unroll
+            for (int jt = 0; jt < NJT; ++jt) acc1[jt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bv[jt], acc1[jt], 0, 0, 0);
+            if (BAYES) {
+                const float wv[NJT] = {ow[0].x, ow[0].y, ow[0].z, ow[0].w, ow[1].x, ow[1].y, ow[1].z, ow[1].w};
+#pragma unroll
+                for (int jt = 0; jt < NJT; ++jt) acc2[jt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, wv[jt], acc2[jt], 0, 0, 0);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next stage landed (the DMA is invisible to hipcc's own counting)
+        __syncthreads();                                     // ... and this one is fully consumed
+#pragma unroll
+        for (int k = 0; k < KS; ++k) dz[k] = dzn[k];
+        w = wn;
+    }
+
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int irow = i0 + rowmap(r, half);
+        float v[NJT];
+        uint32_t si = 0u;                    // s_in word of the lane's eight hidden units 8 il .. 8 il + 7 (all in word il / 4)
+        if (BAYES) si = INJ ? p.sinbits[(int64_t)irow * NJT + (il >> 2)] : sign_word(p.si_k0, p.si_k1, (uint32_t)irow, (uint32_t)(il >> 2));
+#pragma unroll
+        for (int jt = 0; jt < NJT; ++jt) {
+            v[jt] = acc1[jt][r];
+            if (BAYES) { const float y2 = acc2[jt][r]; v[jt] += ((si >> ((8 * il + jt) & 31)) & 1u) ? -y2 : y2; }
+        }
+        float* dst = p.slab + ((int64_t)cg * p.Bpad + irow) * H + 8 * il;
+        *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1275,16 +1412,25 @@ __global__ __launch_bounds__(512) void k_out_fwd_h3e(OutFwd6Args pp) {
 // ------------------------------------------------------------------------------------------------
 template <int H, bool BAYES>
 static void fwd_dispatch(hipStream_t st, const FusedOut& f, const OutFwdArgs& a, const SpecialArgs& s, int grid, int phases) {
-    constexpr int STAGE = (BAYES ? 2 : 1) * BN * 4 * H + 512;
+    constexpr int HS = H > 128 ? 128 : H;                                   // hidden units per LDS stage (out_fwd_f32_body)
+    constexpr int STAGE = (BAYES ? 2 : 1) * BN * 4 * HS + 512;
     const size_t lds = 2 * STAGE;
     const bool dh = f.dh != nullptr;
     const bool inj = BAYES && (f.s_out.inj != nullptr || f.s_in.inj != nullptr);  // packed images instead of the hash
+    // H = 256: the forward kernel without its dh products, then k_out_dh on the dz it stored (before the sparse fix-up of phase 4 patches dzT)
 #define NTF_LAUNCH_FWD(TR, DHF)                                                                                           \
     do {                                                                                                                  \
-        auto kf = inj ? k_out_fwd<H, BAYES, TR, DHF, BAYES> : k_out_fwd<H, BAYES, TR, DHF, false>;                        \
+        constexpr bool DHK = (DHF) && H <= 128;                                                                           \
+        auto kf = inj ? k_out_fwd<H, BAYES, TR, DHK, BAYES> : k_out_fwd<H, BAYES, TR, DHK, false>;                        \
         if (phases & 2) {                                                                                                 \
             set_max_lds(reinterpret_cast<const void*>(kf), (int)lds); \
             hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, st, a);                                                    \
+            if ((DHF) && H == 256) {                                                                                      \
+                auto kd = inj ? k_out_dh<BAYES, BAYES> : k_out_dh<BAYES, false>;                                          \
+                const size_t ldsd = 2 * (size_t)(BAYES ? 2 : 1) * 32 * 4 * 256;                                           \
+                set_max_lds(reinterpret_cast<const void*>(kd), (int)ldsd);                                                \
+                hipLaunchKernelGGL(kd, dim3(grid), dim3(256), ldsd, st, a);                                               \
+            }                                                                                                             \
         }                                                                                                                 \
         if (phases & 4) launch_out_special(st, H, BAYES, TR, DHF, s);                                                     \
     } while (0)
@@ -1427,7 +1573,7 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
         return;
     }
 #define NTF_H(HH) do { if (f.bayes) fwd_dispatch<HH, true>(st, f, a, s, grid, phases); else fwd_dispatch<HH, false>(st, f, a, s, grid, phases); } while (0)
-    if (f.H == 128) NTF_H(128); else if (f.H == 64) NTF_H(64); else NTF_H(32);
+    if (f.H == 256) NTF_H(256); else if (f.H == 128) NTF_H(128); else if (f.H == 64) NTF_H(64); else NTF_H(32);
 #undef NTF_H
 }
 

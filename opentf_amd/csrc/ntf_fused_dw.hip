@@ -104,8 +104,10 @@ __device__ __forceinline__ void dw_produce_finish(const DwArgs& p, float kl, flo
     if (threadIdx.x == 0) { double t = 0.0; for (int w = 0; w < nwaves; ++w) t += red[w]; atomicAdd(p.nx_kl, t * p.nx_klw); }
 }
 
-template <int H, bool BAYES, bool ADAM>
-__device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem) {  // ADAM: see DwArgs
+// HG > H: the layer's rows are HG wide and this workgroup owns the hidden units [jh H, (jh + 1) H) of its experts (H = 256 as two launches of H = 128's
+// shape per expert tile, k_out_dw_h2): the epilogue is element-wise per weight; the bias gradients belong to the jh = 0 workgroups.
+template <int H, bool BAYES, bool ADAM, int HG = H>
+__device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem, int jh = 0) {  // ADAM: see DwArgs
     constexpr int NJT = H / 32;
     constexpr int KB = 32;                  // batch rows per K block
     constexpr int HROW = 4 * H;
@@ -142,7 +144,8 @@ __device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem) {  
         for (int n = 0; n < (HI + DW_WAVES - 1) / DW_WAVES; ++n) {
             const int inst = wave_u * ((HI + DW_WAVES - 1) / DW_WAVES) + n;
             if (inst < HI) {
-                const int64_t goff = (int64_t)ib * KB * H + inst * 256 + lane * 4;  // h tile rows are contiguous in memory
+                int64_t goff = (int64_t)ib * KB * H + inst * 256 + lane * 4;  // h tile rows are contiguous in memory
+                if constexpr (HG != H) { const int f = inst * 256 + lane * 4; goff = (int64_t)(ib * KB + f / H) * HG + jh * H + f % H; }
                 glds16(p.h + goff, sb + TA + inst * 1024);
                 if (BAYES) glds16(p.hs + goff, sb + TA + TH + inst * 1024);
             }
@@ -210,14 +213,14 @@ __device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem) {  
 
     sum1 += __shfl_xor(sum1, 32, 64);
     sum2 += __shfl_xor(sum2, 32, 64);
-    if (half == 0 && c < p.M) { p.g_b[c] = sum1; if (BAYES) p.g_bp[c] = sum2; }
+    if (half == 0 && c < p.M && jh == 0) { p.g_b[c] = sum1; if (BAYES) p.g_bp[c] = sum2; }
 
     float nx_kl = 0.f, nx_amax = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int cr = c0 + wave * 32 + rowmap(r, half);
         if (cr >= p.M) continue;
-        const int64_t idx0 = (int64_t)cr * H + NJT * il;  // NJT consecutive hidden units per lane: one wide access per array
+        const int64_t idx0 = (int64_t)cr * HG + jh * H + NJT * il;  // NJT consecutive hidden units per lane: one wide access per array
         float gm[NJT], gr[NJT], pm[NJT], pr[NJT];
 #pragma unroll
         for (int jt = 0; jt < NJT; ++jt) {
@@ -248,16 +251,22 @@ __device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem) {  
                     p.m_rho[idx0 + jt] = m2; p.v_rho[idx0 + jt] = v2;
                 }
             }
-            if constexpr (H == 128) { if (p.produce) { if constexpr (BAYES) dw_produce_next(p, idx0, nmu, nrho, nx_kl, nx_amax); else dw_produce_next_fnn(p, idx0, nmu, nx_amax); } }   // (this kernel as the fp16x3 step's range fallback)
+            if constexpr (H == 128 && HG == 128) { if (p.produce) { if constexpr (BAYES) dw_produce_next(p, idx0, nmu, nrho, nx_kl, nx_amax); else dw_produce_next_fnn(p, idx0, nmu, nx_amax); } }   // (this kernel as the fp16x3 step's range fallback)
         }
     }
-    if constexpr (ADAM && H == 128) { if (p.produce) dw_produce_finish<BAYES>(p, nx_kl, nx_amax, reinterpret_cast<double*>(smem), DW_WAVES); }
+    if constexpr (ADAM && H == 128 && HG == 128) { if (p.produce) dw_produce_finish<BAYES>(p, nx_kl, nx_amax, reinterpret_cast<double*>(smem), DW_WAVES); }
 }
 
 template <int H, bool BAYES, bool ADAM>
 __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw(DwArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     out_dw_f32_body<H, BAYES, ADAM>(p, smem);
+}
+// H = 256: blockIdx.y = the hidden half of the expert tile blockIdx.x
+template <bool BAYES, bool ADAM>
+__global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_h2(DwArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    out_dw_f32_body<128, BAYES, ADAM, 256>(p, smem, (int)blockIdx.y);
 }
 // the same as the range FALLBACK behind a split-product kernel that cannot run the f32 body itself (k_out_dw_q, the split-K launches): it runs only in a step whose
 // range flag is raised - in every other step it is a no-op on the critical path, so it is launched on ONE round of workgroups that walk the tiles (p.ntile of
@@ -853,6 +862,14 @@ void launch_fused_out_dw(hipStream_t st, const FusedDw& f) {
     const bool guard = f.bf16x6 && f.np == 2 && f.rflag != nullptr;
     a.sT = reinterpret_cast<const uint32_t*>(ws + w.sbitsT);
     a.ksplit = 1; a.part = nullptr; a.slab = 0; a.part_row0 = 0;
+    if (f.H == 256 && !f.fallback_only) {   // exact-f32 only (no split-product kernels at this width): each 256-expert tile as two hidden-half workgroups
+        const size_t lds = 2 * ((size_t)DW_TC * 32 * 4 + (size_t)(f.bayes ? 2 : 1) * 32 * 4 * 128);
+#define NTF_DWH(BY, AD) do { auto kf = k_out_dw_h2<BY, AD>; set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);              \
+        hipLaunchKernelGGL(kf, dim3(grid, 2), dim3(64 * DW_WAVES), lds, st, a); } while (0)
+        if (f.bayes) { if (f.adam) NTF_DWH(true, true); else NTF_DWH(true, false); } else { if (f.adam) NTF_DWH(false, true); else NTF_DWH(false, false); }
+#undef NTF_DWH
+        return;
+    }
     if (f.fallback_only) {   // the exact-f32 kernel of a step whose split-product launches (several, e.g. the tail split of a whole step) were issued with no_fallback
         if (!guard) return;
         a.rmode = 2; a.a_scale = f.a_scale; a.unscale = 1.f / (f.a_scale * f.h_scale);

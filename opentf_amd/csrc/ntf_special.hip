@@ -125,7 +125,7 @@ void launch_out_special(hipStream_t st, int H, bool bayes, bool train, bool dh, 
         else if (dh) hipLaunchKernelGGL((k_out_special<HH, BY, true, true>), dim3(s.B), dim3(64), 0, st, s);                                  \
         else hipLaunchKernelGGL((k_out_special<HH, BY, true, false>), dim3(s.B), dim3(64), 0, st, s); } while (0)
 #define NTF_SPH(HH) do { if (bayes) NTF_SPK(HH, true); else NTF_SPK(HH, false); } while (0)
-    if (H == 128) NTF_SPH(128); else if (H == 64) NTF_SPH(64); else NTF_SPH(32);
+    if (H == 256) NTF_SPH(256); else if (H == 128) NTF_SPH(128); else if (H == 64) NTF_SPH(64); else NTF_SPH(32);
 #undef NTF_SPH
 #undef NTF_SPK
 }

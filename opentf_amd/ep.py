@@ -48,8 +48,8 @@ def expert_shards(M: int, world: int):
 
 
 def can_shard(dims, world: int) -> bool:
-    """the fused output-layer path (h[-1] in {32, 64, 128}) and at least one 256-expert tile per rank"""
-    return len(dims) >= 2 and dims[-2] in (32, 64, 128) and -(-int(dims[-1]) // TILE) >= world
+    """the fused output-layer path (h[-1] in {32, 64, 128, 256}) and at least one 256-expert tile per rank"""
+    return len(dims) >= 2 and dims[-2] in (32, 64, 128, 256) and -(-int(dims[-1]) // TILE) >= world
 
 
 class ExpertParallel:

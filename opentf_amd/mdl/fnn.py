@@ -161,7 +161,7 @@ def make_fnn(base):
             """How torchrun's processes share a training step (world > 1).  "ep": the output layer is split along the expert axis - every GPU
             steps the whole minibatch of cfg.b rows on its experts, the only exchange is d(hidden) (opentf_amd/ep.py); "dp": the rows are
             split, the gradients reduce-scattered (opentf_amd/dp.py).  NTF_PARALLEL = ep | dp forces one; default: ep whenever the model
-            shards (h[-1] in {32, 64, 128} and at least one 256-expert tile per GPU) - it moves ~500x fewer bytes per step."""
+            shards (h[-1] in {32, 64, 128, 256} and at least one 256-expert tile per GPU) - it moves ~500x fewer bytes per step."""
             from ..ep import can_shard
             want = os.environ.get("NTF_PARALLEL", "auto").lower()
             if world <= 1:   # NTF_PARALLEL=ep with NTF_EP_FORCE_EXCHANGE=1: the sharded code path on one GPU (validation; the shard is the whole layer)
