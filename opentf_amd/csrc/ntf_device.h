@@ -61,14 +61,6 @@ __device__ __forceinline__ void normal4(const NormalSpec& s, int64_t q, int64_t 
     z[2] = r1 * __builtin_amdgcn_cosf(a1); z[3] = r1 * __builtin_amdgcn_sinf(a1);
 }
 
-// two f32 -> three packed bf16 pairs (element 0 in the low half)
-__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p1) : "v"(x0), "v"(x1));
-    const float r0 = x0 - __uint_as_float(p1 << 16), r1 = x1 - __uint_as_float(p1 & 0xFFFF0000u);
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p2) : "v"(r0), "v"(r1));
-    const float s0 = r0 - __uint_as_float(p2 << 16), s1 = r1 - __uint_as_float(p2 & 0xFFFF0000u);
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p3) : "v"(s0), "v"(s1));
-}
 // two f32 -> two packed fp16 pairs, x = x1 + x2 to 22 bits (both conversions round to nearest; fp16 subnormals are honoured by the MFMA)
 __device__ __forceinline__ void split_pair_h(float x0, float x1, uint32_t& p1, uint32_t& p2) {
     typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
@@ -79,31 +71,29 @@ __device__ __forceinline__ void split_pair_h(float x0, float x1, uint32_t& p1, u
     const h2_t a2 = __builtin_convertvector(r, h2_t);
     p1 = __builtin_bit_cast(uint32_t, a1); p2 = __builtin_bit_cast(uint32_t, a2);
 }
-// NP = 3: bf16 three-way split (bf16x6 products);  NP = 2: fp16 two-way split of x * scale (fp16x3 products), scale an exact power of two
-template <int NP> __device__ __forceinline__ void split_pair_np(float x0, float x1, float scale, uint32_t (&p)[3]) {
-    if (NP == 3) split_pair(x0, x1, p[0], p[1], p[2]);
-    else {   // saturate at the fp16 range instead of producing inf (weights beyond +-255, activations beyond +-4094: far outside any trained model)
-        split_pair_h(__builtin_amdgcn_fmed3f(x0 * scale, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(x1 * scale, -65504.f, 65504.f), p[0], p[1]); p[2] = 0u;
-    }
+// the fp16 two-way split of x * scale (fp16x3 products), scale an exact power of two: p[0] = the hi plane pair, p[1] = the lo plane pair
+__device__ __forceinline__ void split_pair_scaled(float x0, float x1, float scale, uint32_t (&p)[2]) {
+    // saturate at the fp16 range instead of producing inf (weights beyond +-255, activations beyond +-4094: far outside any trained model)
+    split_pair_h(__builtin_amdgcn_fmed3f(x0 * scale, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(x1 * scale, -65504.f, 65504.f), p[0], p[1]);
 }
-// split planes of a row-major [M, H] f32 matrix for the split-product forward kernel: [tile of 32 rows][plane 0..NP-1][row in tile][H];
+// split planes of a row-major [M, H] f32 matrix for the split-product forward kernels: [tile of 32 rows][plane hi, lo][row in tile][H];
 // stores the planes of the element pair (row, j), (row, j+1), j even
-template <int NP> __device__ __forceinline__ void planes_store_pair(uint16_t* planes, int64_t row, int j, int H, float x0, float x1, float scale) {
-    uint32_t p[3];
-    split_pair_np<NP>(x0, x1, scale, p);
-    uint32_t* o = reinterpret_cast<uint32_t*>(planes + ((row >> 5) * (32 * NP) + (row & 31)) * H + j);
+__device__ __forceinline__ void planes_store_pair(uint16_t* planes, int64_t row, int j, int H, float x0, float x1, float scale) {
+    uint32_t p[2];
+    split_pair_scaled(x0, x1, scale, p);
+    uint32_t* o = reinterpret_cast<uint32_t*>(planes + ((row >> 5) * 64 + (row & 31)) * H + j);
 #pragma unroll
-    for (int q = 0; q < NP; ++q) o[(size_t)q * 16 * H] = p[q];
+    for (int q = 0; q < 2; ++q) o[(size_t)q * 16 * H] = p[q];
 }
 
 // the same for four consecutive elements (row, j .. j+3), j % 4 == 0: one 8-byte store per plane
-template <int NP> __device__ __forceinline__ void planes_store_quad(uint16_t* planes, int64_t row, int j, int H, float x0, float x1, float x2, float x3, float scale) {
-    uint32_t p[3], q[3];
-    split_pair_np<NP>(x0, x1, scale, p);
-    split_pair_np<NP>(x2, x3, scale, q);
-    uint2* o = reinterpret_cast<uint2*>(planes + ((row >> 5) * (32 * NP) + (row & 31)) * H + j);
+__device__ __forceinline__ void planes_store_quad(uint16_t* planes, int64_t row, int j, int H, float x0, float x1, float x2, float x3, float scale) {
+    uint32_t p[2], q[2];
+    split_pair_scaled(x0, x1, scale, p);
+    split_pair_scaled(x2, x3, scale, q);
+    uint2* o = reinterpret_cast<uint2*>(planes + ((row >> 5) * 64 + (row & 31)) * H + j);
 #pragma unroll
-    for (int k = 0; k < NP; ++k) o[(size_t)k * 8 * H] = make_uint2(p[k], q[k]);   // plane stride = 32 rows x H elements = 64 H bytes = 8 H uint2
+    for (int k = 0; k < 2; ++k) o[(size_t)k * 8 * H] = make_uint2(p[k], q[k]);   // plane stride = 32 rows x H elements = 64 H bytes = 8 H uint2
 }
 
 // the same on the hardware exp2 / log2 / rcp (1 ulp each): log1p(e) = log(u) * e / (u - 1) with u = fl(1 + e) cancels the rounding of

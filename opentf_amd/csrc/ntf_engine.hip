@@ -92,14 +92,7 @@ struct ntf_engine {
     float* gemm_slab = nullptr;       // split-K partial sums of the generic GEMM
     double* d_kl = nullptr; double* d_acc = nullptr; int64_t* d_acc_steps = nullptr;
     int fwd_kernel = -1;
-#ifdef NTF_DIAG
-    // NTF_COSCHED=ncg (a -DNTF_DIAG build; RESULTS ARE GARBAGE): the co-scheduling experiment of DESIGN.md section 4 - the forward kernel on NRB * ncg workgroups (one
-    // per CU) while, on the side stream, the dW + Adam kernel of the PREVIOUS step's operands fills the CUs it leaves free; the step's own dW launch is skipped
-    int cosched = 0; bool cosched_have = false; FusedDw cosched_dw; hipEvent_t ev_co0 = nullptr, ev_co1 = nullptr;
-#endif
     int lean = 1;                     // NTF_LEAN=0: the dW epilogue also writes the f32 copy of the next step's sigma * eps (round 3's 64 B per pair; A/B runs)
-    int dw_tail = 0;                  // NTF_DW_TAIL=1|2|3 (-DNTF_DIAG builds only; measured SLOWER): the last partial round of half-tiles as split-K launches (dw_launch_whole)
-    int n_cu = 256;
     int dw_ksplit = 0;                // 0: automatic (few expert tiles -> split the dW kernel's K range), else forced (NTF_DW_KSPLIT)
     int32_t* d_range = nullptr;       // fp16x3 range guard (lives behind d_kl[0]): [0] raised for the current step, [1] steps that fell back to the f32 kernels
     int64_t range_fallbacks_host = 0; // inference calls redone on the generic path for the same reason
@@ -152,7 +145,7 @@ struct ntf_engine {
     // unigram_b staging (sparse per-batch alias table)
     std::vector<int32_t> ub_entries; void* ub_host[2] = {nullptr, nullptr}; void* ub_dev[2] = {nullptr, nullptr}; hipEvent_t ub_ev[2] = {nullptr, nullptr};
     bool ub_used[2] = {false, false}; size_t ub_cap = 0; int ub_slot = 0; int ub_nsup[2] = {0, 0}; double ub_total[2] = {0, 0};
-    uint16_t* pl_mu = nullptr; uint16_t* pl_wp = nullptr;   // bf16 split planes of the output layer's mu / Wp (bf16x6 arithmetic)
+    uint16_t* pl_mu = nullptr; uint16_t* pl_wp = nullptr;   // fp16 split planes of the output layer's mu / Wp (fp16x3 arithmetic)
     hipStream_t st2 = nullptr;        // side stream: Adam of finished expert chunks runs beside the dW kernel of the next chunk
     hipEvent_t ev_chunk = nullptr, ev_side = nullptr;
     hipStream_t st3 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the hidden layers' backward runs beside the output layer's dW kernel
@@ -258,14 +251,7 @@ extern "C" int ntf_engine_create(const ntf_config* cfg, ntf_engine** out) {
     }
     if (const char* ks = getenv("NTF_DW_KSPLIT")) e->dw_ksplit = atoi(ks);
     if (const char* ln = getenv("NTF_LEAN")) e->lean = atoi(ln);
-#ifdef NTF_DIAG
-    if (const char* dt = getenv("NTF_DW_TAIL")) e->dw_tail = atoi(dt);
-#endif
-    { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && ncu > 0) e->n_cu = ncu; }
     if (const char* hp = getenv("NTF_HEAD_PREFETCH")) e->head_prefetch = atoi(hp);
-#ifdef NTF_DIAG
-    if (const char* co = getenv("NTF_COSCHED")) e->cosched = atoi(co);
-#endif
     if (const char* pf = getenv("NTF_PREFETCH")) e->prefetch = atoi(pf);
     if (const char* hd = getenv("NTF_HEAD")) e->head = atoi(hd);
     if (const char* mb = getenv("NTF_MERGE_BIAS")) e->merge_bias = atoi(mb);
@@ -605,8 +591,7 @@ static NormalSpec normal_spec(ntf_engine* e, const StepCtx& c, int layer, int te
     return s;
 }
 
-// split-product arithmetic of the fused output layer: number of planes and the exact power-of-two scales of fp16x3
-static inline int mfma_np(const ntf_engine*) { return 2; }   // fp16x3: two fp16 planes per operand (the three-plane bf16x6 arithmetic was retired in round 6)
+// split-product arithmetic of the fused output layer: the exact power-of-two scales of fp16x3
 constexpr float kW16Scale = 256.f, kH16Scale = 16.f;          // weights (|w| << 256), hidden activations (|h| << 4096)
 static inline float dz_scale16(const ntf_engine* e, int global_B) {   // |dz| <= max(tpw, tnw) / B  ->  scaled below 2^14
     const float dzmax = std::max(std::max(e->cfg.tpw, e->cfg.tnw), 1e-30f) / (float)std::max(global_B, 1);
@@ -821,9 +806,9 @@ static void head_launch_multihot(ntf_engine* e, hipStream_t st, const StepCtx& c
         FusedOut f;
         f.B = c.B; f.H = lo.in; f.M = M; f.bayes = 1; f.train = 1; f.h = e->act[1]; f.ws = ws;
         f.s_in = sign_spec(e, c, e->L - 1, T_S_IN, lo.in); f.s_out = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out);
-        f.bf16x6 = 1; f.np = mfma_np(e); f.h_scale = kH16Scale; f.w_scale = kW16Scale; f.planes_ready = 1; f.h_ready = 0; f.rflag = rflag;
+        f.split = 1; f.h_scale = kH16Scale; f.w_scale = kW16Scale; f.planes_ready = 1; f.h_ready = 0; f.rflag = rflag;
         launch_fused_out_fwd(st, f, 1);
-        if (want_planes) launch_fused_prep_planes(st, c.B, lo.in, M, 1, ws, mfma_np(e), kH16Scale, nullptr, 0, 2);
+        if (want_planes) launch_fused_prep_planes(st, c.B, lo.in, M, 1, ws, kH16Scale, nullptr, 0, 2);
     }
     if (with_bias) launch_flipout_perturb(st, e->P + lo.off[NTF_P_RHO_BIAS], kl ? e->P + lo.off[NTF_P_BIAS] : nullptr, lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1], 1.0 / (double)e->Mg, kl);
 }
@@ -840,7 +825,7 @@ static void head_launch(ntf_engine* e, hipStream_t st, const StepCtx& c, char* w
     a.X = e->act[0]; a.act1 = e->act[1]; a.hz = wp.hz; a.hs = wp.hs; a.sinbits = wp.sinbits;
     a.hb = want_planes ? wp.hb : nullptr; a.sinT = wp.sinT;
     a.h_scale = kH16Scale;
-    const bool guard = mfma_np(e) == 2 && rflag != nullptr;
+    const bool guard = rflag != nullptr;
     a.h_limit = guard ? 65504.f / kH16Scale : 0.f; a.rflag = guard ? rflag : nullptr;
     if (e->cfg.bayesian) {
         const double share = e->ep ? 1.0 / (double)e->ep_world : 1.0;   // expert shards: a replicated layer's KL is counted once over the shards
@@ -854,43 +839,6 @@ static void head_launch(ntf_engine* e, hipStream_t st, const StepCtx& c, char* w
         }
     }
     launch_head(st, a);
-}
-
-// The output layer's dW (+ Adam + next-step operands) of a whole step: ONE k_out_dw_q launch.
-// Round 5 experiment, kept for -DNTF_DIAG builds (NTF_DW_TAIL=1|2|3) because VERDICT r4 asked for it and the numbers are the answer: the launch cut at its last whole
-// round of half-tiles (2 x CUs slots) - [0, rounds x slots) to k_out_dw_q, every slot the same number of tiles, the rest to the split-K form of k_out_dw_p2 +
-// k_out_dw_finish (behind it, in front of it, or beside it on another stream).  Measured at config 2 (profiles/r5_dw_tail.md): the 1 536-tile launch alone 0.528 ms (three
-// rounds cost 0.176 ms each; the fourth, partial round of the one-launch form costs only 0.07 ms: a CU left with one workgroup runs it faster), the tail 0.088 + 0.078 ms -
-// 0.66-0.68 ms against 0.60.  Every launch pays its own ramp (first main loops: HBM idle) and tail (last epilogues: matrix pipe idle), ~0.1 ms; cutting the launch adds one.
-static int dw_launch_whole(ntf_engine* e, const FusedDw& f) {
-#ifndef NTF_DIAG
-    launch_fused_out_dw(e->st, f);
-    return NTF_OK;
-#else
-    const int slots = 2 * e->n_cu, total_q = (f.M + 127) / 128, full_q = total_q / slots * slots, tail_q = total_q - full_q;
-    const bool can = e->dw_tail > 0 && f.dz_packed && f.adam && f.ksplit <= 1 && f.wg_count <= 0 && f.H == 128 && full_q > 0 && tail_q > 0 &&
-                     tail_q * 10 <= slots * 8 && e->Zout != nullptr;
-    if (!can) { launch_fused_out_dw(e->st, f); return NTF_OK; }
-    const int tail_p2 = (tail_q + 1) / 2, nib = fused_ldb(f.B) / 32;
-    // K ranges per tail tile: as many as fill whole rounds of one 256-expert workgroup per CU (two rounds unless the tail is tiny), at least 4 K blocks each
-    int ks = std::max(1, std::min({2 * e->n_cu / tail_p2, 8, std::max(1, nib / 4)}));
-    if (const char* v = getenv("NTF_DW_TAIL_KS")) ks = std::max(1, atoi(v));
-    if (ks < 2 || fused_dw_part_floats(tail_p2 * 256, f.H, ks) > (int64_t)e->cfg.max_batch * e->cfg.dims[e->L]) { launch_fused_out_dw(e->st, f); return NTF_OK; }
-    FusedDw fm = f; fm.wg_begin = 0; fm.wg_count = full_q / 2; fm.no_fallback = 1;
-    FusedDw ft = f; ft.wg_begin = full_q / 2; ft.wg_count = tail_p2; ft.ksplit = ks; ft.part = e->Zout; ft.no_fallback = 1;
-    if (e->dw_tail == 3) {
-        if (!e->st2) { HIPCHK(e, hipStreamCreateWithFlags(&e->st2, hipStreamNonBlocking)); HIPCHK(e, hipEventCreateWithFlags(&e->ev_chunk, hipEventDisableTiming)); HIPCHK(e, hipEventCreateWithFlags(&e->ev_side, hipEventDisableTiming)); }
-        HIPCHK(e, hipEventRecord(e->ev_chunk, e->st));
-        HIPCHK(e, hipStreamWaitEvent(e->st2, e->ev_chunk, 0));
-        launch_fused_out_dw(e->st, fm);
-        launch_fused_out_dw(e->st2, ft);
-        HIPCHK(e, hipEventRecord(e->ev_side, e->st2));
-        HIPCHK(e, hipStreamWaitEvent(e->st, e->ev_side, 0));
-    } else if (e->dw_tail == 2) { launch_fused_out_dw(e->st, ft); launch_fused_out_dw(e->st, fm); }
-    else { launch_fused_out_dw(e->st, fm); launch_fused_out_dw(e->st, ft); }
-    if (f.rflag) { FusedDw fb = f; fb.fallback_only = 1; launch_fused_out_dw(e->st, fb); }
-    return NTF_OK;
-#endif
 }
 
 // Data-parallel pipelining of the step's head (round 5).  The parameters of the output layer arrive by all-gather in the dW chunks' ranges (ntf_dw_chunk_range: 65 536
@@ -962,7 +910,7 @@ static int prefetch_next_head(ntf_engine* e, const StepCtx& c, hipStream_t head_
     if ((r = sample_negatives(e, n))) return r;
     if (e->cfg.bayesian) {
         const SignSpec so = sign_spec(e, n, e->L - 1, T_S_OUT, lo.out);
-        Scope t(e, F_OUT_FUSED_AUX); launch_fused_prep_planes(e->st, n.B, lo.in, M, 1, ws_next, 2, kH16Scale, &so, 0, 1);
+        Scope t(e, F_OUT_FUSED_AUX); launch_fused_prep_planes(e->st, n.B, lo.in, M, 1, ws_next, kH16Scale, &so, 0, 1);
     }
     HIPCHK(e, hipEventRecord(e->ev_aux, e->st4));
     e->st = head_st;
@@ -1026,7 +974,7 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
     // the step's KL sum and fp16x3 range flag: zero, or the values the previous step's dW epilogue produced for this one (moved into place by that step's Adam launch
     // if pre_rotated, else here)
     // (an evaluation step of a chain that has the output layer's KL term kept: the sum starts from it, the lean producer below adds none)
-    chain_ok = c.chain && !c.train && fused && e->cfg.bayesian && !use_pre && !nfr && !c.inj && e->pl_wp && e->pl_mu && mfma_np(e) == 2 && range_ptr(e) && e->d_chain;
+    chain_ok = c.chain && !c.train && fused && e->cfg.bayesian && !use_pre && !nfr && !c.inj && e->pl_wp && e->pl_mu && range_ptr(e) && e->d_chain;
     chain_lean = chain_ok && e->chain_valid; chain_fill = chain_ok && !e->chain_valid;
     if (chain_fill) HIPCHK(e, hipMemsetAsync(e->d_chain, 0, 16, e->st));
     if (chain_fill) { pch.kl_out2 = e->d_chain; pch.mu_flag_out = reinterpret_cast<int*>(e->d_chain + 1); e->chain_valid = true; }
@@ -1051,7 +999,7 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
             e->st = e->st3;
             { Scope t(e, F_FLIPOUT_OPERAND);
               launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT], chain_lean ? nullptr : e->P + lo.off[NTF_P_WEIGHT], lo.nw(), normal_spec(e, c, e->L - 1, T_EPS_W), chain_nof32 ? nullptr : e->Wp[e->L - 1],
-                                     1.0 / out_nw, e->d_kl, e->pl_wp, (e->pl_wp && !chain_lean) ? e->pl_mu : nullptr, e->P + lo.off[NTF_P_WEIGHT], lo.in, mfma_np(e), kW16Scale, range_ptr(e), nullptr, pch); }
+                                     1.0 / out_nw, e->d_kl, e->pl_wp, (e->pl_wp && !chain_lean) ? e->pl_mu : nullptr, e->P + lo.off[NTF_P_WEIGHT], lo.in, kW16Scale, range_ptr(e), nullptr, pch); }
             HIPCHK(e, hipEventRecord(e->ev_join, e->st3));
             prod_side = true;
         }
@@ -1061,11 +1009,11 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
             launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS], e->P + lo.off[NTF_P_BIAS], lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1],
                                    1.0 / out_nb, e->d_kl); }
         if ((r = sample_negatives(e, c))) return r;
-        if (c.train && e->cfg.bayesian && e->cfg.mfma != NTF_MFMA_F32 && mfma_np(e) == 2 && lo.in == 128 && e->pl_mu != nullptr) {
+        if (c.train && e->cfg.bayesian && e->cfg.mfma != NTF_MFMA_F32 && lo.in == 128 && e->pl_mu != nullptr) {
             const SignSpec so = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out), si = sign_spec(e, c, e->L - 1, T_S_IN, lo.in);
             if (so.inj == nullptr && si.inj == nullptr) {   // (injected signs: the words are transposed from the packed image k_sign_bits writes on the main stream)
                 Scope t(e, F_OUT_FUSED_AUX);
-                launch_fused_prep_planes(e->st, B, lo.in, M, 1, e->fws, 2, kH16Scale, &so, 0, 1);
+                launch_fused_prep_planes(e->st, B, lo.in, M, 1, e->fws, kH16Scale, &so, 0, 1);
                 swt_aux = true;
             }
         }
@@ -1092,7 +1040,7 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
         if (e->cfg.bayesian) {
             if (!prod_side && !use_pre && !nfr) { Scope t(e, F_FLIPOUT_OPERAND);
               launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT], chain_lean ? nullptr : f.mu, lo.nw(), normal_spec(e, c, e->L - 1, T_EPS_W), chain_nof32 ? nullptr : e->Wp[e->L - 1],
-                                     1.0 / out_nw, e->d_kl, e->pl_wp, (e->pl_wp && !chain_lean) ? e->pl_mu : nullptr, f.mu, lo.in, mfma_np(e), kW16Scale, range_ptr(e), nullptr, pch); }   // + the split planes of Wp and mu
+                                     1.0 / out_nw, e->d_kl, e->pl_wp, (e->pl_wp && !chain_lean) ? e->pl_mu : nullptr, f.mu, lo.in, kW16Scale, range_ptr(e), nullptr, pch); }   // + the split planes of Wp and mu
             if (!aux && !use_head) { Scope t(e, F_FLIPOUT_OPERAND);
               launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS], f.mu_b, lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1],
                                      1.0 / out_nb, e->d_kl); }
@@ -1101,8 +1049,8 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
             f.s_in = sign_spec(e, c, e->L - 1, T_S_IN, lo.in); f.s_out = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out);
         }
         if (!e->cfg.bayesian && use_pre) f.planes_ready = 1;      // (Fnn, round 6: the previous step's dW epilogue wrote the planes of the updated mu)
-        f.bf16x6 = e->pl_mu != nullptr; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp;
-        f.np = mfma_np(e); f.w_scale = kW16Scale; f.h_scale = kH16Scale; f.dz_scale = dz_scale16(e, c.global_B);
+        f.split = e->pl_mu != nullptr; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp;
+        f.w_scale = kW16Scale; f.h_scale = kH16Scale; f.dz_scale = dz_scale16(e, c.global_B);
         f.rflag = range_ptr(e);
         if (e->fwd_kernel >= 0) f.wide = e->fwd_kernel;   // A/B runs: NTF_FWD_KERNEL = 0, 1, 2 (ntf_fused.h), read when the engine is created
         f.eval_kernel = e->eval_kernel;
@@ -1115,8 +1063,8 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
             f.h_ready = 1;
             if (!f.planes_ready) launch_fused_out_fwd(e->st, f, 1);   // (Fnn: the split planes of mu are made per step)
             if (c.train && e->cfg.mfma != NTF_MFMA_F32 && split_products(e) && !swt_aux && !hp_hit) {   // (one stream: the s_out words were not made beside the head)
-                const bool dz_packed = f.np == 2 && lo.in == 128 && e->pl_mu != nullptr;
-                launch_fused_prep_planes(e->st, B, lo.in, M, e->cfg.bayesian, e->fws, f.np, f.h_scale, dz_packed ? &f.s_out : nullptr, 0, 1);
+                const bool dz_packed = lo.in == 128 && e->pl_mu != nullptr;
+                launch_fused_prep_planes(e->st, B, lo.in, M, e->cfg.bayesian, e->fws, f.h_scale, dz_packed ? &f.s_out : nullptr, 0, 1);
             }
         } else {
         { Scope t(e, F_OUT_FUSED_AUX); launch_fused_out_fwd(e->st, f, 1); }
@@ -1124,9 +1072,9 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
                 // operands of the dW kernel that depend on h and on the sign keys only (split planes of h / h*s_in, transposed s_out words): prepared here, in the
                 // step's head (beside the side-stream producer), not between the forward and the dW kernel
                 Scope t(e, F_OUT_FUSED_AUX);
-                const bool dz_packed = f.np == 2 && lo.in == 128 && e->pl_mu != nullptr;
+                const bool dz_packed = lo.in == 128 && e->pl_mu != nullptr;
                 const bool so_inj = e->cfg.bayesian && (f.s_out.inj != nullptr || f.s_in.inj != nullptr);
-                launch_fused_prep_planes(e->st, B, lo.in, M, e->cfg.bayesian, e->fws, f.np, f.h_scale, dz_packed ? &f.s_out : nullptr, so_inj, swt_aux ? 2 : 3);
+                launch_fused_prep_planes(e->st, B, lo.in, M, e->cfg.bayesian, e->fws, f.h_scale, dz_packed ? &f.s_out : nullptr, so_inj, swt_aux ? 2 : 3);
             }
         }
         if (prod_side) HIPCHK(e, hipStreamWaitEvent(e->st, e->ev_join, 0));
@@ -1137,24 +1085,8 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
             // reads one, and makes it here - a capped grid that exits at once unless the range flag is raised (behind the head: k_head may still raise it)
             Scope t(e, F_FLIPOUT_OPERAND);
             launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT], nullptr, lo.nw(), normal_spec(e, c, e->L - 1, T_EPS_W), e->Wp[e->L - 1], 0.0, nullptr,
-                                   nullptr, nullptr, nullptr, 0, 3, 1.f, nullptr, range_ptr(e));
+                                   nullptr, nullptr, nullptr, 0, 1.f, nullptr, range_ptr(e));
         }
-#ifdef NTF_DIAG
-        if (e->cosched > 0 && c.train) {
-            f.ncg_limit = e->cosched;
-            static const bool fwd_only = getenv("NTF_COSCHED_FWD_ONLY") != nullptr;      // the forward kernel alone on its reduced grid (no dW at all in the step)
-            if (e->cosched_have && !fwd_only) {
-                if ((r = side_stream(e))) return r;
-                if (!e->ev_co0) { HIPCHK(e, hipEventCreateWithFlags(&e->ev_co0, hipEventDisableTiming)); HIPCHK(e, hipEventCreateWithFlags(&e->ev_co1, hipEventDisableTiming)); }
-                HIPCHK(e, hipEventRecord(e->ev_co0, e->st));
-                { Scope t(e, F_OUT_FUSED_FWD); launch_fused_out_fwd(e->st, f, 2); }       // enqueued first: its workgroups take their CUs, the dW workgroups the rest
-                HIPCHK(e, hipStreamWaitEvent(e->st3, e->ev_co0, 0));
-                { StreamRestore guard{e, e->st}; e->st = e->st3; Scope t(e, F_OUT_FUSED_DW); launch_fused_out_dw(e->st, e->cosched_dw); }
-                HIPCHK(e, hipEventRecord(e->ev_co1, e->st3));
-                HIPCHK(e, hipStreamWaitEvent(e->st, e->ev_co1, 0));
-            } else { Scope t(e, F_OUT_FUSED_FWD); launch_fused_out_fwd(e->st, f, 2); }
-        } else
-#endif
         if (nfr) {
             // range by range: the caller's callback orders this stream behind the all-gathers of the range's parameter chunks; then its operands (eps, sigma eps, the
             // fp16 planes of sigma eps and mu, its share of the KL) and its forward launch.  The whole-layer exact-f32 launch of a range fallback follows the last range.
@@ -1164,9 +1096,9 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
                 const int64_t r0 = (int64_t)fr[j].t_lo * 64, r1 = std::min<int64_t>((int64_t)fr[j].t_hi * 64, M), o0 = r0 * lo.in, n0 = (r1 - r0) * lo.in;
                 { Scope t(e, F_FLIPOUT_OPERAND);
                   NormalSpec es = normal_spec(e, c, e->L - 1, T_EPS_W); es.qbase += o0 / 4;
-                  const int64_t pl0 = r0 / 32 * (32 * mfma_np(e)) * lo.in;      // the planes of 32-expert tile r0 / 32 (fused_planes_elems layout)
+                  const int64_t pl0 = r0 / 32 * 64 * lo.in;      // the planes of 32-expert tile r0 / 32 (fused_planes_elems layout)
                   launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT] + o0, f.mu + o0, n0, es, e->Wp[e->L - 1] + o0, 1.0 / out_nw, e->d_kl,
-                                         e->pl_wp + pl0, e->pl_mu + pl0, f.mu + o0, lo.in, mfma_np(e), kW16Scale, range_ptr(e)); }
+                                         e->pl_wp + pl0, e->pl_mu + pl0, f.mu + o0, lo.in, kW16Scale, range_ptr(e)); }
                 f.chunk_t_lo = fr[j].t_lo; f.chunk_t_hi = fr[j].t_hi; f.chunk_cg_off = fr[j].cg_off; f.chunk_ncg = fr[j].ncg;
                 { Scope t(e, F_OUT_FUSED_FWD); launch_fused_out_fwd(e->st, f, 2); }
             }
@@ -1230,9 +1162,9 @@ backward:
             f.dzT = e->dZout; f.h = in; f.g_mu = gW; f.g_rho = gRW; f.g_b = gb; f.g_bp = gRb; f.ws = e->fws;
             f.mu = e->P + li.off[NTF_P_WEIGHT];
             f.s_out = sout_; f.s_out_inj = e->cfg.bayesian && (sout_.inj != nullptr || sin_.inj != nullptr);
-            f.bf16x6 = e->cfg.mfma != NTF_MFMA_F32 && split_products(e);   // default: the split products (fp16x3) where the width has them
-            f.np = mfma_np(e); f.a_scale = dz_scale16(e, c.global_B); f.h_scale = kH16Scale; f.rflag = range_ptr(e);
-            f.dz_packed = f.bf16x6 && f.np == 2 && li.in == 128 && e->pl_mu != nullptr;   // the fp16x3 forward kernels (H = 128) store packed plane pairs
+            f.split = e->cfg.mfma != NTF_MFMA_F32 && split_products(e);   // default: the split products (fp16x3) where the width has them
+            f.a_scale = dz_scale16(e, c.global_B); f.h_scale = kH16Scale; f.rflag = range_ptr(e);
+            f.dz_packed = f.split && li.in == 128 && e->pl_mu != nullptr;   // the fp16x3 forward kernels (H = 128) store packed plane pairs
             e->last_dz_packed_scale = f.dz_packed ? f.a_scale : 0.f;
             if (f.dz_packed && !c.defer_dw && !(c.fuse_adam && e->cfg.fuse_adam == 2)) {
                 // few expert tiles (a narrow expert shard under a wide minibatch, or a small model) leave most CUs idle at one workgroup per 256 experts:
@@ -1296,10 +1228,7 @@ backward:
                 }
                 if (e->cfg.bayesian) { e->fin_pend = true; e->fin_eps = normal_spec(e, c, l, T_EPS_B); e->fin_klw = kl_share / ((float)out_nb * (float)c.global_B); }
             }
-#ifdef NTF_DIAG
-            if (e->cosched > 0) { e->cosched_dw = f; e->cosched_have = true; goto dw_done; }      // (this step's dW rides beside the NEXT step's forward kernel: timing only)
-#endif
-            { Scope t(e, F_OUT_FUSED_DW); if ((r = dw_launch_whole(e, f))) return r; }
+            { Scope t(e, F_OUT_FUSED_DW); launch_fused_out_dw(e->st, f); }
         dw_done:;
         } else {
             const float* dZ = last ? e->dZout : e->dAct[(l + 1) & 1];
@@ -1444,10 +1373,6 @@ static int apply_adam(ntf_engine* e) {
     const bool bias_nx = e->cfg.bayesian && e->hp.valid && rotate && e->hp.step == e->step && e->merge_bias;
     NormalSpec nx_eps;
     if (bias_nx) { StepCtx nx; nx.step = e->hp.step; nx.B = e->hp.B; nx.global_B = e->hp.B; nx_eps = normal_spec(e, nx, e->L - 1, T_EPS_B); }
-#ifdef NTF_DIAG
-    static const int diag_skip = getenv("NTF_SKIP") ? atoi(getenv("NTF_SKIP")) : 0;     // timing only (results garbage): 1 - no launch here; 2 - the rotation alone
-    if (diag_skip == 1 && bias_nx) {} else if (diag_skip == 2 && bias_nx) launch_step_scalars(e->st, e->d_kl, 1); else
-#endif
     // ... and, as extra workgroups of the same launch, the f32 copy of the next step's sigma * eps that only a step falling back to the exact-f32 kernels reads (lean: the dW
     // epilogue wrote none) - round 4 issued it as a launch of its own in front of every step, a no-op in all but the rarest.  *only_if: the NEXT step's range flag, still in
     // its slot behind the current one (this launch's last workgroup rotates it) and complete: the dW epilogue and the prefetched head are behind this launch
@@ -1840,7 +1765,7 @@ extern "C" int ntf_get_dlogits(ntf_engine* e, float* host, int64_t count) {
     return NTF_OK;
 }
 
-// one MC pass of the inference through the fused bf16x6 forward kernel: probabilities accumulate in the transposed buffer dZout
+// one MC pass of the inference through the fused split-product forward kernel: probabilities accumulate in the transposed buffer dZout
 static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, int pass, int passes, bool want_unc, bool logits) {
     int r;
     if ((r = check_ready(e, false))) return r;
@@ -1860,18 +1785,18 @@ static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const
     f.mu = e->P + lo.off[NTF_P_WEIGHT]; f.mu_b = e->P + lo.off[NTF_P_BIAS];
     f.tnw = e->cfg.tnw; f.tpw = e->cfg.tpw; f.inv_B = 1.f / (float)B;
     f.dzT = e->dZout; f.dh_slab = e->dh_slab; f.ws = e->fws;
-    f.bf16x6 = 1; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp;
-    f.np = mfma_np(e); f.w_scale = kW16Scale; f.h_scale = kH16Scale; f.dz_scale = 1.f;
+    f.split = 1; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp;
+    f.w_scale = kW16Scale; f.h_scale = kH16Scale; f.dz_scale = 1.f;
     if (e->cfg.bayesian) {
         e->pre_valid = false;   // this pass's operands overwrite any prefetched ones
         // (lean: no f32 copy of sigma * eps - the passes read the planes; a raised range flag sends the whole call to the exact-f32 path, which makes its own operands.  Round 6
         //  measured the producer of pass p + 1 beside the forward kernel of pass p, into a second plane buffer: -2 % on a call, +10 % on an evaluation step - removed,
         //  profiles/r6_eval_prefetch_ab.md)
-        const bool nof32 = e->lean && !inj && mfma_np(e) == 2 && e->pl_wp && range_ptr(e);
+        const bool nof32 = e->lean && !inj && e->pl_wp && range_ptr(e);
         { Scope t(e, F_FLIPOUT_OPERAND);
           // (the planes of mu are the first pass's: the passes of one call run back to back on unchanged parameters, and the range flag they share is read behind the last)
           launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT], nullptr, lo.nw(), normal_spec(e, c, e->L - 1, T_EPS_W), nof32 ? nullptr : e->Wp[e->L - 1], 0.0, e->d_kl,
-                                 e->pl_wp, pass == 0 ? e->pl_mu : nullptr, f.mu, lo.in, mfma_np(e), kW16Scale, range_ptr(e));
+                                 e->pl_wp, pass == 0 ? e->pl_mu : nullptr, f.mu, lo.in, kW16Scale, range_ptr(e));
           launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS], nullptr, lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1], 0.0, e->d_kl); }
         f.wp = e->Wp[e->L - 1]; f.bp = e->bp[e->L - 1];
         f.s_in = sign_spec(e, c, e->L - 1, T_S_IN, lo.in); f.s_out = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out);

@@ -21,7 +21,7 @@ namespace ntf {
 int fused_ldb(int B) { return rup(B, BM); }
 int fused_dw_tile() { return DW_TC; }
 int64_t fused_dw_part_floats(int M, int H, int ksplit) { return (int64_t)ksplit * 2 * ((int64_t)rup(M, DW_TC) * (H + 1)); }
-int64_t fused_planes_elems(int M, int H) { return ((int64_t)M + 63) / 64 * 64 * H * 3; }   // rows padded to the 64-expert tile of k_out_fwd_h3x
+int64_t fused_planes_elems(int M, int H) { return ((int64_t)M + 63) / 64 * 64 * H * 2; }   // hi and lo plane, rows padded to the 64-expert tile of k_out_fwd_h3p / _h3e
 bool fused_supported(int H) { return H == 32 || H == 64 || H == 128 || H == 256; }   // 256: exact-f32 kernels only (no split-product form)
 int fused_loss_slots(int) { return 0; }
 
@@ -488,9 +488,9 @@ __global__ __launch_bounds__(256, 1) void k_out_dh(OutFwdArgs p) {
 
 // ------------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------------
-// forward + loss + dz + dh of the output layer in bf16x6 arithmetic (H = 128).
-// Weights arrive pre-split: k_split_planes writes, per 32-expert tile, the three bf16 planes [32 rows][H] of mu (and of Wp); a tile
-// (2 matrices x 3 planes x 8 KiB + biases) is one LDS stage, filled by LDS-DMA.  In LDS a plane is the dual-use image
+// forward + loss + dz + dh of the output layer in fp16x3 arithmetic (H = 128).
+// Weights arrive pre-split: k_split_planes writes, per 32-expert tile, the two fp16 planes [32 rows][H] of mu (and of Wp); a tile
+// (2 matrices x 2 planes x 8 KiB + biases) is one LDS stage, filled by LDS-DMA.  In LDS a plane is the dual-use image
 //   off(row, ch) = 256*row + 16*(ch ^ (((row&3)<<2) | ((row>>2)&3)))          (ch = 16-byte chunk = 8 hidden units)
 // read by rows (ds_read_b128: A operand of zT = mu . hT, k = hidden unit) and by columns (ds_read_b64_tr_b16: B operand of
 // dh = dz . mu, k = expert), conflict free both ways.  h's planes stay in registers (B operand of zT); the zT accumulator (lane = batch
@@ -498,10 +498,10 @@ __global__ __launch_bounds__(256, 1) void k_out_dh(OutFwdArgs p) {
 // element e of lane half h  <->  expert 16s + 8(e>>2) + 4h + (e&3).
 // ------------------------------------------------------------------------------------------------
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-constexpr int BN6 = 32;   // experts per tile of the bf16x6 forward kernel
+constexpr int BN6 = 32;   // experts per tile of k_out_fwd_b6
 
-// planes[tile][plane][row][H] (bf16) of a row-major f32 matrix W [M, H]; rows past M are zero
-__global__ void k_split_planes(const float* __restrict__ W, int M, int H, int np, float scale, uint16_t* __restrict__ out, int* __restrict__ rflag) {
+// planes[tile][plane][row][H] (fp16 of W * scale) of a row-major f32 matrix W [M, H]; rows past M are zero
+__global__ void k_split_planes(const float* __restrict__ W, int M, int H, float scale, uint16_t* __restrict__ out, int* __restrict__ rflag) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;    // one thread per pair of hidden units
     const int hp = H / 2;
     const int64_t row = t / hp; const int j = (int)(t % hp) * 2;
@@ -509,8 +509,8 @@ __global__ void k_split_planes(const float* __restrict__ W, int M, int H, int np
     if (row >= Mp) return;
     float x0 = 0.f, x1 = 0.f;
     if (row < M) { const float2 v = *reinterpret_cast<const float2*>(W + row * H + j); x0 = v.x; x1 = v.y; }
-    if (np == 2 && rflag && !(fmaxf(fabsf(x0), fabsf(x1)) * scale <= 65504.f)) *rflag = 1;
-    if (np == 3) planes_store_pair<3>(out, row, j, H, x0, x1, 1.f); else planes_store_pair<2>(out, row, j, H, x0, x1, scale);
+    if (rflag && !(fmaxf(fabsf(x0), fabsf(x1)) * scale <= 65504.f)) *rflag = 1;
+    planes_store_pair(out, row, j, H, x0, x1, scale);
 }
 
 struct OutFwd6Args {
@@ -519,7 +519,7 @@ struct OutFwd6Args {
     float pscale; int pacc;          // PROBS: dzT[c][i] (+)= sigmoid(leaky_relu(z)) * pscale; pacc: accumulate onto the previous MC passes
     int plogit;                      // PROBS: store the logit leaky_relu(z) itself instead (ntf_logits: the quantity the 1e-4 parity bar is stated on)
     unsigned long long* stamps;           // diagnostics (k_out_fwd_h3p<.., STAMP>, -DNTF_DIAG builds): per wave cycle sums
-    float h_scale, dz_scale, u_z, u_dh;   // fp16x3 (NP = 2): scales applied to h / dz before their split, and 1/(w scale * h scale), 1/(dz scale * w scale); 1 for bf16x6
+    float h_scale, dz_scale, u_z, u_dh;   // scales applied to h / dz before their split, and 1/(w scale * h scale), 1/(dz scale * w scale)
 };
 // fp16x3 training step: dzT holds, per element, the two fp16 planes of dz * dz_scale packed in one dword (hi | lo << 16) - the split the forward
 // kernel makes anyway for its dh products - so that the dW kernel reads MFMA operands instead of splitting f32 values again
@@ -543,17 +543,17 @@ __device__ __forceinline__ float unpack_planes(uint32_t d, float inv_scale) {
 
 // PROBS (inference, TRAIN = false): instead of the loss, the probabilities sigmoid(leaky_relu(z)) go (accumulated over the MC passes) to the
 // transposed buffer dzT [expert][batch], and lossp gets the row's entropy terms sum_c -p log(p + 1e-15) of this pass (src/mdl/fnn.py:196-208)
-template <bool BAYES, bool TRAIN, bool DH, bool INJ, bool PROBS, int NP>
-__global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {   // NP = 3: bf16x6, NP = 2: fp16x3
+template <bool BAYES, bool TRAIN, bool DH, bool INJ, bool PROBS>
+__global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const OutFwdArgs& p = pp.a;
     constexpr int H = 128, NJT = 4, NKS = H / 16;
     constexpr int PLANE = BN6 * H * 2;          // 8 KiB
-    constexpr int TM = NP * PLANE;              // one matrix of a tile
+    constexpr int TM = 2 * PLANE;               // one matrix of a tile: hi and lo plane
     constexpr int NMAT = BAYES ? 2 : 1;
     constexpr int STAGE = NMAT * TM + 512;      // + two 64-float bias tiles
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, half = lane >> 5;
-    if (NP == 2 && range_guard_skip(p.rflag, p.rmode, false)) return;
+    if (range_guard_skip(p.rflag, p.rmode, false)) return;
 
     int bid = blockIdx.x;
     const int nblk = gridDim.x;
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {   // NP
     const bool row_ok = i < p.B;
 
     // B operand of zT: h[i][16s + 8*half + e] split into planes; sign masks of s_in for the same elements
-    u32x4 hp[NKS][3];
+    u32x4 hp[NKS][2];
     uint32_t sinw[NJT];      // s_in sign words of this row: the signed B operand h*s_in is hp ^ (mask built from these bits), per use
 #pragma unroll
     for (int w = 0; w < NJT; ++w)
@@ -578,9 +578,9 @@ __global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {   // NP
         const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            uint32_t pq[3];
-            split_pair_np<NP>(x[2 * q], x[2 * q + 1], pp.h_scale, pq);
-            hp[s][0][q] = pq[0]; hp[s][1][q] = pq[1]; hp[s][2][q] = pq[2];
+            uint32_t pq[2];
+            split_pair_scaled(x[2 * q], x[2 * q + 1], pp.h_scale, pq);
+            hp[s][0][q] = pq[0]; hp[s][1][q] = pq[1];
         }
     }
     const float rmask = row_ok ? 1.f : 0.f;
@@ -664,33 +664,33 @@ __global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {   // NP
                 pold[r] = pp.pacc ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(dz_rsrc, dz_voff, ((r & 3) + 8 * (r >> 2)) * dz_row_bytes, 0)) : 0.f;
         }
 
-        // ---- zT = mu . hT (+ Wp . (h*s_in)T): 8 k-steps of 16 hidden units; half-groups (k-step, matrix) of 3 fragment reads + 6 MFMAs,
+        // ---- zT = mu . hT (+ Wp . (h*s_in)T): 8 k-steps of 16 hidden units; half-groups (k-step, matrix) of 2 fragment reads + 3 MFMAs,
         // the reads of the next half-group in flight under the MFMAs of the current one
         {
             constexpr int NHG = NKS * NMAT;
-            auto z_load = [&](int hg, u32x4 (&fr)[3]) {
+            auto z_load = [&](int hg, u32x4 (&fr)[2]) {
                 const int s = hg / NMAT, mat = hg % NMAT;
                 const char* ap = sb + 256 * il + 16 * ((2 * s + half) ^ fil) + mat * TM;
 #pragma unroll
-                for (int q = 0; q < NP; ++q) fr[q] = *reinterpret_cast<const u32x4*>(ap + q * PLANE);
+                for (int q = 0; q < 2; ++q) fr[q] = *reinterpret_cast<const u32x4*>(ap + q * PLANE);
             };
-            u32x4 fr[2][3];
+            u32x4 fr[2][2];
             z_load(0, fr[0]);
 #pragma unroll
             for (int hg = 0; hg < NHG; ++hg) {
                 if (hg + 1 < NHG) z_load(hg + 1, fr[(hg + 1) & 1]);
                 asm volatile("" ::: "memory");
                 const int s = hg / NMAT, mat = hg % NMAT;
-                if (mat == 0) X1 = mfma_np<NP>(fr[hg & 1], hp[s], X1);
+                if (mat == 0) X1 = mfma3h(fr[hg & 1], hp[s], X1);
                 else {
-                    u32x4 hs[3];
+                    u32x4 hs[2];
                     const uint32_t w8 = sinw[s >> 1] >> (16 * (s & 1) + 8 * half);
                     u32x4 hm;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) hm[q] = ((w8 << (15 - 2 * q)) & 0x8000u) | ((w8 << (30 - 2 * q)) & 0x80000000u);
 #pragma unroll
-                    for (int q = 0; q < NP; ++q) hs[q] = hp[s][q] ^ hm;
-                    X2 = mfma_np<NP>(fr[hg & 1], hs, X2);
+                    for (int q = 0; q < 2; ++q) hs[q] = hp[s][q] ^ hm;
+                    X2 = mfma3h(fr[hg & 1], hs, X2);
                 }
             }
         }
@@ -715,12 +715,10 @@ __global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {   // NP
             }
             lacc.tile = fmaf(fmaf(__builtin_amdgcn_logf(tt), 0.6931471805599453f, lc), rmask, lacc.tile);
             if (TRAIN) {
-                const float dz = rscale * __builtin_amdgcn_rcpf(tt) * (pos ? 1.f : kLeakySlope);
-                if (NP != 2) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dz), dz_rsrc, dz_voff, cr * dz_row_bytes, 0);
-                X1[r] = dz;
+                X1[r] = rscale * __builtin_amdgcn_rcpf(tt) * (pos ? 1.f : kLeakySlope);   // dz, stored below as packed plane pairs
             }
         };
-        auto store_packed = [&](int r0, uint32_t p_hi, uint32_t p_lo) {   // NP == 2: registers r0, r0 + 1 as packed plane pairs
+        auto store_packed = [&](int r0, uint32_t p_hi, uint32_t p_lo) {   // registers r0, r0 + 1 as packed plane pairs
             uint32_t d0, d1;
             pack_planes(p_hi, p_lo, d0, d1);
             __builtin_amdgcn_raw_buffer_store_b32(d0, dz_rsrc, dz_voff, ((r0 & 3) + 8 * (r0 >> 2)) * dz_row_bytes, 0);
@@ -729,32 +727,32 @@ __global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {   // NP
         if (!(TRAIN && DH)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) epilogue(r);
-            if (TRAIN && NP == 2) {
+            if (TRAIN) {
 #pragma unroll
-                for (int r0 = 0; r0 < 16; r0 += 2) { uint32_t pq[3]; split_pair_np<2>(X1[r0], X1[r0 + 1], pp.dz_scale, pq); store_packed(r0, pq[0], pq[1]); }
+                for (int r0 = 0; r0 < 16; r0 += 2) { uint32_t pq[2]; split_pair_scaled(X1[r0], X1[r0 + 1], pp.dz_scale, pq); store_packed(r0, pq[0], pq[1]); }
             }
         } else {
             // ---- dh += dz . mu_tile (+ (dz*s_out) . Wp_tile): the accumulator registers, split, are the A operand.  Only the first half of
             // the epilogue stands alone; the second half is spread over the MFMAs of the first k-step
-            auto split_a = [&](int s2, u32x4 (&ad)[3], u32x4 (&as)[3]) {
+            auto split_a = [&](int s2, u32x4 (&ad)[2], u32x4 (&as)[2]) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    uint32_t pq[3];
+                    uint32_t pq[2];
                     const int r0 = 8 * s2 + 2 * q;
-                    split_pair_np<NP>(X1[r0], X1[r0 + 1], pp.dz_scale, pq);
-                    ad[0][q] = pq[0]; ad[1][q] = pq[1]; ad[2][q] = pq[2];
-                    if (NP == 2) store_packed(r0, pq[0], pq[1]);
+                    split_pair_scaled(X1[r0], X1[r0 + 1], pp.dz_scale, pq);
+                    ad[0][q] = pq[0]; ad[1][q] = pq[1];
+                    store_packed(r0, pq[0], pq[1]);
                     if (BAYES) {
                         const int c0r = (r0 & 3) + 8 * (r0 >> 2);   // registers r0, r0+1 are experts c0r, c0r+1 (+4*half, folded into sw)
                         const uint32_t m = (((sw << (31 - c0r)) & 0x80000000u) >> 16) | ((sw << (30 - c0r)) & 0x80000000u);
-                        as[0][q] = pq[0] ^ m; as[1][q] = pq[1] ^ m; as[2][q] = pq[2] ^ m;
+                        as[0][q] = pq[0] ^ m; as[1][q] = pq[1] ^ m;
                     }
                 }
             };
-            auto tr_load = [&](int g, u32x4 (&bf)[3]) {   // g = (s2, jt, mat): B fragments (k = expert, n = hidden unit 32 jt + il)
+            auto tr_load = [&](int g, u32x4 (&bf)[2]) {   // g = (s2, jt, mat): B fragments (k = expert, n = hidden unit 32 jt + il)
                 const int mat = g % NMAT, jt = (g / NMAT) % NJT, s2 = g / (NMAT * NJT);
 #pragma unroll
-                for (int q = 0; q < NP; ++q) {
+                for (int q = 0; q < 2; ++q) {
                     const uint32_t o = 4096 * s2 + q * PLANE + mat * TM;
                     const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(size_t)(sbase + troff[0][jt] + o)));
                     const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(size_t)(sbase + troff[1][jt] + o)));
@@ -762,19 +760,19 @@ __global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {   // NP
                 }
             };
             constexpr int NG = 2 * NJT * NMAT;
-            u32x4 bf[2][3];
+            u32x4 bf[2][2];
             tr_load(0, bf[0]);
 #pragma unroll
             for (int r = 0; r < 8; ++r) epilogue(r);
-            u32x4 ad[2][3], as[2][3];
+            u32x4 ad[2][2], as[2][2];
             split_a(0, ad[0], as[0]);
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
                 if (g + 1 < NG) tr_load(g + 1, bf[(g + 1) & 1]);
                 asm volatile("" ::: "memory");
                 const int mat = g % NMAT, jt = (g / NMAT) % NJT, s2 = g / (NMAT * NJT);
-                if (mat == 0) Y1[jt] = mfma_np<NP>(ad[s2], bf[g & 1], Y1[jt]);
-                else Y2[jt] = mfma_np<NP>(as[s2], bf[g & 1], Y2[jt]);
+                if (mat == 0) Y1[jt] = mfma3h(ad[s2], bf[g & 1], Y1[jt]);
+                else Y2[jt] = mfma3h(as[s2], bf[g & 1], Y2[jt]);
                 if (s2 == 0) {   // second half of the epilogue in the shadow of the first k-step's MFMAs
                     constexpr int PER = 8 / (NJT * NMAT) > 0 ? 8 / (NJT * NMAT) : 1;
                     if (g * PER < 8) {
@@ -913,8 +911,8 @@ __global__ __launch_bounds__(512) void k_out_fwd_h3p(OutFwd6Args pp) {
             const uint32_t w8 = sw_in >> (16 * (s & 1) + 8 * half);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                uint32_t pq[3];
-                split_pair_np<2>(x[2 * q], x[2 * q + 1], pp.h_scale, pq);
+                uint32_t pq[2];
+                split_pair_scaled(x[2 * q], x[2 * q + 1], pp.h_scale, pq);
                 const uint32_t hm = ((w8 << (15 - 2 * q)) & 0x8000u) | ((w8 << (30 - 2 * q)) & 0x80000000u);
                 hp[s][0][q] = pq[0]; hp[s][1][q] = pq[1];
                 hs[s][0][q] = pq[0] ^ hm; hs[s][1][q] = pq[1] ^ hm;
@@ -1279,8 +1277,8 @@ __global__ __launch_bounds__(512) void k_out_fwd_h3e(OutFwd6Args pp) {
         const uint32_t w8 = sw_in >> (16 * (s & 1) + 8 * half);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            uint32_t pq[3];
-            split_pair_np<2>(x[2 * q], x[2 * q + 1], pp.h_scale, pq);
+            uint32_t pq[2];
+            split_pair_scaled(x[2 * q], x[2 * q + 1], pp.h_scale, pq);
             const uint32_t hm = ((w8 << (15 - 2 * q)) & 0x8000u) | ((w8 << (30 - 2 * q)) & 0x80000000u);
             hp[s][0][q] = pq[0]; hp[s][1][q] = pq[1];
             hs[s][0][q] = pq[0] ^ hm; hs[s][1][q] = pq[1] ^ hm;
@@ -1445,10 +1443,9 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
     if (!f.train && f.H == 128) g.NCG = eval_ncg(g);      // forward-only launches: two workgroups per CU (k_out_fwd_b6)
     // the loss of an evaluation step in fp16x3 (round 6): k_out_fwd_h3e - 256-row workgroups of eight logit waves, one per CU.  NTF_EVAL_KERNEL=0: k_out_fwd_b6 (A/B runs, tests)
     // (Flipout only: with one matrix a sub-tile is 24 MFMAs against the same logit work, and the two workgroups per CU of k_out_fwd_b6 measured 0.309 against 0.317 ms a step)
-    const bool evalp = f.eval_kernel && (f.bayes || f.eval_kernel == 2) && !f.train && !f.probs && f.bf16x6 && f.H == 128 && f.np == 2 && f.chunk_ncg_tot == 0;
+    const bool evalp = f.eval_kernel && (f.bayes || f.eval_kernel == 2) && !f.train && !f.probs && f.split && f.H == 128 && f.chunk_ncg_tot == 0;
     const int nrbe = (g.Bpad + 255) / 256;
     if (evalp) g.NCG = std::max(1, std::min({NCG_MAX / nrbe, g.T, NCG_MAX}));
-    if (f.ncg_limit > 0) g.NCG = std::max(1, std::min(g.NCG, f.ncg_limit));
     const WsLayout w = ws_layout(f.B, f.H, f.M);
     char* ws = static_cast<char*>(f.ws);
     uint32_t* sbits = reinterpret_cast<uint32_t*>(ws + w.sbits);
@@ -1457,7 +1454,7 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
     float* hz = reinterpret_cast<float*>(ws + w.hz);
     float* lossp = reinterpret_cast<float*>(ws + w.lossp);
     const bool inj = f.bayes && (f.s_out.inj != nullptr || f.s_in.inj != nullptr);
-    const bool guard = f.np == 2 && f.rflag != nullptr;   // fp16x3 arithmetic somewhere in this step (forward and / or dW): range-checked operands
+    const bool guard = f.rflag != nullptr;   // fp16x3 arithmetic somewhere in this step (forward and / or dW): range-checked operands
     if (inj && (phases & 1)) hipLaunchKernelGGL(k_sign_bits, dim3((g.nCB + 63) / 64, g.Bpad), dim3(64), 0, st, f.s_out, f.B, f.M, g.nCB, sbits);
     if ((phases & 1) && !f.h_ready) {
         const int n = g.Bpad * (f.H / 32);
@@ -1479,29 +1476,27 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
     s.sbits = sbits; s.sinbits = sinbits; s.rows = f.rows; s.m_indptr = f.m_indptr; s.neg = f.neg; s.m_indices = f.m_indices;
     s.tpw = f.tpw; s.tnw = f.tnw; s.inv_B = f.inv_B; s.dzT = f.dzT; s.dh = f.dh; s.row_fix = f.row_fix;
     s.so_k0 = f.s_out.k0; s.so_k1 = f.s_out.k1; s.so_inj = inj;
-    s.dz_pack_scale = (f.train && f.bf16x6 && f.H == 128 && f.np == 2) ? f.dz_scale : 0.f; s.rflag = f.rflag; s.c_lo = f.c_lo;
-    s.wp_pl = (f.bayes && f.bf16x6 && f.H == 128 && f.np == 2 && f.wp_pl) ? f.wp_pl : nullptr; s.wp_inv_scale = 1.f / f.w_scale;
+    s.dz_pack_scale = (f.train && f.split && f.H == 128) ? f.dz_scale : 0.f; s.rflag = f.rflag; s.c_lo = f.c_lo;
+    s.wp_pl = (f.bayes && f.split && f.H == 128 && f.wp_pl) ? f.wp_pl : nullptr; s.wp_inv_scale = 1.f / f.w_scale;
     int grid = g.NRB * g.NCG;
     const bool range_launch = ranged && f.chunk_ncg > 0 && (phases & 2);      // THIS call launches one range
     if (range_launch) { a.t_lo = f.chunk_t_lo; a.t_hi = f.chunk_t_hi; a.cg_off = f.chunk_cg_off; a.ncg_tot = f.chunk_ncg_tot; a.NCG = f.chunk_ncg; grid = g.NRB * f.chunk_ncg; }
-    if (f.bf16x6 && f.H == 128) {
-        constexpr int np = 2;
+    if (f.split && f.H == 128) {
         if ((phases & 1) && !f.planes_ready) {
             const int64_t Mp = ((int64_t)f.M + BN6 - 1) / BN6 * BN6, n = Mp * (f.H / 2);
-            hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f.mu, f.M, f.H, np, f.w_scale, f.mu_pl, guard ? f.rflag : nullptr);
-            if (f.bayes) hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f.wp, f.M, f.H, np, f.w_scale, f.wp_pl, guard ? f.rflag : nullptr);
+            hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f.mu, f.M, f.H, f.w_scale, f.mu_pl, guard ? f.rflag : nullptr);
+            if (f.bayes) hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f.wp, f.M, f.H, f.w_scale, f.wp_pl, guard ? f.rflag : nullptr);
         }
         if (phases & 2) {
             OutFwd6Args a6; a6.stamps = nullptr; a6.a = a; a6.mu_pl = f.mu_pl; a6.wp_pl = f.wp_pl; a6.pscale = f.pscale; a6.pacc = f.pacc; a6.plogit = f.plogit;
-            a6.a.rmode = (guard && np == 2) ? 1 : 0;
-            a6.h_scale = np == 2 ? f.h_scale : 1.f; a6.dz_scale = np == 2 ? f.dz_scale : 1.f;
-            a6.u_z = np == 2 ? 1.f / (f.w_scale * f.h_scale) : 1.f; a6.u_dh = np == 2 ? 1.f / (f.dz_scale * f.w_scale) : 1.f;
+            a6.a.rmode = guard ? 1 : 0;
+            a6.h_scale = f.h_scale; a6.dz_scale = f.dz_scale;
+            a6.u_z = 1.f / (f.w_scale * f.h_scale); a6.u_dh = 1.f / (f.dz_scale * f.w_scale);
             const bool dh = f.dh != nullptr;
-            const size_t lds = (size_t)2 * ((size_t)(f.bayes ? 2 : 1) * np * BN6 * 128 * 2 + 512);
-#define NTF_L6N(BY, TR, DHF, IJ, PR, NPV) do { auto kf = k_out_fwd_b6<BY, TR, DHF, IJ, PR, NPV>;                               \
+            const size_t lds = (size_t)2 * ((size_t)(f.bayes ? 2 : 1) * 2 * BN6 * 128 * 2 + 512);
+#define NTF_L6(BY, TR, DHF, IJ, PR) do { auto kf = k_out_fwd_b6<BY, TR, DHF, IJ, PR>;                                     \
             set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);       \
             hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, st, a6); } while (0)
-#define NTF_L6(BY, TR, DHF, IJ, PR) NTF_L6N(BY, TR, DHF, IJ, PR, 2)      /* (NP = 3, the bf16x6 arithmetic, is no longer instantiated: retired in round 6) */
 #define NTF_L6B(BY, IJ) do { if (f.probs) NTF_L6(BY, false, false, IJ, true); else if (!f.train) NTF_L6(BY, false, false, IJ, false);  \
                              else if (dh) NTF_L6(BY, true, true, IJ, false); else NTF_L6(BY, true, false, IJ, false); } while (0)
             if (evalp) {
@@ -1513,7 +1508,7 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
                 if (f.bayes) { if (inj) NTF_LE(true, true); else NTF_LE(true, false); } else NTF_LE(false, false);
 #undef NTF_LE
             } else
-            if (np == 2 && f.train && dh && f.wide == 5) {    // the fp16x3 training step: producer / consumer wave pairs, two waves per SIMD (a.T counts 64-expert tiles)
+            if (f.train && dh && f.wide == 5) {    // the fp16x3 training step: producer / consumer wave pairs, two waves per SIMD (a.T counts 64-expert tiles)
                 {
                     const size_t ldsp = 3 * ((size_t)(f.bayes ? 2 : 1) * 2 * 32 * 128 * 2 + 512) + 2 * 16384;
 #define NTF_LP(BY, IJ) do { auto kf = k_out_fwd_h3p<BY, IJ>;                                                                    \
@@ -1552,18 +1547,12 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
             } else if (f.bayes) { if (inj) NTF_L6B(true, true); else NTF_L6B(true, false); } else NTF_L6B(false, false);
 #undef NTF_L6B
 #undef NTF_L6
-#undef NTF_L6N
-#ifdef NTF_DIAG
-            static const bool skip_fb = getenv("NTF_SKIP_FALLBACK") != nullptr;     // timing only: what the conditional exact-f32 launch behind k_out_fwd_h3p costs
-#else
-            constexpr bool skip_fb = false;
-#endif
-            if (guard && np == 2 && !f.probs && !skip_fb && !f.split_fallback && !range_launch) {   // the same pass on the exact-f32 kernel, run only when an operand left the fp16 window
+            if (guard && !f.probs && !f.split_fallback && !range_launch) {   // the same pass on the exact-f32 kernel, run only when an operand left the fp16 window
                 OutFwdArgs af = a; af.rmode = 2;
                 if (f.bayes) fwd_dispatch<128, true>(st, f, af, s, grid, 2); else fwd_dispatch<128, false>(st, f, af, s, grid, 2);
             }
         }
-        if ((phases & 8) && f.split_fallback && guard && f.np == 2 && !f.probs) {   // ... as a launch of its own: behind the last range of a ranged (data-parallel) step, once over the whole layer
+        if ((phases & 8) && f.split_fallback && guard && !f.probs) {   // ... as a launch of its own: behind the last range of a ranged (data-parallel) step, once over the whole layer
             OutFwdArgs af = a; af.rmode = 2;
             if (f.bayes) fwd_dispatch<128, true>(st, f, af, s, grid, 2); else fwd_dispatch<128, false>(st, f, af, s, grid, 2);
         }

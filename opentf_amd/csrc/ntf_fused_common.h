@@ -67,7 +67,7 @@ inline WsLayout ws_layout(int Bmax, int H, int M) {
     w.hs = take((size_t)Bpad * H * 4);
     w.hz = take((size_t)Bpad * H * 4);
     w.lossp = take((size_t)Bpad * NCG_MAX * 4);
-    w.hb = take((size_t)Bpad * H * 2 * 6);   // bf16 split planes of h and h*s_in, K-block tiled (k_prep_planes_T)
+    w.hb = take((size_t)Bpad * H * 2 * 4);   // fp16 split planes (hi, lo) of h and h*s_in, K-block tiled (k_prep_planes_T)
     w.total = o;
     return w;
 }
@@ -160,41 +160,21 @@ template <int N> __device__ __forceinline__ void st_vec(float* p, const float (&
 }
 
 // ================================================================================================
-// bf16x6 variant: every f32 operand x is split exactly into three bf16 values x1 + x2 + x3 (x1 = bf16(x), x2 = bf16(x - x1),
-// x3 = bf16(x - x1 - x2); 24 mantissa bits in all), and a product a*b is taken as the six bf16 MFMA products
-// a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1 accumulated in f32.  Each bf16 x bf16 product is exact in f32 and the dropped terms are
-// <= 2^-24 relative, so the result carries f32 accuracy (measured: the same error against f64 as the f32 MFMA) while the matrix
-// pipe does 6 x 32 cycles per 16-deep k-step of a 32x32 tile instead of 8 x 64 (v_mfma_f32_32x32x2_f32) — and, unlike the f32 MFMA,
-// v_mfma_f32_32x32x16_bf16 leaves 24 of its 32 cycles free for vector instructions of the same wave.
+// Split-product arithmetic (fp16x3): every f32 operand x is scaled by an exact power of two 2^k (k per tensor) and split into two fp16 values
+// x1 = fp16(x 2^k), x2 = fp16(x 2^k - x1) (22 mantissa bits; fp16 subnormals are honoured by the MFMA, checked on the hardware), and a product a*b
+// is taken as the three fp16 MFMA products a1b1 + a1b2 + a2b1 on v_mfma_f32_32x32x16_f16, accumulated in f32: an error against f64 1.2 x that
+// of the f32 MFMA (5.7e-7 vs 4.6e-7 of the largest element on the forward product) at 3 x 16 cycles per 16-deep k-step of a 32x32 tile
+// instead of 8 x 64 (v_mfma_f32_32x32x2_f32).
 // ================================================================================================
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ f16x8 as_frag_h(u32x4 v) { return __builtin_bit_cast(f16x8, v); }
-// acc += a*b with a = a1+a2+a3, b = b1+b2+b3 (smallest terms first)
-__device__ __forceinline__ f32x16 mfma6(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a[2]), as_frag(b[0]), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a[0]), as_frag(b[2]), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a[1]), as_frag(b[1]), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a[1]), as_frag(b[0]), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a[0]), as_frag(b[1]), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a[0]), as_frag(b[0]), acc, 0, 0, 0);
-    return acc;
-}
-
-// fp16x3 variant of the same idea: x * 2^k (k per tensor, exact) split into two fp16 values (22 mantissa bits; fp16 subnormals are honoured by
-// the MFMA, checked on the hardware), a product = a1b1 + a1b2 + a2b1 on v_mfma_f32_32x32x16_f16: half the matrix work of bf16x6 for an error
-// against f64 1.2 x that of the f32 MFMA (5.7e-7 vs 4.6e-7 of the largest element on the forward product).
-__device__ __forceinline__ f32x16 mfma3h(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 acc) {
+// acc += a*b with a = a1+a2, b = b1+b2 (fragment 0: the hi plane, 1: the lo plane; smallest terms first)
+__device__ __forceinline__ f32x16 mfma3h(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x16 acc) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_frag_h(a[1]), as_frag_h(b[0]), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_frag_h(a[0]), as_frag_h(b[1]), acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_frag_h(a[0]), as_frag_h(b[0]), acc, 0, 0, 0);
     return acc;
-}
-template <int NP> __device__ __forceinline__ f32x16 mfma_np(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 acc) {
-    if (NP == 3) return mfma6(a, b, acc); else return mfma3h(a, b, acc);
 }
 
 }  // namespace ntf

@@ -82,15 +82,15 @@ __device__ __forceinline__ void dw_produce_next(const DwArgs& p, int64_t idx0, c
     const int64_t row = idx0 >> 7; const int j = (int)(idx0 & 127);      // H = 128
     amax = fmaxf(amax, fmaxf(fmaxf(fabsf(ov[0]), fabsf(ov[1])), fmaxf(fabsf(ov[2]), fabsf(ov[3]))));
     amax = fmaxf(amax, fmaxf(fmaxf(fabsf(mu4[0]), fabsf(mu4[1])), fmaxf(fabsf(mu4[2]), fabsf(mu4[3]))));
-    planes_store_quad<2>(p.nx_pl_wp, row, j, 128, ov[0], ov[1], ov[2], ov[3], p.nx_pscale);
-    planes_store_quad<2>(p.nx_pl_mu, row, j, 128, mu4[0], mu4[1], mu4[2], mu4[3], p.nx_pscale);
+    planes_store_quad(p.nx_pl_wp, row, j, 128, ov[0], ov[1], ov[2], ov[3], p.nx_pscale);
+    planes_store_quad(p.nx_pl_mu, row, j, 128, mu4[0], mu4[1], mu4[2], mu4[3], p.nx_pscale);
 }
 // Fnn (round 6): no Flipout operand - the next step's operand is the fp16 planes of the UPDATED mu alone (k_split_planes made them in a pass of its own over the layer at
 // the head of every step: 4 B read + 4 B written per weight on the way to the forward kernel)
 __device__ __forceinline__ void dw_produce_next_fnn(const DwArgs& p, int64_t idx0, const float (&mu4)[4], float& amax) {
     const int64_t row = idx0 >> 7; const int j = (int)(idx0 & 127);      // H = 128
     amax = fmaxf(amax, fmaxf(fmaxf(fabsf(mu4[0]), fabsf(mu4[1])), fmaxf(fabsf(mu4[2]), fabsf(mu4[3]))));
-    planes_store_quad<2>(p.nx_pl_mu, row, j, 128, mu4[0], mu4[1], mu4[2], mu4[3], p.nx_pscale);
+    planes_store_quad(p.nx_pl_mu, row, j, 128, mu4[0], mu4[1], mu4[2], mu4[3], p.nx_pscale);
 }
 // ... and once per workgroup: the KL' sum (one double atomic, as the stand-alone producer) and the range flag.  red = 8-byte-aligned LDS scratch of >= nwaves doubles
 template <bool BAYES = true>
@@ -282,39 +282,39 @@ __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_fallback(DwArgs p) 
     }
 }
 
-// hb: for every 32-row K block ib of the batch, the planes [p = h1,h2,h3,(hs1,hs2,hs3)][j][r = 0..31] of bf16 — the B operand
+// hb: for every 32-row K block ib of the batch, the fp16 planes [p = h hi, h lo, (hs hi, hs lo)][j][r = 0..31] of the values times scale — the B operand
 // (k = batch row, n = hidden unit) of the dW products reads 8 consecutive batch rows of one hidden unit as one 16-byte chunk.
-__global__ void k_prep_planes_T(const float* __restrict__ hz, const float* __restrict__ hs, int bayes, int Bpad, int H, int np, float scale,
+__global__ void k_prep_planes_T(const float* __restrict__ hz, const float* __restrict__ hs, int bayes, int Bpad, int H, float scale,
                                 uint16_t* __restrict__ hb) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;          // (ib, j, r), r fastest
     if (t >= Bpad * H) return;
     const int r = t & 31, j = (t >> 5) % H, ib = t / (32 * H);
-    const int npl = (bayes ? 2 : 1) * np;
+    const int npl = (bayes ? 2 : 1) * 2;
     uint16_t* tile = hb + (size_t)ib * npl * H * 32;
     // slot of hidden unit j in the image: column tile jt = j % NJT, lane il = j / NJT (NJT = H / 32).  The dW kernels read slot (jt, il) as the B column of
     // lane il in tile jt, so a lane's NJT accumulators are NJT CONSECUTIVE hidden units: its epilogue moves 4 NJT-byte pieces, 32 lanes one whole row
     const int njt = H >> 5, slot = 32 * (j % njt) + j / njt;
     for (int q = 0; q < (bayes ? 2 : 1); ++q) {
         const float x = (q ? hs : hz)[(int64_t)(ib * 32 + r) * H + j];
-        uint32_t p[3];
-        if (np == 3) split_pair_np<3>(x, 0.f, 1.f, p); else split_pair_np<2>(x, 0.f, scale, p);
-        for (int k = 0; k < np; ++k) tile[((q * np + k) * H + slot) * 32 + r] = (uint16_t)p[k];
+        uint32_t p[2];
+        split_pair_scaled(x, 0.f, scale, p);
+        for (int k = 0; k < 2; ++k) tile[((q * 2 + k) * H + slot) * 32 + r] = (uint16_t)p[k];
     }
 }
 
-// dW with bf16x6 products.  Workgroup = 8 waves x 32 experts; K = batch in 32-row blocks, two LDS stages filled by LDS-DMA:
+// dW with fp16x3 products.  Workgroup = 8 waves x 32 experts; K = batch in 32-row blocks, two LDS stages filled by LDS-DMA:
 //   A (k = batch row): the f32 dzT tile [256 experts][32 rows], 16-byte chunks XOR-swizzled ((row>>1)&7) exactly as in k_out_dw; a lane reads
-//     the 8 consecutive values of ITS expert (two ds_read_b128) and splits them in registers;
-//   B: the bf16 planes of h / h*s_in for the K block ([plane][j][32 rows], chunks swizzled with (j>>2)&3): one ds_read_b128 per fragment.
+//     the 8 consecutive values of ITS expert (two ds_read_b128), scales them by a_scale and splits them in registers;
+//   B: the fp16 planes of h / h*s_in for the K block ([plane][j][32 rows], chunks swizzled with (j>>2)&3): one ds_read_b128 per fragment.
 // No compiler-visible global load sits in the loop: hipcc would wait for it with a vmcnt that, in the real in-order queue, also waits
 // for the DMA issued just before.
-template <int H, bool BAYES, bool ADAM, int NP>
+template <int H, bool BAYES, bool ADAM>
 __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_b6(DwArgs p) {   // ADAM: update mu / rho and their moments in the epilogue (see DwArgs)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NJT = H / 32;
-    constexpr int NPL = (BAYES ? 2 : 1) * NP;   // NP = 3: bf16x6, NP = 2: fp16x3 (planes pre-scaled by 2^k, dz scaled by p.a_scale here)
+    constexpr int NPL = (BAYES ? 2 : 1) * 2;    // hi and lo plane of h (and of h*s_in), pre-scaled by 2^k; dz is scaled by p.a_scale here
     constexpr int TA = DW_TC * 32 * 4;            // dzT tile bytes
-    constexpr int PLANE = H * 64;                 // bytes of one plane of one K block: [H][32 rows] bf16
+    constexpr int PLANE = H * 64;                 // bytes of one plane of one K block: [H][32 rows] fp16
     constexpr int TB = NPL * PLANE;
     constexpr int STAGE = TA + TB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, half = lane >> 5;
@@ -373,19 +373,19 @@ __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_b6(DwArgs p) {   //
         const uint32_t word = word_next;
         const char* sA = smem + buf * STAGE;
         const char* sB = sA + TA;
-        // the K block as a flat, software-pipelined sequence of half-groups hg = (ks, jt, plain | signed): 3 fragment reads + 6 MFMAs
+        // the K block as a flat, software-pipelined sequence of half-groups hg = (ks, jt, plain | signed): 2 fragment reads + 3 MFMAs
         // each; the reads of half-group hg+1 are in flight while the MFMAs of hg run (explicit double buffer: left to itself hipcc
         // reuses the fragment registers and waits for every ds_read right before the MFMA that needs it)
         constexpr int NHG = 2 * NJT * (BAYES ? 2 : 1);
         const char* bbase = sB + il * 64;
         const int swz = (il >> 2) & 3;
-        auto load_b = [&](int hg, u32x4 (&dst)[3]) {
+        auto load_b = [&](int hg, u32x4 (&dst)[2]) {
             const int which = BAYES ? (hg & 1) : 0, g = BAYES ? (hg >> 1) : hg, ks = g / NJT, jt = g % NJT;
-            const char* bp = bbase + jt * 2048 + 16 * ((2 * ks + half) ^ swz) + which * NP * PLANE;
+            const char* bp = bbase + jt * 2048 + 16 * ((2 * ks + half) ^ swz) + which * 2 * PLANE;
 #pragma unroll
-            for (int q = 0; q < NP; ++q) dst[q] = *reinterpret_cast<const u32x4*>(bp + q * PLANE);
+            for (int q = 0; q < 2; ++q) dst[q] = *reinterpret_cast<const u32x4*>(bp + q * PLANE);
         };
-        u32x4 a[2][3], as[2][3];
+        u32x4 a[2][2], as[2][2];
         auto prep_a = [&](int ks) {
             const int ch = 4 * ks + 2 * half, sw = (crow >> 1) & 7;
             const float4 lo = *reinterpret_cast<const float4*>(sA + crow * 128 + 16 * (ch ^ sw));
@@ -394,19 +394,19 @@ __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_b6(DwArgs p) {   //
             const uint32_t w8 = word >> (ks * 16 + half * 8);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                uint32_t pq[3];
-                split_pair_np<NP>(x[2 * q], x[2 * q + 1], p.a_scale, pq);
-                a[ks][0][q] = pq[0]; a[ks][1][q] = pq[1]; a[ks][2][q] = pq[2];
+                uint32_t pq[2];
+                split_pair_scaled(x[2 * q], x[2 * q + 1], p.a_scale, pq);
+                a[ks][0][q] = pq[0]; a[ks][1][q] = pq[1];
                 sum1 += x[2 * q] + x[2 * q + 1];
                 if (BAYES) {
                     const uint32_t m = ((w8 << (15 - 2 * q)) & 0x8000u) | ((w8 << (30 - 2 * q)) & 0x80000000u);
-                    as[ks][0][q] = pq[0] ^ m; as[ks][1][q] = pq[1] ^ m; as[ks][2][q] = pq[2] ^ m;
+                    as[ks][0][q] = pq[0] ^ m; as[ks][1][q] = pq[1] ^ m;
                     sum2 += __uint_as_float(__float_as_uint(x[2 * q]) ^ ((w8 << (31 - 2 * q)) & 0x80000000u)) +
                             __uint_as_float(__float_as_uint(x[2 * q + 1]) ^ ((w8 << (30 - 2 * q)) & 0x80000000u));
                 }
             }
         };
-        u32x4 bq[2][3];
+        u32x4 bq[2][2];
         load_b(0, bq[0]);
         prep_a(0);
 #pragma unroll
@@ -414,12 +414,12 @@ __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_b6(DwArgs p) {   //
             if (hg + 1 < NHG) load_b(hg + 1, bq[(hg + 1) & 1]);
             asm volatile("" ::: "memory");   // keep the prefetch above this half-group's MFMAs
             const int which = BAYES ? (hg & 1) : 0, g = BAYES ? (hg >> 1) : hg, ks = g / NJT, jt = g % NJT;
-            if (which) acc2[jt] = mfma_np<NP>(as[ks], bq[hg & 1], acc2[jt]);
-            else acc1[jt] = mfma_np<NP>(a[ks], bq[hg & 1], acc1[jt]);
+            if (which) acc2[jt] = mfma3h(as[ks], bq[hg & 1], acc2[jt]);
+            else acc1[jt] = mfma3h(a[ks], bq[hg & 1], acc1[jt]);
             if (hg == (NHG / 2 > 1 ? 1 : 0)) prep_a(1);   // before the first k-step-1 half-group; its vector work runs in the shadow of the following MFMAs
             // next K block: DMA issue + sign words in the middle of the MFMA phase, not in front of it — the two waves of a SIMD leave
             // every barrier in phase, and vector work bunched at the top of the iteration would meet the partner's vector work there
-            if (hg == (NP == 2 ? 0 : NHG / 2) && ib + 1 < nib) { stage(ib + 1, buf ^ 1); if (BAYES && !p.so_inj) word_next = sign_col_word(ib + 1); }   // fp16x3: the K block is short, give the DMA all of it
+            if (hg == 0 && ib + 1 < nib) { stage(ib + 1, buf ^ 1); if (BAYES && !p.so_inj) word_next = sign_col_word(ib + 1); }   // the K block is short: give the DMA all of it
         }
         if (BAYES && p.so_inj && ib + 1 < nib) word_next = sign_col_word(ib + 1);   // injected signs (tests): a visible load, kept out of the MFMA phase
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // next K block (DMA) has landed
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_b6(DwArgs p) {   //
         if (ADAM) { ld_vec<NJT>(p.m_mu + idx0, a_m1); ld_vec<NJT>(p.v_mu + idx0, a_v1); if (BAYES) { ld_vec<NJT>(p.m_rho + idx0, a_m2); ld_vec<NJT>(p.v_rho + idx0, a_v2); } }
 #pragma unroll
         for (int jt = 0; jt < NJT; ++jt) {
-            float gm = acc1[jt][r] * p.unscale, gr = 0.f, pm = 0.f, rh = 0.f;   // unscale: 1 / (dz scale * h scale), 1 for bf16x6
+            float gm = acc1[jt][r] * p.unscale, gr = 0.f, pm = 0.f, rh = 0.f;   // unscale: 1 / (dz scale * h scale)
             if (BAYES) {
                 rh = v_rho[jt];
                 pm = v_mu[jt];
@@ -625,10 +625,10 @@ constexpr int QTC = 32 * QW;     // experts per workgroup
 template <bool BAYES, bool ADAM, bool STAMP = false, bool SPLIT = false>
 __global__ __launch_bounds__(64 * QW, 2) void k_out_dw_q(DwArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int H = 128, NJT = 4, NP = 2;
+    constexpr int H = 128, NJT = 4;
     constexpr int TA = QTC * 32 * 4;              // packed dz [128 experts][32 rows] dwords, 16-byte chunks XOR-swizzled ((row>>1)&7)
     constexpr int PLANE = H * 64;                 // [H slots][32 rows] fp16
-    constexpr int TB = NP * PLANE;                // the two planes of h
+    constexpr int TB = 2 * PLANE;                 // the two planes of h
     constexpr int SRC_TB = (BAYES ? 2 : 1) * TB;  // hb holds the planes of h * s_in behind them (k_out_dw_p2's operands)
     constexpr int TW = BAYES ? 1024 : 0;          // s_out words of the tile's experts (512 B), s_in words of the hidden units (512 B)
     constexpr int STAGE = TA + TB + TW;
@@ -709,14 +709,13 @@ __global__ __launch_bounds__(64 * QW, 2) void k_out_dw_q(DwArgs p) {
         constexpr int NG = 2 * NJT;                 // (ks, jt) groups: one B fragment each, used plain and (Flipout) signed
         const char* bbase = sB + il * 64;
         const int swz = (il >> 2) & 3;
-        auto load_b = [&](int g, u32x4 (&dst)[3]) {
+        auto load_b = [&](int g, u32x4 (&dst)[2]) {
             const int ks = g / NJT, jt = g % NJT;
             const char* bp = bbase + jt * 2048 + 16 * ((2 * ks + half) ^ swz);
 #pragma unroll
-            for (int q = 0; q < NP; ++q) dst[q] = *reinterpret_cast<const u32x4*>(bp + q * PLANE);
-            dst[2] = u32x4{0u, 0u, 0u, 0u};
+            for (int q = 0; q < 2; ++q) dst[q] = *reinterpret_cast<const u32x4*>(bp + q * PLANE);
         };
-        u32x4 a[2][3], as[2][3];
+        u32x4 a[2][2], as[2][2];
         auto prep_a = [&](int ks) {      // rows 16 ks + 8 half .. + 7 of this lane's expert: 8 packed dwords -> the hi and the lo plane fragment (k_out_dw_p2)
             const int ch = 4 * ks + 2 * half, sw = (crow >> 1) & 7;
             const u32x4 lo = *reinterpret_cast<const u32x4*>(sA + crow * 128 + 16 * (ch ^ sw));
@@ -726,20 +725,20 @@ __global__ __launch_bounds__(64 * QW, 2) void k_out_dw_q(DwArgs p) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const uint32_t p1 = __builtin_amdgcn_perm(x[2 * q + 1], x[2 * q], 0x05040100u), p2 = __builtin_amdgcn_perm(x[2 * q + 1], x[2 * q], 0x07060302u);
-                a[ks][0][q] = p1; a[ks][1][q] = p2; a[ks][2][q] = 0u;
+                a[ks][0][q] = p1; a[ks][1][q] = p2;
                 sum1 = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2_t, p1), ones, sum1, false);
                 sum1 = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2_t, p2), ones, sum1, false);
                 if (BAYES) {
                     const uint32_t m = ((w8 << (15 - 2 * q)) & 0x8000u) | ((w8 << (30 - 2 * q)) & 0x80000000u);
                     const uint32_t s1 = p1 ^ m, s2 = p2 ^ m;
-                    as[ks][0][q] = s1; as[ks][1][q] = s2; as[ks][2][q] = 0u;
+                    as[ks][0][q] = s1; as[ks][1][q] = s2;
                     sum2 = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2_t, s1), ones, sum2, false);
                     sum2 = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2_t, s2), ones, sum2, false);
                 }
             }
         };
         constexpr int BR = DWQ_BRING;           // B fragments in flight: the fragment of group g + BR - 1 is fetched while group g's MFMAs run
-        u32x4 bq[BR][3], bs[3];
+        u32x4 bq[BR][2], bs[2];
 #pragma unroll
         for (int g = 0; g < BR - 1; ++g) load_b(g, bq[g]);
         prep_a(0);
@@ -755,7 +754,7 @@ __global__ __launch_bounds__(64 * QW, 2) void k_out_dw_q(DwArgs p) {
             if (g + BR - 1 < NG) load_b(g + BR - 1, bq[(g + BR - 1) % BR]);
             asm volatile("" ::: "memory");
             const int ks = g / NJT, jt = g % NJT;
-            acc1[jt] = mfma_np<NP>(a[ks], bq[g % BR], acc1[jt]);
+            acc1[jt] = mfma3h(a[ks], bq[g % BR], acc1[jt]);
             dma();
             if (BAYES) {
                 const uint32_t v = iw[jt] << (ks ? shl1 : shl0);
@@ -764,8 +763,7 @@ __global__ __launch_bounds__(64 * QW, 2) void k_out_dw_q(DwArgs p) {
                     const uint32_t m = (v << q) & 0x80008000u;
                     bs[0][q] = bq[g % BR][0][q] ^ m; bs[1][q] = bq[g % BR][1][q] ^ m;
                 }
-                bs[2] = u32x4{0u, 0u, 0u, 0u};
-                acc2[jt] = mfma_np<NP>(as[ks], bs, acc2[jt]);
+                acc2[jt] = mfma3h(as[ks], bs, acc2[jt]);
                 dma();
             }
             if (g == 0) prep_a(1);
@@ -859,10 +857,10 @@ void launch_fused_out_dw(hipStream_t st, const FusedDw& f) {
     a.cur_eps = f.cur_eps; a.lean = (a.produce && f.lean) ? 1 : 0;
     a.nx_eps = f.nx_eps; a.nx_wp = f.nx_wp; a.nx_pl_wp = f.nx_pl_wp; a.nx_pl_mu = f.nx_pl_mu; a.nx_pscale = f.nx_pscale; a.nx_klw = f.nx_klw; a.nx_kl = f.nx_kl; a.nx_rflag = f.nx_rflag;
     a.ntile = 0; a.stagger = 0; a.stamps = nullptr;
-    const bool guard = f.bf16x6 && f.np == 2 && f.rflag != nullptr;
+    const bool guard = f.split && f.rflag != nullptr;
     a.sT = reinterpret_cast<const uint32_t*>(ws + w.sbitsT);
     a.ksplit = 1; a.part = nullptr; a.slab = 0; a.part_row0 = 0;
-    if (f.H == 256 && !f.fallback_only) {   // exact-f32 only (no split-product kernels at this width): each 256-expert tile as two hidden-half workgroups
+    if (f.H == 256) {   // exact-f32 only (no split-product kernels at this width): each 256-expert tile as two hidden-half workgroups
         const size_t lds = 2 * ((size_t)DW_TC * 32 * 4 + (size_t)(f.bayes ? 2 : 1) * 32 * 4 * 128);
 #define NTF_DWH(BY, AD) do { auto kf = k_out_dw_h2<BY, AD>; set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);              \
         hipLaunchKernelGGL(kf, dim3(grid, 2), dim3(64 * DW_WAVES), lds, st, a); } while (0)
@@ -870,12 +868,7 @@ void launch_fused_out_dw(hipStream_t st, const FusedDw& f) {
 #undef NTF_DWH
         return;
     }
-    if (f.fallback_only) {   // the exact-f32 kernel of a step whose split-product launches (several, e.g. the tail split of a whole step) were issued with no_fallback
-        if (!guard) return;
-        a.rmode = 2; a.a_scale = f.a_scale; a.unscale = 1.f / (f.a_scale * f.h_scale);
-        goto exact_f32;
-    }
-    if (f.bf16x6 && f.np == 2 && f.dz_packed) {   // fp16x3 step, H = 128: the forward kernel left packed plane pairs in dzT
+    if (f.split && f.dz_packed) {   // fp16x3 step, H = 128: the forward kernel left packed plane pairs in dzT
         a.a_scale = f.a_scale; a.unscale = 1.f / (f.a_scale * f.h_scale); a.rmode = guard ? 1 : 0;
         const int ks = (f.ksplit > 1 && f.part) ? std::min(f.ksplit, std::max(1, g.Bpad / 32)) : 1;
         if (ks > 1) {   // few expert tiles (a narrow expert shard under a wide minibatch): every half-tile's K range split over ks workgroups (k_out_dw_q<.., SPLIT>), k_out_dw_finish adds the parts and runs the epilogue
@@ -893,7 +886,7 @@ void launch_fused_out_dw(hipStream_t st, const FusedDw& f) {
             hipLaunchKernelGGL((k_out_dw_finish<BY, AD>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, a); } while (0)
             if (f.bayes) { if (f.adam) NTF_DWQS(true, true); else NTF_DWQS(true, false); } else { if (f.adam) NTF_DWQS(false, true); else NTF_DWQS(false, false); }
 #undef NTF_DWQS
-            if (!guard || f.no_fallback) return;
+            if (!guard) return;
             a.rmode = 2; a.ksplit = 1; a.wg_begin = wg256; a.part_row0 = 0;
             goto exact_f32;
         }
@@ -933,25 +926,22 @@ void launch_fused_out_dw(hipStream_t st, const FusedDw& f) {
             }
             else if (f.bayes) { if (f.adam) NTF_DWQ(true, true); else NTF_DWQ(true, false); } else { if (f.adam) NTF_DWQ(false, true); else NTF_DWQ(false, false); }
 #undef NTF_DWQ
-            if (!guard || f.no_fallback) return;
+            if (!guard) return;
             a.rmode = 2; a.wg_begin = wg256; a.ntile = 0; a.stagger = 0;   // the exact-f32 kernel behind it runs only when the range flag is raised
             goto exact_f32;
         }
     }
-    if (f.bf16x6) {
-        constexpr int np = 2;
+    if (f.split) {
         a.rmode = guard ? 1 : 0;
-        a.a_scale = np == 2 ? f.a_scale : 1.f; a.unscale = np == 2 ? 1.f / (f.a_scale * f.h_scale) : 1.f;
-#define NTF_DWB2(HH, BY, AD, NPV) do { auto kf = k_out_dw_b6<HH, BY, AD, NPV>; const size_t lds = 2 * ((size_t)DW_TC * 128 + (size_t)(BY ? 2 : 1) * NPV * HH * 64); \
+        a.a_scale = f.a_scale; a.unscale = 1.f / (f.a_scale * f.h_scale);
+#define NTF_DWB1(HH, BY, AD) do { auto kf = k_out_dw_b6<HH, BY, AD>; const size_t lds = 2 * ((size_t)DW_TC * 128 + (size_t)(BY ? 2 : 1) * 2 * HH * 64); \
         set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);                                      \
         hipLaunchKernelGGL(kf, dim3(grid), dim3(64 * DW_WAVES), lds, st, a); } while (0)
-#define NTF_DWB1(HH, BY, AD) NTF_DWB2(HH, BY, AD, 2)
 #define NTF_DWB(HH) do { if (f.bayes) { if (f.adam) NTF_DWB1(HH, true, true); else NTF_DWB1(HH, true, false); }                                            \
                          else { if (f.adam) NTF_DWB1(HH, false, true); else NTF_DWB1(HH, false, false); } } while (0)
         if (f.H == 128) NTF_DWB(128); else if (f.H == 64) NTF_DWB(64); else NTF_DWB(32);
 #undef NTF_DWB
 #undef NTF_DWB1
-#undef NTF_DWB2
         if (!guard) return;
         a.rmode = 2;   // fall through: the exact-f32 kernel, which runs only when the range flag is raised
     }
@@ -967,9 +957,9 @@ exact_f32:
 #undef NTF_DW
 }
 
-// bf16 split planes of the hidden activations for the dW kernel (once per step, after launch_fused_out_fwd's phase 1)
+// fp16 split planes of the hidden activations for the dW kernel (once per step, after launch_fused_out_fwd's phase 1)
 // which: 1 = the transposed s_out words (they depend on the sign key only: the engine issues them on its auxiliary stream), 2 = the h planes, 3 = both
-void launch_fused_prep_planes(hipStream_t st, int B, int H, int M, int bayes, void* ws_, int np, float h_scale, const SignSpec* s_out, int s_out_inj, int which) {
+void launch_fused_prep_planes(hipStream_t st, int B, int H, int M, int bayes, void* ws_, float h_scale, const SignSpec* s_out, int s_out_inj, int which) {
     const Geom g = geom(B, M);
     const WsLayout w = ws_layout(B, H, M);
     char* ws = static_cast<char*>(ws_);
@@ -981,8 +971,8 @@ void launch_fused_prep_planes(hipStream_t st, int B, int H, int M, int bayes, vo
     if (!(which & 2)) return;
     const int n = g.Bpad * H;
     hipLaunchKernelGGL(k_prep_planes_T, dim3((n + 255) / 256), dim3(256), 0, st, reinterpret_cast<const float*>(ws + w.hz), reinterpret_cast<const float*>(ws + w.hs),
-                       bayes, g.Bpad, H, np == 2 ? 2 : 3, h_scale, reinterpret_cast<uint16_t*>(ws + w.hb));
-    if (bayes && H == 128 && np == 2)   // k_out_dw_q rebuilds the planes of h * s_in from these words
+                       bayes, g.Bpad, H, h_scale, reinterpret_cast<uint16_t*>(ws + w.hb));
+    if (bayes && H == 128)   // k_out_dw_q rebuilds the planes of h * s_in from these words
         hipLaunchKernelGGL(k_sin_words_T, dim3((g.Bpad / 32 * 128 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(ws + w.sinbits), g.Bpad, reinterpret_cast<uint32_t*>(ws + w.sinT));
 }
 

@@ -224,12 +224,12 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs p) {
         for (int it = 0; it < 8; ++it) {
             const int slot = (tid >> 4) + 16 * it, jj = 4 * (slot & 31) + (slot >> 5);
             const float x0 = Hs[(2 * rp) * HS_LD + jj], x1 = Hs[(2 * rp + 1) * HS_LD + jj];
-            uint32_t pq[3];
-            split_pair_np<2>(x0, x1, p.h_scale, pq);
+            uint32_t pq[2];
+            split_pair_scaled(x0, x1, p.h_scale, pq);
             tile[(0 * HH + slot) * 16 + rp] = pq[0]; tile[(1 * HH + slot) * 16 + rp] = pq[1];
             if (BAYES) {
                 const uint32_t b0 = (SW[(2 * rp) * 4 + (jj >> 5)] >> (jj & 31)) & 1u, b1 = (SW[(2 * rp + 1) * 4 + (jj >> 5)] >> (jj & 31)) & 1u;
-                split_pair_np<2>(b0 ? -x0 : x0, b1 ? -x1 : x1, p.h_scale, pq);
+                split_pair_scaled(b0 ? -x0 : x0, b1 ? -x1 : x1, p.h_scale, pq);
                 tile[(2 * HH + slot) * 16 + rp] = pq[0]; tile[(3 * HH + slot) * 16 + rp] = pq[1];
             }
         }

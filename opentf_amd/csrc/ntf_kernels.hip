@@ -252,10 +252,10 @@ void launch_multihot_bwd(hipStream_t st, const int64_t* rows, int B, int S, int 
 // =====================================================================================
 // out = softplus(rho) * eps; when mu is given, also adds this tensor's KL(N(mu, sigma^2) || N(0,1)) * w to kl_out.
 // Grid-stride over quads with a bounded grid, so that the KL costs one double atomic per workgroup (<= 2048 in all).
-// planes_w / planes_mu (output layer, bf16x6 arithmetic): also the bf16 split planes of out and of pmu for the forward kernel.
+// planes_w / planes_mu (output layer, fp16x3 arithmetic): also the fp16 split planes of out and of pmu (times pscale) for the forward kernel.
 __global__ __launch_bounds__(256) void k_flipout_perturb(const float* __restrict__ rho, const float* __restrict__ mu, int64_t n, NormalSpec eps,
                                                          float* __restrict__ out, double w, double* kl_out, uint16_t* __restrict__ planes_w,
-                                                         uint16_t* __restrict__ planes_mu, const float* __restrict__ pmu, int H, int np, float pscale,
+                                                         uint16_t* __restrict__ planes_mu, const float* __restrict__ pmu, int H, float pscale,
                                                          int* __restrict__ rflag, const int* __restrict__ only_if, PerturbChain ch) {
     if (only_if && __builtin_nontemporal_load(only_if) == 0) return;   // (the f32 copy of sigma * eps for a step that fell back to the exact-f32 kernels, see launch_flipout_perturb)
     const int64_t quads = (n + 3) / 4;
@@ -283,15 +283,10 @@ __global__ __launch_bounds__(256) void k_flipout_perturb(const float* __restrict
                 const bool p2 = (H & (H - 1)) == 0;
                 const int64_t row = p2 ? (e0 >> (31 - __builtin_clz(H))) : e0 / H; const int j = p2 ? (int)(e0 & (H - 1)) : (int)(e0 - row * H);
                 const float4 m4 = planes_mu ? *reinterpret_cast<const float4*>(pmu + e0) : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (np == 3) {
-                    planes_store_quad<3>(planes_w, row, j, H, ov[0], ov[1], ov[2], ov[3], 1.f);
-                    if (planes_mu) planes_store_quad<3>(planes_mu, row, j, H, m4.x, m4.y, m4.z, m4.w, 1.f);
-                } else {
-                    amax = fmaxf(amax, fmaxf(fmaxf(fabsf(ov[0]), fabsf(ov[1])), fmaxf(fabsf(ov[2]), fabsf(ov[3]))));
-                    if (planes_mu) amax_mu = fmaxf(amax_mu, fmaxf(fmaxf(fabsf(m4.x), fabsf(m4.y)), fmaxf(fabsf(m4.z), fabsf(m4.w))));
-                    planes_store_quad<2>(planes_w, row, j, H, ov[0], ov[1], ov[2], ov[3], pscale);
-                    if (planes_mu) planes_store_quad<2>(planes_mu, row, j, H, m4.x, m4.y, m4.z, m4.w, pscale);
-                }
+                amax = fmaxf(amax, fmaxf(fmaxf(fabsf(ov[0]), fabsf(ov[1])), fmaxf(fabsf(ov[2]), fabsf(ov[3]))));
+                if (planes_mu) amax_mu = fmaxf(amax_mu, fmaxf(fmaxf(fabsf(m4.x), fabsf(m4.y)), fmaxf(fabsf(m4.z), fabsf(m4.w))));
+                planes_store_quad(planes_w, row, j, H, ov[0], ov[1], ov[2], ov[3], pscale);
+                if (planes_mu) planes_store_quad(planes_mu, row, j, H, m4.x, m4.y, m4.z, m4.w, pscale);
             }
         } else {
             for (int j = 0; j < 4 && e0 + j < n; ++j) {
@@ -309,11 +304,11 @@ __global__ __launch_bounds__(256) void k_flipout_perturb(const float* __restrict
     }
 }
 void launch_flipout_perturb(hipStream_t st, const float* rho, const float* mu, int64_t n, NormalSpec eps, float* out, double w, double* kl_out,
-                            uint16_t* planes_w, uint16_t* planes_mu, const float* pmu, int H, int np, float pscale, int* rflag, const int* only_if, PerturbChain ch) {
+                            uint16_t* planes_w, uint16_t* planes_mu, const float* pmu, int H, float pscale, int* rflag, const int* only_if, PerturbChain ch) {
     if (n <= 0) return;
     const int64_t quads = (n + 3) / 4;
     const int blocks = (int)std::min<int64_t>((quads + 255) / 256, only_if ? 256 : 2048);   // (only_if: a no-op in all but the rarest step - one short round of workgroups)
-    hipLaunchKernelGGL(k_flipout_perturb, dim3(blocks), dim3(256), 0, st, rho, mu, n, eps, out, w, kl_out, planes_w, planes_mu, pmu, H, np, pscale, (planes_w && np == 2) ? rflag : nullptr, only_if, ch);
+    hipLaunchKernelGGL(k_flipout_perturb, dim3(blocks), dim3(256), 0, st, rho, mu, n, eps, out, w, kl_out, planes_w, planes_mu, pmu, H, pscale, planes_w ? rflag : nullptr, only_if, ch);
 }
 
 __global__ void k_flipout_grad_finalize(const float* __restrict__ mu, const float* __restrict__ rho, float* __restrict__ g_mu,

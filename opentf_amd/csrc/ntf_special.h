@@ -84,7 +84,7 @@ __device__ __forceinline__ float special_dz(float z, float y, float tpw, float i
     bce_terms(z, sp, sg, dact);
     return tpw * (sg - y) * dact * inv_B;
 }
-__device__ __forceinline__ uint32_t special_dz_packed(float dzt, float scale) { uint32_t pq[3]; split_pair_np<2>(dzt, 0.f, scale, pq); return (pq[0] & 0xFFFFu) | (pq[1] << 16); }
+__device__ __forceinline__ uint32_t special_dz_packed(float dzt, float scale) { uint32_t pq[2]; split_pair_scaled(dzt, 0.f, scale, pq); return (pq[0] & 0xFFFFu) | (pq[1] << 16); }
 
 // one wave per team: loss terms, dz and d(hidden) terms of the special entries + the sums of the forward kernel's partials (ntf_special.hip)
 void launch_out_special(hipStream_t st, int H, bool bayes, bool train, bool dh, const SpecialArgs& s);

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Diagnostic builds of the library beside the shipped one (never shipped; selected per process with NTF_LIB_PATH):
-#   profiles/mk_variants.sh diag   -> scratch/var/diag.so       -DNTF_DIAG: ablations, stamps, NTF_SKIP, NTF_DW_TAIL, the co-scheduling experiment
+#   profiles/mk_variants.sh diag   -> scratch/var/diag.so       -DNTF_DIAG: ablations (NTF_FWD_ABL=9), stamps (NTF_DW_STAMP_FILE)
 #   profiles/mk_variants.sh ieee   -> scratch/var/adam_ieee.so  -DNTF_ADAM_IEEE: adam_step on sqrtf and a true division (r5_ep_tolerance.md)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd); D=$R/scratch/var; mkdir -p $D/obj
