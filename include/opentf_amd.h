@@ -225,6 +225,10 @@ int ntf_forward_topk(ntf_engine* e, const int64_t* rows, int32_t B, int32_t nmc,
 int ntf_gather_meanpool(ntf_engine* e, const int64_t* rows, int64_t n, float* out_host);
 
 /* ---- raw device views for RCCL (torch.distributed) and measurement */
+/* ntf_grad_buffer: every step computes its gradient from zero, whatever the buffer held before (src/mdl/fnn.py:122-140).  The multi-hot
+ * first layer's one-pass sweep clears the rows it reads, and the next step skips the memset in front of its scatter; taking this view
+ * makes the next step zero the layer's gradient again, so the caller may write the buffer between steps.  A view held across steps
+ * (dp.py) is safe only on engines that never sweep; data-parallel steps do not (they ignore fuse_adam). */
 int ntf_grad_buffer(ntf_engine* e, void** dev_ptr, int64_t* n_floats);
 int ntf_param_buffer(ntf_engine* e, void** dev_ptr, int64_t* n_floats);
 /* A caller that WRITES parameters through the view above (an all-gather, a broadcast: torch.optim's `p.data.copy_`, src/mdl/fnn.py:104) says so before the next

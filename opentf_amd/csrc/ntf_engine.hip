@@ -1904,7 +1904,9 @@ extern "C" int ntf_gather_meanpool(ntf_engine* e, const int64_t* rows, int64_t n
 
 // ------------------------------------------------------------------------------------------ views
 extern "C" int ntf_grad_buffer(ntf_engine* e, void** dev_ptr, int64_t* n_floats) {
-    if (!e || !dev_ptr || !n_floats) return NTF_EINVAL; *dev_ptr = e->G; *n_floats = e->n_params; return NTF_OK;
+    if (!e || !dev_ptr || !n_floats) return NTF_EINVAL; *dev_ptr = e->G; *n_floats = e->n_params;
+    e->g0_clean = false;    // whoever takes the raw view may write through it: the next multi-hot first-layer scatter clears its rows first
+    return NTF_OK;
 }
 extern "C" int ntf_param_buffer(ntf_engine* e, void** dev_ptr, int64_t* n_floats) {
     if (!e || !dev_ptr || !n_floats) return NTF_EINVAL; *dev_ptr = e->P; *n_floats = e->n_params;

@@ -160,7 +160,9 @@ class DataParallel:
         # all-gather has bytes to move.  Default by that evidence (round 6): ranged iff the group really has peers; NTF_DP_RANGES=1 / 0 forces it on / off (A/B runs, tests).
         rng_env = os.environ.get("NTF_DP_RANGES")
         self.ranged_head = (rng_env != "0") if rng_env is not None else (self.world > 1 and not self.emulate)
-        self._grad = engine.grad_tensor()  # flat view of the engine's gradient buffer (HBM; aliases, no copy)
+        # flat view of the engine's gradient buffer (HBM; aliases, no copy), taken once and written by every reduce-scatter.  Safe to hold: the
+        # steps issued here never run the multi-hot first-layer sweep, whose next step would skip zeroing the rows (fuse_adam is ignored under DP)
+        self._grad = engine.grad_tensor()
         # NTF_DP_FORCE_ALLREDUCE=1: run the collectives even at world_size 1 (exercises RCCL on the aliased buffers on a 1-GPU box)
         self.force_allreduce = (dist.is_initialized() and os.environ.get("NTF_DP_FORCE_ALLREDUCE", "0") == "1") or bool(self.emulate)
         self.n_chunks = engine.dw_chunks() if (overlap and hasattr(engine, "dw_chunks")) else 0

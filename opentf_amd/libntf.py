@@ -153,6 +153,14 @@ class DeviceView:
         self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "<f4", "data": (int(ptr), False), "version": 2, "strides": None}
 
 
+def gemm_f32(m, n, k, A, sam, sak, B, sbk, sbn, C_, ldc, stream=None):
+    """ntf_k_gemm_f32 on caller-owned device memory (addresses as ints): C[i * ldc + j] = sum_p A[i * sam + p * sak] * B[p * sbk + j * sbn]
+    for i < m, j < n, f32 MFMA products and accumulation, queued on `stream` (a hipStream_t; None: the null stream).  No synchronisation."""
+    rc = lib().ntf_k_gemm_f32(stream, int(m), int(n), int(k), A, int(sam), int(sak), B, int(sbk), int(sbn), C_, int(ldc))
+    if rc != 0:
+        raise NtfError(f"ntf_k_gemm_f32 failed ({rc})")
+
+
 class Engine:
     """One Fnn/Bnn model resident on one MI355X.  dims = [D, *h, M].
     expert_shard = (lo, hi), ep_world = G: this engine owns the experts [lo, hi) of the output layer only (one of G such engines, one per GPU;
