@@ -96,16 +96,59 @@ __device__ __forceinline__ void planes_store_quad(uint16_t* planes, int64_t row,
     for (int k = 0; k < 2; ++k) o[(size_t)k * 8 * H] = make_uint2(p[k], q[k]);   // plane stride = 32 rows x H elements = 64 H bytes = 8 H uint2
 }
 
-// the same on the hardware exp2 / log2 / rcp (1 ulp each): log1p(e) = log(u) * e / (u - 1) with u = fl(1 + e) cancels the rounding of
-// 1 + e (~2 ulp overall, against ~1 ulp of the library call that costs >100 vector instructions); also returns log(sigma) for the KL
+// sigma = softplus(rho) and the terms of its Flipout / KL gradient, for every kernel that finalizes a rho gradient or produces sigma * eps.
+// Flipout: d(sigma eps)/d rho = eps sg with sg = sigmoid(rho); KL (log sigma_p - log sigma + sigma^2 / 2 + ..): d/d rho = (sigma - 1 / sigma) sg,
+// which a caller takes as klw * kl_a * kl_b.  With e = e^rho, three regimes:
+//   e < 2^-24 (rho < -16.6): log1p(e) = e (1 - e/2 + ..) and 1 / (1 + e) both round to the leading term, so sigma = e, sg = e, log sigma = rho,
+//                            and (sigma - 1/sigma) sg = e^2 - sg / sigma = -1 in f32 (kl_a = -1, kl_b = 1): nothing divides by sigma, which is
+//                            subnormal below rho = -87.3 (1 / sigma overflows below -88.7) and 0 where e^rho underflows
+//   rho > 20:                log1p(e^-rho) < 2^-28 rho and e^-rho < 2^-28 are below half an ulp: sigma = rho, sg = 1
+//   between:                 the kernels' arithmetic as it was (the benchmark's rho ~ -3 lies here: its results do not move by a bit)
+// isig = 1 / sigma except in the lowest regime (lo), where it is 1 and a caller that recovers eps sg as (w / sigma) sg from w = sigma eps takes w alone
+// (sg / sigma = 1 there).
+struct RhoTerms { float sigma, log_sigma, sg, isig, kl_a, kl_b; bool lo; };
+constexpr float kRhoTailE = 5.9604645e-08f;     // 2^-24
+constexpr float kRhoHead = 20.f;
+// on the hardware exp2 / log2 / rcp (1 ulp each).  FIN (the gradient finalizers): sigma by the series below e = 2^-6, log(1 + e) above;
+// otherwise (the sigma * eps producers) log1p(e) = log(u) * e / (u - 1) with u = fl(1 + e), which cancels the rounding of 1 + e (~2 ulp overall,
+// against ~1 ulp of the library call that costs >100 vector instructions).  The two forms stay as they were, each bit for bit in the middle regime.
+template <bool FIN>
+__device__ __forceinline__ RhoTerms rho_terms_fast(float rho) {
+    RhoTerms t;
+    const float e = __builtin_amdgcn_exp2f(fminf(rho, 80.f) * 1.4426950408889634f), u = 1.f + e;
+    float sigma;
+    if (FIN) sigma = e < 0.015625f ? e * (1.f - e * (0.5f - e * (0.33333333f - 0.25f * e))) : __builtin_amdgcn_logf(u) * 0.6931471805599453f;
+    else { const float d = u - 1.f; sigma = d == 0.f ? e : (__builtin_amdgcn_logf(u) * 0.6931471805599453f) * (e * __builtin_amdgcn_rcpf(d)); }
+    const bool lo = e < kRhoTailE, hi = rho > kRhoHead;
+    t.lo = lo;
+    t.sigma = hi ? rho : sigma;
+    t.log_sigma = lo ? rho : __builtin_amdgcn_logf(t.sigma) * 0.6931471805599453f;
+    t.sg = hi ? 1.f : e * __builtin_amdgcn_rcpf(u);
+    t.isig = lo ? 1.f : __builtin_amdgcn_rcpf(t.sigma);
+    t.kl_a = lo ? -1.f : t.sigma - t.isig;
+    t.kl_b = lo ? 1.f : t.sg;
+    return t;
+}
 __device__ __forceinline__ float softplus_rho_fast(float rho, float& log_sigma) {
-    const float e = __builtin_amdgcn_exp2f(fminf(rho, 80.f) * 1.4426950408889634f);
-    const float u = 1.f + e, d = u - 1.f;
-    const float sigma = d == 0.f ? e : (__builtin_amdgcn_logf(u) * 0.6931471805599453f) * (e * __builtin_amdgcn_rcpf(d));
-    log_sigma = __builtin_amdgcn_logf(sigma) * 0.6931471805599453f;
-    return sigma;
+    const RhoTerms t = rho_terms_fast<false>(rho);
+    log_sigma = t.log_sigma;
+    return t.sigma;
 }
 __device__ __forceinline__ float softplus_rho(float rho) { return log1pf(expf(rho)); }  // sigma = log1p(exp(rho))
+// the same regimes on the library expf / log1pf / logf (the exact-f32 paths)
+__device__ __forceinline__ RhoTerms rho_terms(float rho) {
+    RhoTerms t;
+    const float e = expf(rho);
+    const bool lo = e < kRhoTailE;
+    t.lo = lo;
+    t.sigma = softplus_rho(rho);
+    t.sg = 1.f / (1.f + expf(-rho));
+    t.isig = lo ? 1.f : 1.f / t.sigma;
+    t.kl_a = lo ? -1.f : t.sigma - t.isig;
+    t.kl_b = lo ? 1.f : t.sg;
+    t.log_sigma = lo ? rho : logf(t.sigma);
+    return t;
+}
 
 // terms of binary_cross_entropy_with_logits on l = leaky_relu(z) (src/mdl/fnn.py:25,46):
 //   sp = softplus(l) = bce(l, y=0);  sg = sigmoid(l);  dact = d leaky_relu / dz

@@ -229,10 +229,9 @@ __device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem, int
             else {
                 const float rh = ADAM ? p.w_rho[idx0 + jt] : p.rho[idx0 + jt], w = p.wp[idx0 + jt];
                 pr[jt] = rh;
-                const float sigma = softplus_rho(rh);
-                const float sg = 1.f / (1.f + expf(-rh));
+                const RhoTerms t = rho_terms(rh);      // (ntf_device.h: eps sg = (w / sigma) sg, = w where sg / sigma rounds to 1)
                 gm[jt] = acc1[jt][r] + p.klw * pm[jt];
-                gr[jt] = acc2[jt][r] * (w / sigma) * sg + p.klw * (sigma - 1.f / sigma) * sg;
+                gr[jt] = (t.lo ? acc2[jt][r] * w : acc2[jt][r] * (w / t.sigma) * t.sg) + p.klw * t.kl_a * t.kl_b;
             }
         }
         if (!ADAM) {
@@ -450,12 +449,11 @@ __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_b6(DwArgs p) {   //
                 pm = v_mu[jt];
                 const float w = v_wp[jt];
                 // sigma = log1p(e^rho), sigmoid(rho) = e^rho / (1 + e^rho) on the hardware exp2/log2/rcp (the library expf/log1pf cost more vector
-                // instructions here than the whole K loop); the short series keeps log1p accurate where 1 + e^rho rounds
-                const float e = __builtin_amdgcn_exp2f(fminf(rh, 80.f) * 1.44269504f), t = 1.f + e;
-                const float sigma = e < 0.015625f ? e * (1.f - e * (0.5f - e * (0.33333333f - 0.25f * e))) : __builtin_amdgcn_logf(t) * 0.69314718f;
-                const float sg = e * __builtin_amdgcn_rcpf(t), isig = __builtin_amdgcn_rcpf(sigma);
+                // instructions here than the whole K loop); the short series keeps log1p accurate where 1 + e^rho rounds (ntf_device.h rho_terms_fast)
+                const RhoTerms t = rho_terms_fast<true>(rh);
                 gm += p.klw * pm;
-                gr = (acc2[jt][r] * p.unscale) * (w * isig) * sg + p.klw * (sigma - isig) * sg;
+                const float s2 = acc2[jt][r] * p.unscale;
+                gr = (t.lo ? s2 * w : s2 * (w * t.isig) * t.sg) + p.klw * t.kl_a * t.kl_b;
             } else if (ADAM) pm = v_mu[jt];
             o_mu[jt] = gm; o_rho[jt] = gr;
             if (ADAM) {   // in place: the updated parameter goes where the gradient would have gone
@@ -522,11 +520,9 @@ __device__ __forceinline__ void dw_finish_ops(const DwArgs& p, int64_t idx0, con
         if (BAYES) {
             rh = o.rho[jt];
             pm = o.mu[jt];
-            const float e = __builtin_amdgcn_exp2f(fminf(rh, 80.f) * 1.44269504f), t = 1.f + e;
-            const float sigma = e < 0.015625f ? e * (1.f - e * (0.5f - e * (0.33333333f - 0.25f * e))) : __builtin_amdgcn_logf(t) * 0.69314718f;
-            const float sg = e * __builtin_amdgcn_rcpf(t), isig = __builtin_amdgcn_rcpf(sigma);
+            const RhoTerms t = rho_terms_fast<true>(rh);     // (ntf_device.h)
             gm += p.klw * pm;
-            gr = s2[jt] * z[jt] * sg + p.klw * (sigma - isig) * sg;
+            gr = s2[jt] * z[jt] * t.sg + p.klw * t.kl_a * t.kl_b;
         } else if (ADAM) pm = o.mu[jt];
         o_mu[jt] = gm; o_rho[jt] = gr;
         if (ADAM) {   // in place: the updated parameter goes where the gradient would have gone

@@ -322,10 +322,8 @@ __global__ void k_flipout_grad_finalize(const float* __restrict__ mu, const floa
     for (int j = 0; j < 4; ++j) {
         const int64_t e = e0 + j;
         if (e >= n) break;
-        const float r = rho[e];
-        const float sg = 1.f / (1.f + expf(-r));  // d softplus / d rho
-        const float sigma = softplus_rho(r);
-        g_rho[e] = g_rho[e] * z[j] * sg + klw * (sigma - 1.f / sigma) * sg;
+        const RhoTerms t = rho_terms(rho[e]);     // (ntf_device.h) sg = d softplus / d rho
+        g_rho[e] = g_rho[e] * z[j] * t.sg + klw * t.kl_a * t.kl_b;
         g_mu[e] += klw * mu[e];
     }
 }
@@ -738,9 +736,8 @@ struct AdamRanges { int64_t lo[4], n[4]; int blk0[5]; int cnt; int fin[4]; Norma
                     struct { const float* rho; float* out; int64_t n; NormalSpec eps; const int* only_if; int blk0, nblk; } f32c; };
 __device__ __forceinline__ void fin_mu(float& g, float p, float klw) { g += klw * p; }
 __device__ __forceinline__ void fin_rho(float& g, float r, float z, float klw) {
-    const float sg = 1.f / (1.f + expf(-r));  // d softplus / d rho
-    const float sigma = softplus_rho(r);
-    g = g * z * sg + klw * (sigma - 1.f / sigma) * sg;
+    const RhoTerms t = rho_terms(r);          // (ntf_device.h) sg = d softplus / d rho
+    g = g * z * t.sg + klw * t.kl_a * t.kl_b;
 }
 __device__ __forceinline__ void rotate_scalars(double* kl) {      // next step's KL sum and range flag -> current (see k_step_scalars)
     int32_t* w = reinterpret_cast<int32_t*>(kl);
@@ -878,12 +875,10 @@ void launch_adam_ranges(hipStream_t st, float* P, float* G, float* M1, float* V2
 }
 
 // ---- launch_flipout_sweep (ntf_kernels.h): finalize + Adam + next-step operand of one Flipout weight tensor in one pass
-// fin_rho on the hardware transcendentals, as the output layer's dW epilogue takes it (ntf_fused_dw.hip dw_finish_ops): sigma by the series below e = 2^-6, log(1 + e) above
+// fin_rho on the hardware transcendentals, as the output layer's dW epilogue takes it (ntf_fused_dw.hip dw_finish_ops; ntf_device.h rho_terms_fast)
 __device__ __forceinline__ void fin_rho_fast(float& g, float r, float z, float klw) {
-    const float e = __builtin_amdgcn_exp2f(fminf(r, 80.f) * 1.44269504f), t = 1.f + e;
-    const float sigma = e < 0.015625f ? e * (1.f - e * (0.5f - e * (0.33333333f - 0.25f * e))) : __builtin_amdgcn_logf(t) * 0.69314718f;
-    const float sg = e * __builtin_amdgcn_rcpf(t), isig = __builtin_amdgcn_rcpf(sigma);
-    g = g * z * sg + klw * (sigma - isig) * sg;
+    const RhoTerms t = rho_terms_fast<true>(r);
+    g = g * z * t.sg + klw * t.kl_a * t.kl_b;
 }
 __global__ __launch_bounds__(256) void k_flipout_sweep(FlipoutSweep a, float lr_over_bc1) {
     const int64_t quads = a.n >> 2;
