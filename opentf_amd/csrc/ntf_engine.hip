@@ -95,7 +95,7 @@ struct ntf_engine {
     int lean = 1;                     // NTF_LEAN=0: the dW epilogue also writes the f32 copy of the next step's sigma * eps (round 3's 64 B per pair; A/B runs)
     int dw_ksplit = 0;                // 0: automatic (few expert tiles -> split the dW kernel's K range), else forced (NTF_DW_KSPLIT)
     int32_t* d_range = nullptr;       // fp16x3 range guard (lives behind d_kl[0]): [0] raised for the current step, [1] steps that fell back to the f32 kernels
-    int64_t range_fallbacks_host = 0; // inference calls redone on the generic path for the same reason
+    int64_t range_fallbacks_host = 0; // inference calls redone on the exact-f32 kernel (NTF_INFER_F32=0: the generic path) for the same reason
     float* tk_vals = nullptr; int32_t* tk_idx = nullptr; int64_t tk_cap = 0;
     // injection staging (device)
     std::vector<float*> inj_eps_w, inj_eps_b, inj_s_in, inj_s_out;
@@ -124,6 +124,8 @@ struct ntf_engine {
     // step's sigma * eps and KL in one pass, on the side stream beside the dW kernel.  pre0_step: the step whose Wp[0] / KL the last sweep produced (used iff that step also
     // starts on the output layer's prefetched operands: one validity protocol, pre_valid / pre_step); l0_swept: this step's Adam of the layer's weights ran in the sweep
     // (apply_adam leaves them out); g0_clean: the layer's gradient rows are all zero (the sweep clears what it reads: no memset in front of the scatter)
+    int infer_f32 = 1;                // NTF_INFER_F32=0 (A/B runs, tests): inference without the split planes (h[-1] of 32, 64, 256; 128 with mfma = NTF_MFMA_F32; a raised range flag) on the
+                                      // generic chain - k_gemm into dense [B, M] logits + launch_sigmoid_acc per MC pass - instead of the exact-f32 fused kernel k_out_probs
     int eval_kernel = 1;              // NTF_EVAL_KERNEL=0 (A/B runs, tests): evaluation steps on k_out_fwd_b6 as in round 5 instead of k_out_fwd_h3e
     int mh_head = 1;                  // NTF_MH_HEAD=0 (A/B runs): a multi-hot step's head (first-layer operands, gather-sum, h images) inline in its own step as in rounds 1-5; 1 (round 6): as ONE
                                       // unit (head_launch's multi-hot form) that the previous step issues for the next staged batch beside its dW kernel, behind the first layer's sweep
@@ -259,6 +261,7 @@ extern "C" int ntf_engine_create(const ntf_config* cfg, ntf_engine** out) {
     if (const char* fp = getenv("NTF_FNN_PIPE")) e->fnn_pipe = atoi(fp);
     if (const char* mh = getenv("NTF_MH_HEAD")) e->mh_head = atoi(mh);
     if (const char* ek = getenv("NTF_EVAL_KERNEL")) e->eval_kernel = atoi(ek);
+    if (const char* nf = getenv("NTF_INFER_F32")) e->infer_f32 = atoi(nf);
     if (const char* fc = getenv("NTF_F32_COPY_MERGED")) e->f32_copy_merged = atoi(fc);
     if (const char* eh = getenv("NTF_EP_HEAD_PREFETCH")) e->ep_head_prefetch = atoi(eh);
     if (const char* dr = getenv("NTF_DP_RANGES")) e->dp_ranges = atoi(dr);
@@ -1700,26 +1703,33 @@ static int infer_pass(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_i
     return forward_layers(e, c, true, false);  // logits (post leaky_relu) in dZout
 }
 
-static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, int pass, int passes, bool want_unc, bool logits);
+static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, int pass, int passes, bool want_unc, bool logits, bool split);
 static int range_raised(ntf_engine* e, bool& raised);
+// inference on the fused kernels: the split-product one where its planes exist (H = 128, default arithmetic), else - and behind a raised range flag - the exact-f32 one
+static bool infer_split(const ntf_engine* e) { return fused_ok(e) && e->pl_mu != nullptr; }
+static bool infer_fused(const ntf_engine* e) { return fused_ok(e) && (e->infer_f32 || e->pl_mu != nullptr); }
 
 extern "C" int ntf_logits(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, float* logits_host) {
     if (!e || !logits_host) return NTF_EINVAL;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     const int M = e->cfg.dims[e->L];
-    if (e->pl_mu && fused_ok(e)) {
-        // the kernel the inference ships (k_out_fwd_b6 in its probs mode), storing leaky_relu(z) instead of its sigmoid
+    if (infer_fused(e)) {
+        // the kernel the inference ships (k_out_fwd_b6 / k_out_probs), storing leaky_relu(z) instead of its sigmoid
         if (!e->Pbuf) DM(e, &e->Pbuf, (int64_t)e->cfg.max_batch * M);
         const uint64_t step0 = e->step;
-        if (range_ptr(e)) HIPCHK(e, hipMemsetAsync(e->d_range, 0, 4, e->st));
-        int r = infer_pass_fused(e, rows, B, inj, 0, 1, false, true); if (r) return r;
-        bool raised; if ((r = range_raised(e, raised))) return r;
-        if (!raised) {
+        bool split = infer_split(e), done = false;
+        for (int arm = 0; arm < 2 && !done; ++arm) {      // the split-product kernel; behind a raised range flag (or without planes) the exact-f32 one, same generator keys
+            if (split && range_ptr(e)) HIPCHK(e, hipMemsetAsync(e->d_range, 0, 4, e->st));
+            int r = infer_pass_fused(e, rows, B, inj, 0, 1, false, true, split); if (r) return r;
+            bool raised = false; if (split && (r = range_raised(e, raised))) return r;
+            done = !raised;
+            if (raised) { e->step = step0; split = false; if (!e->infer_f32) break; }
+        }
+        if (done) {
             HIPCHK(e, hipMemcpyAsync(logits_host, e->Pbuf, (size_t)B * M * 4, hipMemcpyDeviceToHost, e->st));
             HIPCHK(e, hipStreamSynchronize(e->st));
             return NTF_OK;
         }
-        e->step = step0;
     }
     StepCtx c; int r = infer_pass(e, rows, B, inj, c); if (r) return r;
     HIPCHK(e, hipMemcpyAsync(logits_host, e->dZout, (size_t)B * M * 4, hipMemcpyDeviceToHost, e->st));
@@ -1765,8 +1775,9 @@ extern "C" int ntf_get_dlogits(ntf_engine* e, float* host, int64_t count) {
     return NTF_OK;
 }
 
-// one MC pass of the inference through the fused split-product forward kernel: probabilities accumulate in the transposed buffer dZout
-static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, int pass, int passes, bool want_unc, bool logits) {
+// one MC pass of the inference through the fused forward kernel: probabilities accumulate in the transposed buffer dZout
+// split: the split-product kernel on the fp16 planes (H = 128), range-checked; else the exact-f32 kernel on mu / sigma * eps themselves (any fused width)
+static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, int pass, int passes, bool want_unc, bool logits, bool split) {
     int r;
     if ((r = check_ready(e, false))) return r;
     StepCtx c; c.B = B; c.global_B = B; c.inj = inj; c.train = false; c.step = e->step++;
@@ -1785,24 +1796,26 @@ static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const
     f.mu = e->P + lo.off[NTF_P_WEIGHT]; f.mu_b = e->P + lo.off[NTF_P_BIAS];
     f.tnw = e->cfg.tnw; f.tpw = e->cfg.tpw; f.inv_B = 1.f / (float)B;
     f.dzT = e->dZout; f.dh_slab = e->dh_slab; f.ws = e->fws;
-    f.split = 1; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp;
+    f.split = split; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp;
     f.w_scale = kW16Scale; f.h_scale = kH16Scale; f.dz_scale = 1.f;
+    int32_t* const rflag = split ? range_ptr(e) : nullptr;
     if (e->cfg.bayesian) {
         e->pre_valid = false;   // this pass's operands overwrite any prefetched ones
         // (lean: no f32 copy of sigma * eps - the passes read the planes; a raised range flag sends the whole call to the exact-f32 path, which makes its own operands.  Round 6
         //  measured the producer of pass p + 1 beside the forward kernel of pass p, into a second plane buffer: -2 % on a call, +10 % on an evaluation step - removed,
         //  profiles/r6_eval_prefetch_ab.md)
-        const bool nof32 = e->lean && !inj && e->pl_wp && range_ptr(e);
+        // (the exact-f32 kernel: the f32 sigma * eps and no planes)
+        const bool nof32 = split && e->lean && !inj && e->pl_wp && rflag;
         { Scope t(e, F_FLIPOUT_OPERAND);
           // (the planes of mu are the first pass's: the passes of one call run back to back on unchanged parameters, and the range flag they share is read behind the last)
           launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT], nullptr, lo.nw(), normal_spec(e, c, e->L - 1, T_EPS_W), nof32 ? nullptr : e->Wp[e->L - 1], 0.0, e->d_kl,
-                                 e->pl_wp, pass == 0 ? e->pl_mu : nullptr, f.mu, lo.in, kW16Scale, range_ptr(e));
+                                 split ? e->pl_wp : nullptr, split && pass == 0 ? e->pl_mu : nullptr, f.mu, lo.in, kW16Scale, rflag);
           launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS], nullptr, lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1], 0.0, e->d_kl); }
         f.wp = e->Wp[e->L - 1]; f.bp = e->bp[e->L - 1];
         f.s_in = sign_spec(e, c, e->L - 1, T_S_IN, lo.in); f.s_out = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out);
         f.planes_ready = 1;
     }
-    f.probs = 1; f.pacc = pass > 0; f.pscale = 1.0f / (float)passes; f.plogit = logits; f.rflag = range_ptr(e);
+    f.probs = 1; f.pacc = pass > 0; f.pscale = 1.0f / (float)passes; f.plogit = logits; f.rflag = rflag;
     { Scope t(e, F_OUT_FUSED_AUX); launch_fused_out_fwd(e->st, f, 1); }
     { Scope t(e, F_OUT_FUSED_FWD); launch_fused_out_fwd(e->st, f, 2); }
     { Scope t(e, F_INFER); launch_fused_probs_finish(e->st, B, lo.in, M, e->fws, e->dZout, e->Pbuf, want_unc ? e->ent_mc : nullptr, 1.0f / (float)passes, pass == passes - 1); }
@@ -1826,17 +1839,22 @@ static int infer_probs(ntf_engine* e, const int64_t* rows, int32_t B, int32_t nm
     if (!e->Pbuf) DM(e, &e->Pbuf, (int64_t)e->cfg.max_batch * M);
     const int passes = e->cfg.bayesian ? std::max(1, nmc) : 1;
     if (want_unc) HIPCHK(e, hipMemsetAsync(e->ent_mc, 0, (size_t)B * 4, e->st));
-    if (e->pl_mu && fused_ok(e)) {     // split-product forward kernel (H = 128): no dense logits, MC mean accumulated on the fly
+    if (infer_fused(e)) {     // fused forward kernel: no dense logits, MC mean accumulated on the fly
         const uint64_t step0 = e->step;
-        if (range_ptr(e)) HIPCHK(e, hipMemsetAsync(e->d_range, 0, 4, e->st));
-        for (int p = 0; p < passes; ++p) { int r = infer_pass_fused(e, rows, B, inj_per_mc ? &inj_per_mc[p] : nullptr, p, passes, want_unc, false); if (r) return r; }
-        bool raised; int r = range_raised(e, raised); if (r) return r;
-        if (!raised) {
-            if (want_unc) { Scope t(e, F_INFER); launch_row_entropy(e->st, e->Pbuf, B, M, e->ent_mean); }
-            return NTF_OK;
+        bool split = infer_split(e);      // the split-product kernel (H = 128); without planes, and behind a raised range flag, the exact-f32 one
+        for (int arm = 0; arm < 2; ++arm) {
+            if (split && range_ptr(e)) HIPCHK(e, hipMemsetAsync(e->d_range, 0, 4, e->st));
+            for (int p = 0; p < passes; ++p) { int r = infer_pass_fused(e, rows, B, inj_per_mc ? &inj_per_mc[p] : nullptr, p, passes, want_unc, false, split); if (r) return r; }
+            bool raised = false; if (split) { int r = range_raised(e, raised); if (r) return r; }
+            if (!raised) {
+                if (want_unc) { Scope t(e, F_INFER); launch_row_entropy(e->st, e->Pbuf, B, M, e->ent_mean); }
+                return NTF_OK;
+            }
+            e->step = step0;   // an operand left the fp16 window: the same passes (same generator keys) again on the exact-f32 kernel (NTF_INFER_F32=0: the generic chain below)
+            split = false;
+            if (want_unc) HIPCHK(e, hipMemsetAsync(e->ent_mc, 0, (size_t)B * 4, e->st));
+            if (!e->infer_f32) break;
         }
-        e->step = step0;   // an operand left the fp16 window: the same passes (same generator keys) again on the exact-f32 path below
-        if (want_unc) HIPCHK(e, hipMemsetAsync(e->ent_mc, 0, (size_t)B * 4, e->st));
     }
     for (int p = 0; p < passes; ++p) {
         StepCtx c; int r = infer_pass(e, rows, B, inj_per_mc ? &inj_per_mc[p] : nullptr, c); if (r) return r;

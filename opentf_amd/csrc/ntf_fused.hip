@@ -77,8 +77,12 @@ __global__ void k_prep_h(SignSpec si, int bayes, const float* __restrict__ h, in
 // H = 256: a 64-expert tile of both matrices (128 KiB) does not fit twice into LDS.  It is staged as NKH = 2 hidden halves of HS = 128 units, one after the
 // other through the same two buffers (each stage has H = 128's layout), the zT accumulators running on over both halves; the epilogue follows the last half.
 // d(hidden) does not fit into the registers beside the h operand at 256: DH is H <= 128 only (k_out_dh computes it at 256).
-template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ>
+// PROBS (inference, TRAIN = false): as in k_out_fwd_b6 - instead of the loss, sigmoid(leaky_relu(z)) * pscale goes (added to what the earlier MC passes left, pacc) to
+// the transposed buffer dzT, or leaky_relu(z) itself (plogit), and lossp gets the row's entropy terms sum_c -p log(p + 1e-15) of this pass.  An inference call whose
+// split-product passes raised the range flag is redone on this form by the HOST (infer_probs: the f32 sigma * eps has to be produced first), as unconditional launches (rmode 0).
+template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ, bool PROBS = false>
 __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem) {
+    static_assert(!PROBS || (!TRAIN && !DH), "the probability epilogue replaces the loss: forward only");
     constexpr int HS = H > 128 ? 128 : H;    // hidden units per stage
     constexpr int NKH = H / HS;              // stages per tile
     static_assert(!DH || NKH == 1, "the forward kernel's d(hidden) products are H <= 128 only");
@@ -212,6 +216,15 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
         const int dz_voff = ((i >> 5) * 8192 + 4 * half * 32 + (i & 31)) * 4;
         const float* bias_mu = reinterpret_cast<const float*>(sb + NMAT * TB) + 4 * half;
         const float* bias_p = reinterpret_cast<const float*>(sb + NMAT * TB + 256) + 4 * half;
+        float pold[2][16];   // PROBS, later MC passes: the running sums of this tile, fetched under the zT products of the last hidden part
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                pold[u][r] = 0.f;
+                if (PROBS && LAST && p.pacc)
+                    pold[u][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(dz_rsrc, dz_voff, (u * 32 + (r & 3) + 8 * (r >> 2)) * dz_row_bytes, 0));
+            }
 
         // operand fetch and MFMA issue are separate so that the fetch for group g+1 can be issued before the MFMAs of group g
         // (one wave per SIMD: nobody else hides the LDS latency)
@@ -251,6 +264,13 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
             const float l = pos ? z : z * kLeakySlope;
             const float lc = fmaxf(l, -80.f);
             const float tt = 1.f + __builtin_amdgcn_exp2f(lc * -1.4426950408889634f);
+            if (PROBS) {
+                const float pr = __builtin_amdgcn_rcpf(tt) * rmask;       // experts past M: bias -1e30 -> tt = 1 + e^80 -> 0
+                lacc.tile = fmaf(-pr * 0.6931471805599453f, __builtin_amdgcn_logf(pr + 1e-15f), lacc.tile);
+                const float o = p.plogit ? l : fmaf(pr, p.pscale, pold[u][r]);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), dz_rsrc, dz_voff, cr * dz_row_bytes, 0);
+                return;
+            }
             lacc.tile = fmaf(fmaf(__builtin_amdgcn_logf(tt), 0.6931471805599453f, lc), rmask, lacc.tile);
             if (TRAIN) {
                 const float dz = rscale * __builtin_amdgcn_rcpf(tt) * (pos ? 1.f : kLeakySlope);
@@ -333,10 +353,10 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
       });
     }
 
-    // per-row loss partial of this column group
+    // per-row loss (PROBS: entropy) partial of this column group
     float lsum = lacc.sum;
     lsum += __shfl_xor(lsum, 32, 64);
-    if (half == 0) p.lossp[(int64_t)i * p.NCG + cg] = p.tnw * lsum;
+    if (half == 0) p.lossp[(int64_t)i * p.NCG + cg] = PROBS ? lsum : p.tnw * lsum;
 
     if constexpr (TRAIN && DH) {
 #pragma unroll
@@ -365,6 +385,12 @@ template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ>
 __global__ __launch_bounds__(256, 1) void k_out_fwd(OutFwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     out_fwd_f32_body<H, BAYES, TRAIN, DH, INJ>(p, smem);
+}
+// the inference form (PROBS).  H <= 64: a stage pair is at most 66.5 KiB of LDS - two workgroups share a CU (eval_ncg), hence two waves per SIMD
+template <int H, bool BAYES, bool INJ>
+__global__ __launch_bounds__(256, H <= 64 ? 2 : 1) void k_out_probs(OutFwdArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    out_fwd_f32_body<H, BAYES, false, false, INJ, true>(p, smem);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -516,8 +542,6 @@ __global__ void k_split_planes(const float* __restrict__ W, int M, int H, float 
 struct OutFwd6Args {
     OutFwdArgs a;
     const uint16_t *mu_pl, *wp_pl;   // k_split_planes images of mu and Wp
-    float pscale; int pacc;          // PROBS: dzT[c][i] (+)= sigmoid(leaky_relu(z)) * pscale; pacc: accumulate onto the previous MC passes
-    int plogit;                      // PROBS: store the logit leaky_relu(z) itself instead (ntf_logits: the quantity the 1e-4 parity bar is stated on)
     unsigned long long* stamps;           // diagnostics (k_out_fwd_h3p<.., STAMP>, -DNTF_DIAG builds): per wave cycle sums
     float h_scale, dz_scale, u_z, u_dh;   // scales applied to h / dz before their split, and 1/(w scale * h scale), 1/(dz scale * w scale)
 };
@@ -661,7 +685,7 @@ __global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {
         if (PROBS) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                pold[r] = pp.pacc ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(dz_rsrc, dz_voff, ((r & 3) + 8 * (r >> 2)) * dz_row_bytes, 0)) : 0.f;
+                pold[r] = p.pacc ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(dz_rsrc, dz_voff, ((r & 3) + 8 * (r >> 2)) * dz_row_bytes, 0)) : 0.f;
         }
 
         // ---- zT = mu . hT (+ Wp . (h*s_in)T): 8 k-steps of 16 hidden units; half-groups (k-step, matrix) of 2 fragment reads + 3 MFMAs,
@@ -709,7 +733,7 @@ __global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {
             if (PROBS) {
                 const float pr = __builtin_amdgcn_rcpf(tt) * rmask;       // experts past M: bias -1e30 -> tt = 1 + e^80 -> 0
                 lacc.tile = fmaf(-pr * 0.6931471805599453f, __builtin_amdgcn_logf(pr + 1e-15f), lacc.tile);
-                const float o = pp.plogit ? l : fmaf(pr, pp.pscale, pold[r]);
+                const float o = p.plogit ? l : fmaf(pr, p.pscale, pold[r]);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), dz_rsrc, dz_voff, cr * dz_row_bytes, 0);
                 return;
             }
@@ -1432,7 +1456,14 @@ static void fwd_dispatch(hipStream_t st, const FusedOut& f, const OutFwdArgs& a,
         }                                                                                                                 \
         if (phases & 4) launch_out_special(st, H, BAYES, TR, DHF, s);                                                     \
     } while (0)
-    if (!f.train) NTF_LAUNCH_FWD(false, false);
+    if (f.probs) {      // inference: probabilities / logits to the transposed buffer, entropy partials to the workspace; no fix-up
+        if (phases & 2) {
+            auto kf = inj ? k_out_probs<H, BAYES, BAYES> : k_out_probs<H, BAYES, false>;
+            set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);
+            hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, st, a);
+        }
+    }
+    else if (!f.train) NTF_LAUNCH_FWD(false, false);
     else if (dh) NTF_LAUNCH_FWD(true, true);
     else NTF_LAUNCH_FWD(true, false);
 #undef NTF_LAUNCH_FWD
@@ -1440,7 +1471,7 @@ static void fwd_dispatch(hipStream_t st, const FusedOut& f, const OutFwdArgs& a,
 
 void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
     Geom g = geom(f.B, f.M);
-    if (!f.train && f.H == 128) g.NCG = eval_ncg(g);      // forward-only launches: two workgroups per CU (k_out_fwd_b6)
+    if (!f.train && (f.H == 128 || (f.probs && f.H <= 64))) g.NCG = eval_ncg(g);      // forward-only launches: two workgroups per CU (k_out_fwd_b6; k_out_probs at H <= 64)
     // the loss of an evaluation step in fp16x3 (round 6): k_out_fwd_h3e - 256-row workgroups of eight logit waves, one per CU.  NTF_EVAL_KERNEL=0: k_out_fwd_b6 (A/B runs, tests)
     // (Flipout only: with one matrix a sub-tile is 24 MFMAs against the same logit work, and the two workgroups per CU of k_out_fwd_b6 measured 0.309 against 0.317 ms a step)
     const bool evalp = f.eval_kernel && (f.bayes || f.eval_kernel == 2) && !f.train && !f.probs && f.split && f.H == 128 && f.chunk_ncg_tot == 0;
@@ -1467,6 +1498,7 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
     a.tnw = f.tnw; a.inv_B = f.inv_B; a.dzT = f.dzT; a.slab = f.dh_slab; a.lossp = lossp;
     a.so_k0 = f.s_out.k0; a.so_k1 = f.s_out.k1; a.si_k0 = f.s_in.k0; a.si_k1 = f.s_in.k1; a.so_inj = f.s_out.inj != nullptr; a.si_inj = f.s_in.inj != nullptr;
     a.rflag = f.rflag; a.rmode = 0;
+    a.pscale = f.pscale; a.pacc = f.pacc; a.plogit = f.plogit;
     a.t_lo = 0; a.t_hi = g.T; a.cg_off = 0; a.ncg_tot = g.NCG;
     const bool ranged = f.chunk_ncg_tot > 0;      // the split-product forward of this step runs (ran) as launches over ranges of the experts (FusedOut.chunk_*)
     SpecialArgs s;
@@ -1488,7 +1520,7 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
             if (f.bayes) hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f.wp, f.M, f.H, f.w_scale, f.wp_pl, guard ? f.rflag : nullptr);
         }
         if (phases & 2) {
-            OutFwd6Args a6; a6.stamps = nullptr; a6.a = a; a6.mu_pl = f.mu_pl; a6.wp_pl = f.wp_pl; a6.pscale = f.pscale; a6.pacc = f.pacc; a6.plogit = f.plogit;
+            OutFwd6Args a6; a6.stamps = nullptr; a6.a = a; a6.mu_pl = f.mu_pl; a6.wp_pl = f.wp_pl;
             a6.a.rmode = guard ? 1 : 0;
             a6.h_scale = f.h_scale; a6.dz_scale = f.dz_scale;
             a6.u_z = 1.f / (f.w_scale * f.h_scale); a6.u_dh = 1.f / (f.dz_scale * f.w_scale);
@@ -1589,7 +1621,7 @@ __global__ __launch_bounds__(256) void k_transpose_pt(const float* __restrict__ 
 void launch_fused_probs_finish(hipStream_t st, int B, int H, int M, void* ws_, const float* PT, float* P, float* ent_rows /*nullable: += this pass * scale*/, float scale, bool transpose,
                                float unpack_inv_scale) {
     Geom g = geom(B, M);
-    if (H == 128) g.NCG = eval_ncg(g);      // (the inference launches' column groups, launch_fused_out_fwd)
+    if (H <= 128) g.NCG = eval_ncg(g);      // (the inference launches' column groups, launch_fused_out_fwd: every width but 256)
     const WsLayout w = ws_layout(B, H, M);
     if (ent_rows) hipLaunchKernelGGL(k_ent_slots, dim3((B + 255) / 256), dim3(256), 0, st, reinterpret_cast<const float*>(static_cast<char*>(ws_) + w.lossp), B, g.NCG, scale, ent_rows);
     if (transpose) hipLaunchKernelGGL(k_transpose_pt, dim3((M + 31) / 32, g.Bpad / 32), dim3(256), 0, st, PT, M, g.Bpad, B, P, unpack_inv_scale);

@@ -132,6 +132,9 @@ struct OutFwdArgs {
     // fp16x3 range guard: rmode 1 (split-product kernels) = do nothing when *rflag is raised; rmode 2 (the exact-f32 kernels launched right
     // behind them) = run ONLY then, and count the step in rflag[1]; rmode 0 = unconditional
     int* rflag; int rmode;
+    // inference (the PROBS forms of k_out_fwd / k_out_fwd_b6): dzT[c][i] (+)= sigmoid(leaky_relu(z)) * pscale; pacc: accumulate onto the previous MC passes;
+    // plogit: store the logit leaky_relu(z) itself instead (ntf_logits: the quantity the 1e-4 parity bar is stated on)
+    float pscale; int pacc, plogit;
 };
 __device__ __forceinline__ bool range_guard_skip(int* rflag, int rmode, bool count) {
     if (rmode == 0) return false;
