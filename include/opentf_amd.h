@@ -253,7 +253,8 @@ int ntf_k_gemm_f32(void* stream, int m, int n, int k, const float* A, int64_t sa
 /* ---- ranking metrics of the eval stage on the device (next row after the hot path)            src/evl/metric.py:5-35,44-73
  * topk_idx [n, K]: expert ids ranked by decreasing score (ntf_forward_topk order).  The truth / required-skill row of instance i is
  * rows[i] (NULL: i) of the CSR.  out_metrics [n, 5*n_cut] = P, recall, ndcg_cut, map_cut, success, each over the cutoffs (trec_eval
- * definitions, binary relevance);  out_cov [n, n_cut] = |skills of the top-k experts ∩ required| / |required|. */
+ * definitions, binary relevance);  out_cov [n, n_cut] = |skills of the top-k experts ∩ required| / |required|.
+ * At most 8 cutoffs, each >= 1.  ntf_skill_coverage returns NTF_EINVAL when a selected required-skill row is empty (0 / 0). */
 int ntf_rank_metrics(int device, const int32_t* topk_idx, int64_t n, int32_t K, const int64_t* truth_indptr, const int32_t* truth_indices,
                      int64_t n_truth_rows, const int64_t* rows, const int32_t* cutoffs, int32_t n_cut, float* out_metrics);
 int ntf_skill_coverage(int device, const int32_t* topk_idx, int64_t n, int32_t K, const int64_t* skill_indptr, const int32_t* skill_indices,

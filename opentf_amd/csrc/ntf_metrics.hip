@@ -140,6 +140,8 @@ extern "C" int ntf_skill_coverage(int device, const int32_t* topk_idx, int64_t n
     if (!topk_idx || n < 1 || K < 1 || !skill_indptr || !cov_indptr || n_skill_rows < 1 || n_experts < 1 || !out || !make_cut(cutoffs, n_cut, c)) return NTF_EINVAL;
     if (rows) { for (int64_t i = 0; i < n; ++i) if (rows[i] < 0 || rows[i] >= n_skill_rows) return NTF_EINVAL; } else if (n > n_skill_rows) return NTF_EINVAL;
     for (int64_t i = 0; i < n * K; ++i) if (topk_idx[i] < 0 || topk_idx[i] >= n_experts) return NTF_EINVAL;
+    // an instance without a required skill has no coverage (0 / 0; the reference raises ZeroDivisionError there): refused, never a NaN in the table
+    for (int64_t i = 0; i < n; ++i) { const int64_t r = rows ? rows[i] : i; if (skill_indptr[r + 1] <= skill_indptr[r]) return NTF_EINVAL; }
     if (hipSetDevice(device) != hipSuccess) return NTF_EHIP;
     DevBuf dk, sip, six, dr, cip, cix, dout;
     if (!dk.put(topk_idx, (size_t)n * K * 4) || !sip.put(skill_indptr, (size_t)(n_skill_rows + 1) * 8) || !six.put(skill_indices, (size_t)skill_indptr[n_skill_rows] * 4) ||

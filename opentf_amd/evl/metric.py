@@ -139,6 +139,9 @@ def calculate_skill_coverage(X, Y_, expertskillvecs, per_instance=False, topks="
     cov = sp.csr_matrix(expertskillvecs); cov.sort_indices()
     cuts = [int(k) for k in topks.split(",")]
     n, E = Y_.shape
+    empty = np.nonzero(np.diff(X.indptr) == 0)[0]
+    if len(empty):  # 0 / 0 in the reference (ZeroDivisionError, src/evl/metric.py:69); a NaN here would silently poison the mean
+        raise libntf.NtfError(f"skill coverage is undefined for instance {int(empty[0])}: it has no required skill ({len(empty)} such instance(s))")
     top = _ranked_topk(Y_, min(max(cuts), E))
     out = np.zeros((n, len(cuts)), dtype=np.float32)
     cu = np.ascontiguousarray(cuts, dtype=np.int32)

@@ -31,6 +31,22 @@ class _neg_str:
     def __eq__(self, o): return self.s == o.s
 
 
+TIEBREAK_TINY = 1e-9
+
+
+def tiebreak_free_dense(S, tiny: float = TIEBREAK_TINY) -> np.ndarray:
+    """f64 scores WITHOUT ties that spell out the device ranking of a scipy CSR prediction matrix with positive stored scores: the stored
+    entries by their score, then the experts the row does not store, which all score 0, by ascending id (-(id + 1) * tiny decreases with
+    id).  The fill values are negative, so below every stored score, and multiples of `tiny`, so distinct in f64."""
+    n, M = S.shape
+    D = np.tile(-(np.arange(M, dtype=np.float64) + 1.0) * tiny, (n, 1))
+    for i in range(n):
+        sl = slice(S.indptr[i], S.indptr[i + 1])
+        assert (S.data[sl] > 0).all()
+        D[i, S.indices[sl]] = S.data[sl].astype(np.float64)
+    return D
+
+
 def trec_metrics(ranked: np.ndarray, relevant: set, cutoffs) -> dict:
     """P_k, recall_k, ndcg_cut_k, map_cut_k, success_k for binary relevance (gain 1, log2 discount)."""
     R = len(relevant)
@@ -62,6 +78,19 @@ def skill_coverage(scores_row: np.ndarray, required_skills: np.ndarray, cov_indp
     for k in cutoffs:
         have = set()
         for e in order[:k]:
+            have.update(int(s) for s in cov_indices[cov_indptr[e]:cov_indptr[e + 1]])
+        out[f"skill_coverage_{k}"] = len(have & req) / len(req)
+    return out
+
+
+def skill_coverage_ranked(ranked, required_skills, cov_indptr, cov_indices, cutoffs) -> dict:
+    """`skill_coverage` for a ranking that is already made: `ranked` holds expert ids by decreasing score (a cutoff above len(ranked)
+    takes the whole list).  Raises ZeroDivisionError for an instance without a required skill, as the reference does."""
+    req = set(int(s) for s in required_skills)
+    out = {}
+    for k in cutoffs:
+        have = set()
+        for e in ranked[:k]:
             have.update(int(s) for s in cov_indices[cov_indptr[e]:cov_indptr[e + 1]])
         out[f"skill_coverage_{k}"] = len(have & req) / len(req)
     return out

@@ -434,10 +434,13 @@ def test_forward_probs_uncertainty_h128(bayesian, mfma):
         assert np.array_equal(idx, order)
 
 
-@pytest.mark.parametrize("M,K,ties", [(40000, 50, False), (70001, 100, False), (40000, 20, True), (33000, 256, False)])
+@pytest.mark.parametrize("M,K,ties", [(40000, 50, False), (70001, 100, False), (40000, 20, True), (33000, 256, False),
+                                      (40000, 257, False), (40000, 2048, False), (2048, 2048, False), (70001, 1, False)])
 def test_topk_sampled_threshold_path_is_exact(M, K, ties):
     """Rows long enough for the sampled-threshold selection (ntf_kernels.hip k_topk_rows): the result must be the exact, deterministic
-    ranking (value descending, expert id ascending among equals) — also when a tie group straddles the K-th place."""
+    ranking (value descending, expert id ascending among equals) — also when a tie group straddles the K-th place.  K above 256 leaves
+    the sampled path for the exact radix selection on a long row (257: the first such K; 2048: the sort's capacity); K = M ranks the
+    whole row; K = 1 sorts nothing."""
     torch.manual_seed(M)
     fsd = O.fnn_init(16, [32], M)
     if ties:   # many experts share one weight row and bias -> identical probabilities
@@ -451,6 +454,49 @@ def test_topk_sampled_threshold_path_is_exact(M, K, ties):
         order = np.lexsort((np.arange(M), -p[i].astype(np.float64)))[:K]     # value desc, id asc
         assert np.array_equal(idx[i], order), i
         assert np.array_equal(vals[i], p[i][order])
+
+
+@pytest.mark.parametrize("M", [40000, 300])
+def test_topk_when_all_but_ten_probabilities_are_exactly_zero(M):
+    """An output bias of -1e6 saturates the sigmoid: the last layer's leaky_relu (slope 0.01) leaves a logit of about -1e4, and
+    1 / (1 + e^10000) is far below the smallest f32 denormal, so every expert but ten has probability exactly +0.0 (bit pattern 0, the
+    smallest key of the radix selection) and the K-th place falls inside that tie group.
+    The ten experts with a probability come first, by value; then the ten lowest ids among the zeros, each with value 0.0."""
+    K = 20
+    torch.manual_seed(M)
+    fsd = O.fnn_init(16, [32], M)
+    live = np.sort(np.random.default_rng(M).choice(np.arange(15, M), 10, replace=False))     # ids 0..14 stay zero: ten of them must follow
+    bias = torch.full((M,), -1.0e6); bias[torch.from_numpy(live)] = 0.0
+    fsd["layers.1.bias"] = bias
+    X = torch.randn(12, 16)
+    f = _engine([16, 32, M], max_batch=12)
+    f.load_state_dict(fsd); f.set_dense_input(X.numpy())
+    p = f.forward(np.arange(12))
+    dead = np.setdiff1d(np.arange(M), live)
+    assert not p[:, dead].view(np.uint32).any() and (p[:, live] > 0).all()                   # exactly +0.0, not a denormal, not -0.0
+    vals, idx = f.forward_topk(np.arange(12), K)
+    for i in range(12):
+        order = live[np.lexsort((live, -p[i, live].astype(np.float64)))]
+        assert np.array_equal(idx[i, :10], order), i
+        assert np.array_equal(vals[i, :10], p[i, order]) and (vals[i, :10] > 0).all()
+        assert np.array_equal(idx[i, 10:], np.arange(10)), (i, idx[i, 10:])
+        assert not vals[i, 10:].view(np.uint32).any()
+
+
+def test_topk_refuses_k_above_the_row_or_the_sort_capacity():
+    from opentf_amd.libntf import NtfError
+    f = _engine([16, 32, 40000], max_batch=4)
+    f.load_state_dict(O.fnn_init(16, [32], 40000)); f.set_dense_input(np.zeros((4, 16), np.float32))
+    assert f.forward_topk(np.arange(4), 2048)[1].shape == (4, 2048)
+    with pytest.raises(NtfError):
+        f.forward_topk(np.arange(4), 2049)           # above the LDS sort's capacity
+    g = _engine([16, 32, 300], max_batch=4)
+    g.load_state_dict(O.fnn_init(16, [32], 300)); g.set_dense_input(np.zeros((4, 16), np.float32))
+    assert g.forward_topk(np.arange(4), 300)[1].shape == (4, 300)
+    with pytest.raises(NtfError):
+        g.forward_topk(np.arange(4), 301)            # K = M + 1
+    with pytest.raises(NtfError):
+        g.forward_topk(np.arange(4), 0)
 
 
 def test_epoch_api_matches_step_api():
