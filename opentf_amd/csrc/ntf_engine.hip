@@ -124,7 +124,7 @@ struct ntf_engine {
     // step's sigma * eps and KL in one pass, on the side stream beside the dW kernel.  pre0_step: the step whose Wp[0] / KL the last sweep produced (used iff that step also
     // starts on the output layer's prefetched operands: one validity protocol, pre_valid / pre_step); l0_swept: this step's Adam of the layer's weights ran in the sweep
     // (apply_adam leaves them out); g0_clean: the layer's gradient rows are all zero (the sweep clears what it reads: no memset in front of the scatter)
-    int infer_f32 = 1;                // NTF_INFER_F32=0 (A/B runs, tests): inference without the split planes (h[-1] of 32, 64, 256; 128 with mfma = NTF_MFMA_F32; a raised range flag) on the
+    int infer_f32 = 1;                // NTF_INFER_F32=0 (A/B runs, tests): inference without the split planes (h[-1] of 32, 64, 96, 160, 192, 224, 256; 128 with mfma = NTF_MFMA_F32; a raised range flag) on the
                                       // generic chain - k_gemm into dense [B, M] logits + launch_sigmoid_acc per MC pass - instead of the exact-f32 fused kernel k_out_probs
     int eval_kernel = 1;              // NTF_EVAL_KERNEL=0 (A/B runs, tests): evaluation steps on k_out_fwd_b6 as in round 5 instead of k_out_fwd_h3e
     int mh_head = 1;                  // NTF_MH_HEAD=0 (A/B runs): a multi-hot step's head (first-layer operands, gather-sum, h images) inline in its own step as in rounds 1-5; 1 (round 6): as ONE
@@ -284,7 +284,7 @@ extern "C" int ntf_engine_create(const ntf_config* cfg, ntf_engine** out) {
     if (cfg->fused && !fused_supported(e->layers[e->L - 1].in) && (int64_t)cfg->dims[e->L] >= 4096 && !getenv("NTF_QUIET")) {
         // (a hidden width outside {32, 64, 128} fell to the generic chain - k_gemm + dense [B, M] loss - without a word: 59 k teams/s against ~740 k at config 2's size)
         static bool warned = false;
-        if (!warned) fprintf(stderr, "opentf_amd: h[-1] = %d has no fused output-layer kernels (32, 64, 128 and 256 have; 128 also the split-product ones): this model runs on the "
+        if (!warned) fprintf(stderr, "opentf_amd: h[-1] = %d has no fused output-layer kernels (32, 64, 96, 128, 160, 192, 224 and 256 have; 128 also the split-product ones): this model runs on the "
                                      "generic GEMM + dense-loss chain, an order of magnitude slower at %d experts (INTEGRATION.md, limits)\n", e->layers[e->L - 1].in, cfg->dims[e->L]);
         warned = true;
     }
@@ -293,7 +293,9 @@ extern "C" int ntf_engine_create(const ntf_config* cfg, ntf_engine** out) {
     e->ep = cfg->experts_global > 0 || e->ep_lo != 0 || e->ep_world > 1;   // a shard may also be the whole layer (ep_world = 1)
     if (e->ep) {
         const char* bad = nullptr;
-        if (!fused_ok(e)) bad = "an expert-sharded output layer needs the fused output-layer path (fused = 1, h[-1] in {32, 64, 128, 256})";
+        const int hl = e->layers[e->L - 1].in;
+        // (96, 160, 192 and 224 have the fused kernels on one GPU only: their shards are not covered by the expert-parallel tests, opentf_amd.ep.can_shard refuses them too)
+        if (!fused_ok(e) || !(hl == 32 || hl == 64 || hl == 128 || hl == 256)) bad = "an expert-sharded output layer needs the fused output-layer path (fused = 1) at h[-1] in {32, 64, 128, 256}; 96, 160, 192 and 224 have it on one GPU and on data-parallel ranks, not as expert shards";
         else if (e->ep_lo < 0 || (e->ep_lo & 255)) bad = "expert_lo must be a non-negative multiple of 256";
         else if ((int64_t)e->ep_lo + cfg->dims[e->L] > e->Mg) bad = "expert_lo + dims[n_layers] exceeds experts_global";
         if (bad) { g_create_error = bad; if (e->own_stream) hipStreamDestroy(e->st); delete e; return NTF_EINVAL; }
@@ -601,8 +603,8 @@ static inline float dz_scale16(const ntf_engine* e, int global_B) {   // |dz| <=
     return std::exp2(std::floor(std::log2(16384.f / dzmax)));
 }
 
-// the fused output layer has split-product (fp16x3) kernels: h[-1] <= 128 (256 runs on the exact-f32 kernels in every mfma mode)
-static bool split_products(const ntf_engine* e) { return e->layers[e->L - 1].in <= 128; }
+// the fused output layer has split-product (fp16x3) kernels: h[-1] of 32, 64 and 128 (96, 160, 192, 224 and 256 run on the exact-f32 kernels in every mfma mode)
+static bool split_products(const ntf_engine* e) { const int h = e->layers[e->L - 1].in; return h == 32 || h == 64 || h == 128; }
 // the range flag of the fp16x3 arithmetic, or null when this engine never multiplies in fp16x3
 static int32_t* range_ptr(const ntf_engine* e) {
     return (fused_ok(e) && split_products(e) && (e->cfg.mfma == NTF_MFMA_DEFAULT || e->cfg.mfma == NTF_MFMA_FP16X3)) ? e->d_range : nullptr;

@@ -22,10 +22,11 @@ int fused_ldb(int B) { return rup(B, BM); }
 int fused_dw_tile() { return DW_TC; }
 int64_t fused_dw_part_floats(int M, int H, int ksplit) { return (int64_t)ksplit * 2 * ((int64_t)rup(M, DW_TC) * (H + 1)); }
 int64_t fused_planes_elems(int M, int H) { return ((int64_t)M + 63) / 64 * 64 * H * 2; }   // hi and lo plane, rows padded to the 64-expert tile of k_out_fwd_h3p / _h3e
-bool fused_supported(int H) { return H == 32 || H == 64 || H == 128 || H == 256; }   // 256: exact-f32 kernels only (no split-product form)
+// 256: exact-f32 kernels only (no split-product form); 96 runs H = 128's exact-f32 kernels, 160 / 192 / 224 run H = 256's, on rows narrower than the tile (fused_tmpl)
+bool fused_supported(int H) { const int Ht = fused_tmpl(H); return Ht == 32 || Ht == 64 || Ht == 128 || Ht == 256; }
 int fused_loss_slots(int) { return 0; }
 
-int64_t fused_dh_slab_floats(int, int H, int) { return (int64_t)4 * NCG_MAX * BM * H; }   // (x 4: up to four range launches of the forward kernel, each with its own column groups)
+int64_t fused_dh_slab_floats(int, int H, int) { return (int64_t)4 * NCG_MAX * BM * fused_tmpl(H); }   // (x 4: up to four range launches of the forward kernel, each with its own column groups)
 
 size_t fused_workspace_bytes(int B, int H, int M) { return ws_layout(B, H, M).total; }
 FusedWsPtrs fused_ws_ptrs(void* ws_, int B, int H, int M) {
@@ -53,24 +54,26 @@ __global__ __launch_bounds__(64) void k_sign_bits(SignSpec so, int B, int M, int
 
 // hz = h zero-padded to Bpad rows (so that DMA / MFMA never touch stale rows); Flipout: sinbits and hs = h * s_in
 // h_limit > 0 (fp16x3 arithmetic): an activation beyond the fp16 window of the scaled split raises *rflag (the step then runs on the f32 kernels)
-__global__ void k_prep_h(SignSpec si, int bayes, const float* __restrict__ h, int B, int H, int Bpad, uint32_t* __restrict__ sinbits,
+// Ht > H (fused_tmpl): hz / hs rows are Ht wide with zero columns behind the H real ones; sinbits keeps H / 32 words a row
+__global__ void k_prep_h(SignSpec si, int bayes, const float* __restrict__ h, int B, int H, int Ht, int Bpad, uint32_t* __restrict__ sinbits,
                          float* __restrict__ hs, float* __restrict__ hz, float h_limit, int* __restrict__ rflag) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int wpr = H / 32;
+    const int wpr = Ht / 32, nw = H / 32;
     if (t >= Bpad * wpr) return;
     const int i = t / wpr, wj = t % wpr;
+    const bool real = wj < nw;
     uint32_t w = 0;
-    if (bayes && i < B) {
+    if (bayes && i < B && real) {
         if (si.inj) { for (int b = 0; b < 32; ++b) if (si.inj[(int64_t)i * si.ld + wj * 32 + b] < 0.f) w |= 1u << b; }
         else w = sign_word(si.k0, si.k1, (uint32_t)i, (uint32_t)wj);
     }
-    if (bayes) sinbits[t] = w;
+    if (bayes && real) sinbits[(int64_t)i * nw + wj] = w;
     for (int b = 0; b < 32; ++b) {
         const int j = wj * 32 + b;
-        const float v = (i < B) ? h[(int64_t)i * H + j] : 0.f;
+        const float v = (i < B && real) ? h[(int64_t)i * H + j] : 0.f;
         if (rflag && !(fabsf(v) <= h_limit)) *rflag = 1;   // also catches NaN / inf
-        hz[(int64_t)i * H + j] = v;
-        if (bayes) hs[(int64_t)i * H + j] = ((w >> b) & 1u) ? -v : v;
+        hz[(int64_t)i * Ht + j] = v;
+        if (bayes) hs[(int64_t)i * Ht + j] = ((w >> b) & 1u) ? -v : v;
     }
 }
 
@@ -80,7 +83,10 @@ __global__ void k_prep_h(SignSpec si, int bayes, const float* __restrict__ h, in
 // PROBS (inference, TRAIN = false): as in k_out_fwd_b6 - instead of the loss, sigmoid(leaky_relu(z)) * pscale goes (added to what the earlier MC passes left, pacc) to
 // the transposed buffer dzT, or leaky_relu(z) itself (plogit), and lossp gets the row's entropy terms sum_c -p log(p + 1e-15) of this pass.  An inference call whose
 // split-product passes raised the range flag is redone on this form by the HOST (infer_probs: the f32 sigma * eps has to be produced first), as unconditional launches (rmode 0).
-template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ, bool PROBS = false>
+// PAD: the weight rows are p.Hr < H floats wide (fused_tmpl).  They are fetched at stride p.Hr; the 16-byte chunks of a stage whose hidden units lie at or past p.Hr
+// are sourced from zeros (the padding columns of row 0 of p.h) - never from the next row, which need not exist and may hold anything.  p.h has H columns, the last
+// H - p.Hr zero; the s_in words are p.Hr / 32 a row.  The swizzle, the LDS image and the MFMA sequence are the template width's.
+template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ, bool PROBS = false, bool PAD = false>
 __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem) {
     static_assert(!PROBS || (!TRAIN && !DH), "the probability epilogue replaces the loss: forward only");
     constexpr int HS = H > 128 ? 128 : H;    // hidden units per stage
@@ -95,6 +101,9 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
     constexpr int NJY = DH ? NJT : 1;        // d(hidden) accumulators
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, il = lane & 31, half = lane >> 5;
     if (range_guard_skip(p.rflag, p.rmode, true)) return;
+    const int Hr = PAD ? p.Hr : H;           // floats per weight row
+    const int nsw = PAD ? (p.Hr >> 5) : NJT; // s_in words per batch row
+    const float* const zsrc = p.h + Hr;      // PAD: 16 bytes of zeros for the chunks past the row's end
 
     // XCD-aware block -> (column group, row block): blocks that stream the same weight tiles share an XCD's L2
     int bid = blockIdx.x;
@@ -118,7 +127,7 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
     uint32_t sinw[NJT];
 #pragma unroll
     for (int w = 0; w < NJT; ++w)
-        sinw[w] = BAYES ? ((INJ ? p.sinbits[(int64_t)i * NJT + w] : (row_ok ? sign_word(p.si_k0, p.si_k1, (uint32_t)i, (uint32_t)w) : 0u)) >> (4 * half)) : 0u;
+        sinw[w] = (BAYES && (!PAD || w < nsw)) ? ((INJ ? p.sinbits[(int64_t)i * nsw + w] : (row_ok ? sign_word(p.si_k0, p.si_k1, (uint32_t)i, (uint32_t)w) : 0u)) >> (4 * half)) : 0u;
     const float rmask = row_ok ? 1.f : 0.f;                 // padding rows of the last row block contribute nothing
     const float rscale = row_ok ? p.tnw * p.inv_B : 0.f;
 
@@ -165,8 +174,10 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
             const int row = off / ROWB, pch = (off % ROWB) >> 4;
             const int q = pch ^ swz<HS>(row);
             const int64_t grow = min(c0 + row, p.M - 1);
-            glds16(p.mu + grow * H + kh * HS + 4 * q, sb + inst * 1024);
-            if (BAYES) glds16(p.wp + grow * H + kh * HS + 4 * q, sb + TB + inst * 1024);
+            const int ku = kh * HS + 4 * q;          // first hidden unit of the chunk
+            const bool in_row = !PAD || ku < Hr;
+            glds16(in_row ? p.mu + grow * Hr + ku : zsrc, sb + inst * 1024);
+            if (BAYES) glds16(in_row ? p.wp + grow * Hr + ku : zsrc, sb + TB + inst * 1024);
         }
         if (kh != NKH - 1) return;
         if (wave_u == 0) glds4(p.mu_b + min(c0 + lane, p.M - 1), sb + NMAT * TB);
@@ -372,7 +383,8 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
                 const int j = NJT * il + jt;  // this lane's hidden units are consecutive: one 4*NJT-byte store per register
                 v[jt] = Y1[jt][r];
                 if (BAYES) {
-                    const uint32_t w = INJ ? p.sinbits[(int64_t)irow * NJT + (j >> 5)] : sign_word(p.si_k0, p.si_k1, (uint32_t)irow, (uint32_t)(j >> 5));
+                    uint32_t w = 0u;             // (PAD: the columns past Hr have no sign word; their sums are zero and k_out_special drops them)
+                    if (!PAD || j < Hr) w = INJ ? p.sinbits[(int64_t)irow * nsw + (j >> 5)] : sign_word(p.si_k0, p.si_k1, (uint32_t)irow, (uint32_t)(j >> 5));
                     const float y2 = Y2[jt][r];
                     v[jt] += ((w >> (j & 31)) & 1u) ? -y2 : y2;
                 }
@@ -385,16 +397,16 @@ __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem
     }
 }
 
-template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ>
+template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ, bool PAD = false>
 __global__ __launch_bounds__(256, 1) void k_out_fwd(OutFwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    out_fwd_f32_body<H, BAYES, TRAIN, DH, INJ>(p, smem);
+    out_fwd_f32_body<H, BAYES, TRAIN, DH, INJ, false, PAD>(p, smem);
 }
 // the inference form (PROBS).  H <= 64: a stage pair is at most 66.5 KiB of LDS - two workgroups share a CU (eval_ncg), hence two waves per SIMD
-template <int H, bool BAYES, bool INJ>
+template <int H, bool BAYES, bool INJ, bool PAD = false>
 __global__ __launch_bounds__(256, H <= 64 ? 2 : 1) void k_out_probs(OutFwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    out_fwd_f32_body<H, BAYES, false, false, INJ, true>(p, smem);
+    out_fwd_f32_body<H, BAYES, false, false, INJ, true, PAD>(p, smem);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -406,7 +418,8 @@ __global__ __launch_bounds__(256, H <= 64 ? 2 : 1) void k_out_probs(OutFwdArgs p
 // double buffered by LDS-DMA.  MFMA k = expert: lane (il, half) feeds dz[i0 + il][c0 + 2k + half] (A) and W[c0 + 2k + half][8 il .. 8 il + 7] (B, one
 // 32-byte read per row and matrix for all eight column tiles); its accumulators hold 8 consecutive hidden units of the rows rowmap(r, half).
 // ------------------------------------------------------------------------------------------------
-template <bool BAYES, bool INJ>
+// PAD (160, 192, 224 hidden units): rows of p.Hr floats, the chunks past them staged from zeros as in the forward kernel; the slabs keep 256 columns.
+template <bool BAYES, bool INJ, bool PAD = false>
 __global__ __launch_bounds__(256, 1) void k_out_dh(OutFwdArgs p) {
     constexpr int H = 256, NJT = H / 32;
     constexpr int KE = 32;                   // experts per stage
@@ -427,6 +440,10 @@ __global__ __launch_bounds__(256, 1) void k_out_dh(OutFwdArgs p) {
     const int i0 = rb * BM + wave * 32;
     const int i = i0 + il;
     const bool row_ok = i < p.B;
+    const int Hr = PAD ? p.Hr : H;
+    const int nsw = PAD ? (p.Hr >> 5) : NJT;
+    const bool in_row = !PAD || 4 * lane < Hr;       // this lane's 16-byte chunk of a staged row lies inside the real row
+    const float* const zsrc = p.h + Hr;              // PAD: zeros (padding columns of row 0 of the zero-padded h)
 
     f32x16 acc1[NJT], acc2[NJT];
 #pragma unroll
@@ -442,8 +459,8 @@ __global__ __launch_bounds__(256, 1) void k_out_dh(OutFwdArgs p) {
         for (int n = 0; n < KE / 4; ++n) {
             const int row = wave_u * (KE / 4) + n;
             const int64_t grow = min(s * KE + row, p.M - 1);
-            glds16(p.mu + grow * H + 4 * lane, sb + row * ROWB);
-            if (BAYES) glds16(p.wp + grow * H + 4 * lane, sb + TB + row * ROWB);
+            glds16(in_row ? p.mu + grow * Hr + 4 * lane : zsrc, sb + row * ROWB);
+            if (BAYES) glds16(in_row ? p.wp + grow * Hr + 4 * lane : zsrc, sb + TB + row * ROWB);
         }
     };
     // A operands of stage s (issued one stage ahead, before that stage's DMA, and consumed behind the wait that publishes it): dz[i][c0 + 2k + half]
@@ -504,7 +521,7 @@ __global__ __launch_bounds__(256, 1) void k_out_dh(OutFwdArgs p) {
         const int irow = i0 + rowmap(r, half);
         float v[NJT];
         uint32_t si = 0u;                    // s_in word of the lane's eight hidden units 8 il .. 8 il + 7 (all in word il / 4)
-        if (BAYES) si = INJ ? p.sinbits[(int64_t)irow * NJT + (il >> 2)] : sign_word(p.si_k0, p.si_k1, (uint32_t)irow, (uint32_t)(il >> 2));
+        if (BAYES && (!PAD || 8 * il < Hr)) si = INJ ? p.sinbits[(int64_t)irow * nsw + (il >> 2)] : sign_word(p.si_k0, p.si_k1, (uint32_t)irow, (uint32_t)(il >> 2));
 #pragma unroll
         for (int jt = 0; jt < NJT; ++jt) {
             v[jt] = acc1[jt][r];
@@ -1436,7 +1453,7 @@ __global__ __launch_bounds__(512) void k_out_fwd_h3e(OutFwd6Args pp) {
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int H, bool BAYES>
+template <int H, bool BAYES, bool PAD = false>
 static void fwd_dispatch(hipStream_t st, const FusedOut& f, const OutFwdArgs& a, const SpecialArgs& s, int grid, int phases) {
     constexpr int HS = H > 128 ? 128 : H;                                   // hidden units per LDS stage (out_fwd_f32_body)
     constexpr int STAGE = (BAYES ? 2 : 1) * BN * 4 * HS + 512;
@@ -1447,22 +1464,22 @@ static void fwd_dispatch(hipStream_t st, const FusedOut& f, const OutFwdArgs& a,
 #define NTF_LAUNCH_FWD(TR, DHF)                                                                                           \
     do {                                                                                                                  \
         constexpr bool DHK = (DHF) && H <= 128;                                                                           \
-        auto kf = inj ? k_out_fwd<H, BAYES, TR, DHK, BAYES> : k_out_fwd<H, BAYES, TR, DHK, false>;                        \
+        auto kf = inj ? k_out_fwd<H, BAYES, TR, DHK, BAYES, PAD> : k_out_fwd<H, BAYES, TR, DHK, false, PAD>;              \
         if (phases & 2) {                                                                                                 \
             set_max_lds(reinterpret_cast<const void*>(kf), (int)lds); \
             hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, st, a);                                                    \
             if ((DHF) && H == 256) {                                                                                      \
-                auto kd = inj ? k_out_dh<BAYES, BAYES> : k_out_dh<BAYES, false>;                                          \
+                auto kd = inj ? k_out_dh<BAYES, BAYES, PAD> : k_out_dh<BAYES, false, PAD>;                                \
                 const size_t ldsd = 2 * (size_t)(BAYES ? 2 : 1) * 32 * 4 * 256;                                           \
                 set_max_lds(reinterpret_cast<const void*>(kd), (int)ldsd);                                                \
                 hipLaunchKernelGGL(kd, dim3(grid), dim3(256), ldsd, st, a);                                               \
             }                                                                                                             \
         }                                                                                                                 \
-        if (phases & 4) launch_out_special(st, H, BAYES, TR, DHF, s);                                                     \
+        if (phases & 4) launch_out_special(st, f.H, BAYES, TR, DHF, s);                                                   \
     } while (0)
     if (f.probs) {      // inference: probabilities / logits to the transposed buffer, entropy partials to the workspace; no fix-up
         if (phases & 2) {
-            auto kf = inj ? k_out_probs<H, BAYES, BAYES> : k_out_probs<H, BAYES, false>;
+            auto kf = inj ? k_out_probs<H, BAYES, BAYES, PAD> : k_out_probs<H, BAYES, false, PAD>;
             set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);
             hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, st, a);
         }
@@ -1475,7 +1492,8 @@ static void fwd_dispatch(hipStream_t st, const FusedOut& f, const OutFwdArgs& a,
 
 void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
     Geom g = geom(f.B, f.M);
-    if (!f.train && (f.H == 128 || (f.probs && f.H <= 64))) g.NCG = eval_ncg(g);      // forward-only launches: two workgroups per CU (k_out_fwd_b6; k_out_probs at H <= 64)
+    const int Ht = fused_tmpl(f.H);          // the kernels' width; Ht != f.H: their PAD forms on rows of f.H floats
+    if (!f.train && (Ht == 128 || (f.probs && Ht <= 64))) g.NCG = eval_ncg(g);      // forward-only launches: two workgroups per CU (k_out_fwd_b6; k_out_probs at H <= 64)
     // the loss of an evaluation step in fp16x3 (round 6): k_out_fwd_h3e - 256-row workgroups of eight logit waves, one per CU.  NTF_EVAL_KERNEL=0: k_out_fwd_b6 (A/B runs, tests)
     // (Flipout only: with one matrix a sub-tile is 24 MFMAs against the same logit work, and the two workgroups per CU of k_out_fwd_b6 measured 0.309 against 0.317 ms a step)
     const bool evalp = f.eval_kernel && (f.bayes || f.eval_kernel == 2) && !f.train && !f.probs && f.split && f.H == 128 && f.chunk_ncg_tot == 0;
@@ -1492,8 +1510,8 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
     const bool guard = f.rflag != nullptr;   // fp16x3 arithmetic somewhere in this step (forward and / or dW): range-checked operands
     if (inj && (phases & 1)) hipLaunchKernelGGL(k_sign_bits, dim3((g.nCB + 63) / 64, g.Bpad), dim3(64), 0, st, f.s_out, f.B, f.M, g.nCB, sbits);
     if ((phases & 1) && !f.h_ready) {
-        const int n = g.Bpad * (f.H / 32);
-        hipLaunchKernelGGL(k_prep_h, dim3((n + 63) / 64), dim3(64), 0, st, f.s_in, f.bayes, f.h, f.B, f.H, g.Bpad, sinbits, hs, hz,
+        const int n = g.Bpad * (Ht / 32);
+        hipLaunchKernelGGL(k_prep_h, dim3((n + 63) / 64), dim3(64), 0, st, f.s_in, f.bayes, f.h, f.B, f.H, Ht, g.Bpad, sinbits, hs, hz,
                            guard ? 65504.f / f.h_scale : 0.f, guard ? f.rflag : nullptr);
     }
     OutFwdArgs a;
@@ -1502,7 +1520,7 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
     a.tnw = f.tnw; a.inv_B = f.inv_B; a.dzT = f.dzT; a.slab = f.dh_slab; a.lossp = lossp;
     a.so_k0 = f.s_out.k0; a.so_k1 = f.s_out.k1; a.si_k0 = f.s_in.k0; a.si_k1 = f.s_in.k1; a.so_inj = f.s_out.inj != nullptr; a.si_inj = f.s_in.inj != nullptr;
     a.rflag = f.rflag; a.rmode = 0;
-    a.pscale = f.pscale; a.pacc = f.pacc; a.plogit = f.plogit;
+    a.pscale = f.pscale; a.pacc = f.pacc; a.plogit = f.plogit; a.Hr = f.H;
     a.t_lo = 0; a.t_hi = g.T; a.cg_off = 0; a.ncg_tot = g.NCG;
     const bool ranged = f.chunk_ncg_tot > 0;      // the split-product forward of this step runs (ran) as launches over ranges of the experts (FusedOut.chunk_*)
     SpecialArgs s;
@@ -1597,8 +1615,9 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
         }
         return;
     }
-#define NTF_H(HH) do { if (f.bayes) fwd_dispatch<HH, true>(st, f, a, s, grid, phases); else fwd_dispatch<HH, false>(st, f, a, s, grid, phases); } while (0)
-    if (f.H == 256) NTF_H(256); else if (f.H == 128) NTF_H(128); else if (f.H == 64) NTF_H(64); else NTF_H(32);
+#define NTF_H(HH, PD) do { if (f.bayes) fwd_dispatch<HH, true, PD>(st, f, a, s, grid, phases); else fwd_dispatch<HH, false, PD>(st, f, a, s, grid, phases); } while (0)
+    if (Ht != f.H) { if (Ht == 256) NTF_H(256, true); else NTF_H(128, true); }
+    else if (f.H == 256) NTF_H(256, false); else if (f.H == 128) NTF_H(128, false); else if (f.H == 64) NTF_H(64, false); else NTF_H(32, false);
 #undef NTF_H
 }
 
@@ -1625,7 +1644,7 @@ __global__ __launch_bounds__(256) void k_transpose_pt(const float* __restrict__ 
 void launch_fused_probs_finish(hipStream_t st, int B, int H, int M, void* ws_, const float* PT, float* P, float* ent_rows /*nullable: += this pass * scale*/, float scale, bool transpose,
                                float unpack_inv_scale) {
     Geom g = geom(B, M);
-    if (H <= 128) g.NCG = eval_ncg(g);      // (the inference launches' column groups, launch_fused_out_fwd: every width but 256)
+    if (fused_tmpl(H) <= 128) g.NCG = eval_ncg(g);      // (the inference launches' column groups, launch_fused_out_fwd: every template width but 256)
     const WsLayout w = ws_layout(B, H, M);
     if (ent_rows) hipLaunchKernelGGL(k_ent_slots, dim3((B + 255) / 256), dim3(256), 0, st, reinterpret_cast<const float*>(static_cast<char*>(ws_) + w.lossp), B, g.NCG, scale, ent_rows);
     if (transpose) hipLaunchKernelGGL(k_transpose_pt, dim3((M + 31) / 32, g.Bpad / 32), dim3(256), 0, st, PT, M, g.Bpad, B, P, unpack_inv_scale);

@@ -23,6 +23,9 @@ constexpr int DW_WAVES = 8;               // waves per workgroup of the dW kerne
 constexpr int DW_TC = 32 * DW_WAVES;      // experts per workgroup of the dW kernel
 
 static inline int rup(int a, int b) { return (a + b - 1) / b * b; }
+// Hidden widths 96, 160, 192 and 224 run the kernels of the next fused width up (96 -> 128; the others -> 256), which take the real row width as a run-time
+// argument (their PAD forms): parameter rows stay exactly H floats, the h operands (hz, hs) and the dh slabs are padded to the template width with zero columns.
+__host__ __device__ constexpr int fused_tmpl(int H) { return H == 96 ? 128 : (H == 160 || H == 192 || H == 224) ? 256 : H; }
 // hipFuncAttributeMaxDynamicSharedMemorySize of a kernel that asks for more than 64 KiB of dynamic LDS: a property of (device, kernel) that never changes - set the first
 // time that kernel is launched with that size, not once per launch (round 4 paid the runtime call on every launch of every big kernel)
 inline void set_max_lds(const void* fn, int bytes) {
@@ -58,14 +61,15 @@ inline int eval_ncg(const Geom& g) { return std::max(1, std::min(2 * NCG_MAX / g
 struct WsLayout { size_t sbits, sbitsT, sinbits, sinT, hs, hz, lossp, hb, total; };
 inline WsLayout ws_layout(int Bmax, int H, int M) {
     const int Bpad = rup(Bmax, BM), nCB = rup((M + 31) / 32, 2);
+    const int Ht = fused_tmpl(H);   // row stride of hz / hs (the s_in words stay H / 32 a row)
     WsLayout w; size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) / 256 * 256; return r; };
     w.sbits = take((size_t)Bpad * nCB * 4);
     w.sbitsT = take((size_t)rup(M, DW_TC) * (Bpad / 32) * 4);   // [expert tile of 256][K block of 32 rows][256 experts]: word = s_out signs of the 32 rows
     w.sinbits = take((size_t)Bpad * (H / 32) * 4);
     w.sinT = take((size_t)(Bpad / 32) * H * 4);   // [K block][hidden unit]: s_in signs of the block's 32 rows (k_sin_words_T)
-    w.hs = take((size_t)Bpad * H * 4);
-    w.hz = take((size_t)Bpad * H * 4);
+    w.hs = take((size_t)Bpad * Ht * 4);
+    w.hz = take((size_t)Bpad * Ht * 4);
     w.lossp = take((size_t)Bpad * NCG_MAX * 4);
     w.hb = take((size_t)Bpad * H * 2 * 4);   // fp16 split planes (hi, lo) of h and h*s_in, K-block tiled (k_prep_planes_T)
     w.total = o;
@@ -135,6 +139,7 @@ struct OutFwdArgs {
     // inference (the PROBS forms of k_out_fwd / k_out_fwd_b6): dzT[c][i] (+)= sigmoid(leaky_relu(z)) * pscale; pacc: accumulate onto the previous MC passes;
     // plogit: store the logit leaky_relu(z) itself instead (ntf_logits: the quantity the 1e-4 parity bar is stated on)
     float pscale; int pacc, plogit;
+    int Hr;   // PAD forms: the real row width of mu / Wp / the s_in words (a multiple of 32 below the template's H); p.h / p.hs / the slabs have the template's stride
 };
 __device__ __forceinline__ bool range_guard_skip(int* rflag, int rmode, bool count) {
     if (rmode == 0) return false;

@@ -31,6 +31,7 @@ struct DwArgs {
     // contiguous part of the K blocks into part[(split * 2 + matrix) * slab ..] (bias sums behind the slabs); k_out_dw_finish adds the parts and runs the epilogue
     int ksplit; float* part; int64_t slab; int part_row0;   // part_row0: first expert of the launched tile range - the slabs hold that range only
     unsigned long long* stamps;   // diagnostics (k_out_dw_q<.., STAMP>, NTF_DW_STAMP_FILE)
+    int Hr;               // PAD forms of the exact-f32 kernels (fused_tmpl): floats per row of mu / rho / Wp, the gradients and the moments
     int ntile, stagger;   // k_out_dw_q, unsplit: expert tiles of this launch (walked by persistent workgroups), start delay of every second workgroup (100 MHz ticks)
     // produce != 0 (fused Adam, Flipout, fp16x3 planes): the epilogue holds the UPDATED mu' / rho' of its elements - it also is the next step's operand producer:
     // eps' (Philox keyed by step + 1), Wp' = softplus(rho') eps' (f32, in place over this step's Wp), the fp16 split planes of Wp' and mu' that the forward kernel
@@ -106,7 +107,10 @@ __device__ __forceinline__ void dw_produce_finish(const DwArgs& p, float kl, flo
 
 // HG > H: the layer's rows are HG wide and this workgroup owns the hidden units [jh H, (jh + 1) H) of its experts (H = 256 as two launches of H = 128's
 // shape per expert tile, k_out_dw_h2): the epilogue is element-wise per weight; the bias gradients belong to the jh = 0 workgroups.
-template <int H, bool BAYES, bool ADAM, int HG = H>
+// PAD: the layer's rows are p.Hr < HG floats wide (96 on H = 128's shape; 160, 192, 224 on the two-workgroup shape of 256): the h tiles keep HG columns, zero past
+// p.Hr; the epilogue addresses rows of p.Hr floats, and a lane whose NJT hidden units lie past p.Hr loads and stores nothing - no parameter, moment or gradient outside
+// its row is touched, and Flipout's KL / rho terms are taken over real elements only.
+template <int H, bool BAYES, bool ADAM, int HG = H, bool PAD = false>
 __device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem, int jh = 0) {  // ADAM: see DwArgs
     constexpr int NJT = H / 32;
     constexpr int KB = 32;                  // batch rows per K block
@@ -216,11 +220,13 @@ __device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem, int
     if (half == 0 && c < p.M && jh == 0) { p.g_b[c] = sum1; if (BAYES) p.g_bp[c] = sum2; }
 
     float nx_kl = 0.f, nx_amax = 0.f;
+    const int ldw = PAD ? p.Hr : HG;                                  // floats per parameter row
+    const bool lane_live = !PAD || jh * H + NJT * il < p.Hr;          // (p.Hr is a multiple of 32 >= NJT: a lane's units are all inside the row or all outside)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int cr = c0 + wave * 32 + rowmap(r, half);
-        if (cr >= p.M) continue;
-        const int64_t idx0 = (int64_t)cr * HG + jh * H + NJT * il;  // NJT consecutive hidden units per lane: one wide access per array
+        if (cr >= p.M || !lane_live) continue;
+        const int64_t idx0 = (int64_t)cr * ldw + jh * H + NJT * il;  // NJT consecutive hidden units per lane: one wide access per array
         float gm[NJT], gr[NJT], pm[NJT], pr[NJT];
 #pragma unroll
         for (int jt = 0; jt < NJT; ++jt) {
@@ -250,22 +256,22 @@ __device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem, int
                     p.m_rho[idx0 + jt] = m2; p.v_rho[idx0 + jt] = v2;
                 }
             }
-            if constexpr (H == 128 && HG == 128) { if (p.produce) { if constexpr (BAYES) dw_produce_next(p, idx0, nmu, nrho, nx_kl, nx_amax); else dw_produce_next_fnn(p, idx0, nmu, nx_amax); } }   // (this kernel as the fp16x3 step's range fallback)
+            if constexpr (H == 128 && HG == 128 && !PAD) { if (p.produce) { if constexpr (BAYES) dw_produce_next(p, idx0, nmu, nrho, nx_kl, nx_amax); else dw_produce_next_fnn(p, idx0, nmu, nx_amax); } }   // (this kernel as the fp16x3 step's range fallback)
         }
     }
-    if constexpr (ADAM && H == 128 && HG == 128) { if (p.produce) dw_produce_finish<BAYES>(p, nx_kl, nx_amax, reinterpret_cast<double*>(smem), DW_WAVES); }
+    if constexpr (ADAM && H == 128 && HG == 128 && !PAD) { if (p.produce) dw_produce_finish<BAYES>(p, nx_kl, nx_amax, reinterpret_cast<double*>(smem), DW_WAVES); }
 }
 
-template <int H, bool BAYES, bool ADAM>
+template <int H, bool BAYES, bool ADAM, bool PAD = false>
 __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw(DwArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    out_dw_f32_body<H, BAYES, ADAM>(p, smem);
+    out_dw_f32_body<H, BAYES, ADAM, H, PAD>(p, smem);
 }
 // H = 256: blockIdx.y = the hidden half of the expert tile blockIdx.x
-template <bool BAYES, bool ADAM>
+template <bool BAYES, bool ADAM, bool PAD = false>
 __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_h2(DwArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    out_dw_f32_body<128, BAYES, ADAM, 256>(p, smem, (int)blockIdx.y);
+    out_dw_f32_body<128, BAYES, ADAM, 256, PAD>(p, smem, (int)blockIdx.y);
 }
 // the same as the range FALLBACK behind a split-product kernel that cannot run the f32 body itself (k_out_dw_q, the split-K launches): it runs only in a step whose
 // range flag is raised - in every other step it is a no-op on the critical path, so it is launched on ONE round of workgroups that walk the tiles (p.ntile of
@@ -856,12 +862,28 @@ void launch_fused_out_dw(hipStream_t st, const FusedDw& f) {
     const bool guard = f.split && f.rflag != nullptr;
     a.sT = reinterpret_cast<const uint32_t*>(ws + w.sbitsT);
     a.ksplit = 1; a.part = nullptr; a.slab = 0; a.part_row0 = 0;
-    if (f.H == 256) {   // exact-f32 only (no split-product kernels at this width): each 256-expert tile as two hidden-half workgroups
+    const int Ht = fused_tmpl(f.H);
+    const bool pad = Ht != f.H;       // 96, 160, 192, 224: the PAD forms of the exact-f32 kernels, in every arithmetic mode (no split-product form at these widths)
+    a.Hr = f.H;
+    if (Ht == 256) {   // exact-f32 only (no split-product kernels at this width): each 256-expert tile as two hidden-half workgroups
         const size_t lds = 2 * ((size_t)DW_TC * 32 * 4 + (size_t)(f.bayes ? 2 : 1) * 32 * 4 * 128);
 #define NTF_DWH(BY, AD) do { auto kf = k_out_dw_h2<BY, AD>; set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);              \
         hipLaunchKernelGGL(kf, dim3(grid, 2), dim3(64 * DW_WAVES), lds, st, a); } while (0)
+#define NTF_DWHP(BY, AD) do { auto kf = k_out_dw_h2<BY, AD, true>; set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);       \
+        hipLaunchKernelGGL(kf, dim3(grid, 2), dim3(64 * DW_WAVES), lds, st, a); } while (0)
+        if (pad) { if (f.bayes) { if (f.adam) NTF_DWHP(true, true); else NTF_DWHP(true, false); } else { if (f.adam) NTF_DWHP(false, true); else NTF_DWHP(false, false); } }
+        else
         if (f.bayes) { if (f.adam) NTF_DWH(true, true); else NTF_DWH(true, false); } else { if (f.adam) NTF_DWH(false, true); else NTF_DWH(false, false); }
+#undef NTF_DWHP
 #undef NTF_DWH
+        return;
+    }
+    if (pad) {      // 96 on H = 128's exact-f32 kernel
+        const size_t lds = 2 * ((size_t)DW_TC * 32 * 4 + (size_t)(f.bayes ? 2 : 1) * 32 * 4 * 128);
+#define NTF_DWP(BY, AD) do { auto kf = k_out_dw<128, BY, AD, true>; set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);      \
+        hipLaunchKernelGGL(kf, dim3(grid), dim3(64 * DW_WAVES), lds, st, a); } while (0)
+        if (f.bayes) { if (f.adam) NTF_DWP(true, true); else NTF_DWP(true, false); } else { if (f.adam) NTF_DWP(false, true); else NTF_DWP(false, false); }
+#undef NTF_DWP
         return;
     }
     if (f.split && f.dz_packed) {   // fp16x3 step, H = 128: the forward kernel left packed plane pairs in dzT

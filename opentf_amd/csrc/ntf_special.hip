@@ -7,11 +7,14 @@ namespace ntf {
 // One wave per team.  H = 128: the wave works as FOUR quarter-waves of 16 lanes x 8 consecutive hidden units, each quarter taking every fourth
 // special entry (and every fourth dh slab): the ~8 dependent dot-product / reduction / BCE chains of a team run four abreast, rows are read as
 // 32-byte pieces (round 2: 55 -> ~20 us per step at B = 1000).  Other widths keep one entry at a time over the whole wave (NV values per lane).
+// H = 96, 160, 192, 224 (fused_tmpl): h * s_in and the dh slabs come with the template width HT as their row stride; only their first H columns are read, so whatever
+// the forward kernels summed into the padding columns never reaches dh.  Parameters, h, the mask, dh and the s_in words have H (H / 32) a row.
 template <int H, bool BAYES, bool TRAIN, bool DH>
 __global__ __launch_bounds__(64) void k_out_special(SpecialArgs p) {
     constexpr bool QUAD = (H == 128);
     constexpr int NQ = QUAD ? 4 : 1;                 // entries in flight
     constexpr int NV = QUAD ? 8 : (H + 63) / 64;     // hidden units per lane
+    constexpr int HT = fused_tmpl(H);                // row stride of p.hs and of the dh slabs
     const int i = blockIdx.x, lane = threadIdx.x;
     const int q = QUAD ? (lane >> 4) : 0, l = QUAD ? (lane & 15) : lane;
     auto hidx = [&](int k) { return QUAD ? 8 * l + k : l + 64 * k; };      // this lane's k-th hidden unit
@@ -26,11 +29,11 @@ __global__ __launch_bounds__(64) void k_out_special(SpecialArgs p) {
     for (int k = 0; k < NV; ++k) {
         const int j = hidx(k);
         acc[k] = 0.f; hr[k] = 0.f; hsr[k] = 0.f;
-        if (j < H) { hr[k] = p.h[(int64_t)i * H + j]; if (BAYES) hsr[k] = p.hs[(int64_t)i * H + j]; }
+        if (j < H) { hr[k] = p.h[(int64_t)i * H + j]; if (BAYES) hsr[k] = p.hs[(int64_t)i * HT + j]; }
     }
     if (TRAIN && DH) {
         for (int cg = q; cg < nslab; cg += NQ) {
-            const float* sl = p.slab + ((int64_t)cg * p.Bpad + i) * H;
+            const float* sl = p.slab + ((int64_t)cg * p.Bpad + i) * HT;
 #pragma unroll
             for (int k = 0; k < NV; ++k) { const int j = hidx(k); if (j < H) acc[k] += sl[j]; }
         }
@@ -121,7 +124,8 @@ void launch_out_special(hipStream_t st, int H, bool bayes, bool train, bool dh, 
         else if (dh) hipLaunchKernelGGL((k_out_special<HH, BY, true, true>), dim3(s.B), dim3(64), 0, st, s);                                  \
         else hipLaunchKernelGGL((k_out_special<HH, BY, true, false>), dim3(s.B), dim3(64), 0, st, s); } while (0)
 #define NTF_SPH(HH) do { if (bayes) NTF_SPK(HH, true); else NTF_SPK(HH, false); } while (0)
-    if (H == 256) NTF_SPH(256); else if (H == 128) NTF_SPH(128); else if (H == 64) NTF_SPH(64); else NTF_SPH(32);
+    if (H == 256) NTF_SPH(256); else if (H == 128) NTF_SPH(128); else if (H == 64) NTF_SPH(64); else if (H == 32) NTF_SPH(32);
+    else if (H == 96) NTF_SPH(96); else if (H == 160) NTF_SPH(160); else if (H == 192) NTF_SPH(192); else NTF_SPH(224);
 #undef NTF_SPH
 #undef NTF_SPK
 }

@@ -48,7 +48,11 @@ def expert_shards(M: int, world: int):
 
 
 def can_shard(dims, world: int) -> bool:
-    """the fused output-layer path (h[-1] in {32, 64, 128, 256}) and at least one 256-expert tile per rank"""
+    """a last hidden width whose fused output-layer kernels run on expert shards (h[-1] in {32, 64, 128, 256}) and at least one 256-expert tile per rank.
+
+    The set is narrower than the widths that have the fused kernels: 96, 160, 192 and 224 run them too (the kernels of 128 / 256 on rows narrower than their tile),
+    but on one GPU only - their shards (the two-phase step, the d(hidden) exchange, shard-local inference) are not covered by the expert-parallel tests, and the
+    engine refuses an expert shard at those widths.  Under torchrun such a model stays data-parallel, on the fused kernels."""
     return len(dims) >= 2 and dims[-2] in (32, 64, 128, 256) and -(-int(dims[-1]) // TILE) >= world
 
 
