@@ -219,6 +219,21 @@ int ntf_logits(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* 
 /* top-K per row of the probabilities, without moving [B, M] to the host   src/pkgmgr.py:125-134 */
 int ntf_forward_topk(ntf_engine* e, const int64_t* rows, int32_t B, int32_t nmc, int32_t K,
                      float* values_host, int32_t* indices_host, float* pred_unc, float* model_unc);
+/* Fused Monte-Carlo inference (NTF_INFER_MC=1 in the environment at engine creation; off by default).  Bnn.test averages nmc stochastic forwards
+ * (src/mdl/fnn.py:202-211); the default path runs them as nmc passes over the output layer, each reading and rewriting the running mean of every probability.
+ * With the switch on, Flipout models with h[-1] = 128 on the default (fp16x3) arithmetic run up to NTF_MC_MAX_GROUP passes inside one kernel launch, the running
+ * sums in registers (ntf_forward / ntf_forward_topk with nmc > 1 and no injected noise; everything else keeps the default path).  The probabilities, the top-K and
+ * pred_unc are bit-identical either way; model_unc differs by the rounding of one f32 sum taken in another order.  The per-pass operands (fp16 planes of
+ * sigma * eps, bias operand) of a launch live in a ring bounded by NTF_INFER_MC_BYTES (default 2 GiB); ntf_infer_mc_plan is the host function that sizes it:
+ * *passes_per_group in [1, min(passes, NTF_MC_MAX_GROUP)] passes per launch and *experts_per_range experts per launch (a positive multiple of 256; the last
+ * range of a layer may be shorter) such that passes_per_group * experts_per_range * (4 h + 4) + experts_per_range * 4 h <= budget_bytes - as many passes per
+ * launch as fit before longer ranges, since only a group holding all passes removes the read-modify-write entirely.  NTF_EINVAL when one pass over 256 experts
+ * does not fit or an argument is not positive.  Needs no engine and no GPU. */
+#define NTF_MC_MAX_GROUP 16
+#define NTF_MC_TILE_GROUP 4      /* 32-expert tiles whose running sums a workgroup holds in registers across the passes of a launch */
+int ntf_infer_mc_plan(int64_t experts, int32_t h, int32_t passes, int64_t budget_bytes, int32_t* passes_per_group, int64_t* experts_per_range);
+/* Monte-Carlo passes served by fused-MC launches whose call was not redone on the exact-f32 kernels behind a raised range flag (ntf_range_fallbacks) */
+int ntf_mc_fused_passes(ntf_engine* e, int64_t* passes);
 
 /* ---- the team2vec gather on its own:  Gnn.get_dense_vecs           src/mdl/emb/gnn.py:484-486
  * out_host [n, d] (may be NULL to keep the result on the device only); rows NULL = 0..n-1. */

@@ -126,6 +126,11 @@ struct ntf_engine {
     // (apply_adam leaves them out); g0_clean: the layer's gradient rows are all zero (the sweep clears what it reads: no memset in front of the scatter)
     int infer_f32 = 1;                // NTF_INFER_F32=0 (A/B runs, tests): inference without the split planes (h[-1] of 32, 64, 96, 160, 192, 224, 256; 128 with mfma = NTF_MFMA_F32; a raised range flag) on the
                                       // generic chain - k_gemm into dense [B, M] logits + launch_sigmoid_acc per MC pass - instead of the exact-f32 fused kernel k_out_probs
+    // NTF_INFER_MC=1 (opt-in): Bnn inference at h[-1] = 128 on fp16x3 runs its Monte-Carlo passes inside k_out_probs_mc (infer_mc_fused) - groups of passes over ranges
+    // of the experts, sized by ntf_infer_mc_plan under NTF_INFER_MC_BYTES.  Allocated on the first such call: mc_ring (a group's fp16 planes of sigma * eps, one slot
+    // of mc_range experts per pass), mc_bp (their bias operands), mc_hz (their zero-padded h images), mc_lossp (entropy partials, a column-group block per range)
+    int infer_mc = 0; int64_t infer_mc_bytes = (int64_t)2 << 30; int64_t mc_fused_passes = 0;
+    uint16_t* mc_ring = nullptr; float *mc_bp = nullptr, *mc_hz = nullptr, *mc_lossp = nullptr; int mc_slots = 0; int64_t mc_range = 0; int64_t mc_lossp_cap = 0;
     int eval_kernel = 1;              // NTF_EVAL_KERNEL=0 (A/B runs, tests): evaluation steps on k_out_fwd_b6 as in round 5 instead of k_out_fwd_h3e
     int mh_head = 1;                  // NTF_MH_HEAD=0 (A/B runs): a multi-hot step's head (first-layer operands, gather-sum, h images) inline in its own step as in rounds 1-5; 1 (round 6): as ONE
                                       // unit (head_launch's multi-hot form) that the previous step issues for the next staged batch beside its dW kernel, behind the first layer's sweep
@@ -262,6 +267,8 @@ extern "C" int ntf_engine_create(const ntf_config* cfg, ntf_engine** out) {
     if (const char* mh = getenv("NTF_MH_HEAD")) e->mh_head = atoi(mh);
     if (const char* ek = getenv("NTF_EVAL_KERNEL")) e->eval_kernel = atoi(ek);
     if (const char* nf = getenv("NTF_INFER_F32")) e->infer_f32 = atoi(nf);
+    if (const char* mc = getenv("NTF_INFER_MC")) e->infer_mc = atoi(mc);
+    if (const char* mb = getenv("NTF_INFER_MC_BYTES")) e->infer_mc_bytes = atoll(mb);
     if (const char* fc = getenv("NTF_F32_COPY_MERGED")) e->f32_copy_merged = atoi(fc);
     if (const char* eh = getenv("NTF_EP_HEAD_PREFETCH")) e->ep_head_prefetch = atoi(eh);
     if (const char* dr = getenv("NTF_DP_RANGES")) e->dp_ranges = atoi(dr);
@@ -354,6 +361,7 @@ extern "C" void ntf_engine_destroy(ntf_engine* e) {
     for (auto& p : e->Wp) dfree(p);
     for (auto& p : e->bp) dfree(p);
     dfree(e->l0_touched);
+    dfree(e->mc_ring); dfree(e->mc_bp); dfree(e->mc_hz); dfree(e->mc_lossp);
     dfree(e->partial); dfree(e->row_fix); dfree(e->d_loss); dfree(e->d_kl); dfree(e->d_chain); dfree(e->d_acc); dfree(e->d_acc_steps);
     dfree(e->ent_mc); dfree(e->ent_mean); dfree(e->dh_slab); dfree(e->fws_set[0]); dfree(e->fws_set[1]); dfree(e->pl_mu); dfree(e->pl_wp); dfree(e->gemm_slab); dfree(e->tk_vals); dfree(e->tk_idx);
     for (auto* v : {&e->inj_eps_w, &e->inj_eps_b, &e->inj_s_in, &e->inj_s_out}) for (auto& p : *v) dfree(p);
@@ -536,6 +544,11 @@ extern "C" int ntf_skip_step(ntf_engine* e) { if (!e) return NTF_EINVAL; e->step
 extern "C" int ntf_prefetched_steps(ntf_engine* e, int64_t* steps) { if (!e || !steps) return NTF_EINVAL; *steps = e->pre_used; return NTF_OK; }
 extern "C" int ntf_head_prefetch_hits(ntf_engine* e, int64_t* steps) { if (!e || !steps) return NTF_EINVAL; *steps = e->hp_used; return NTF_OK; }
 extern "C" int ntf_first_layer_sweeps(ntf_engine* e, int64_t* steps) { if (!e || !steps) return NTF_EINVAL; *steps = e->pre0_used; return NTF_OK; }
+extern "C" int ntf_mc_fused_passes(ntf_engine* e, int64_t* passes) {
+    if (!e || !passes) return NTF_EINVAL;
+    *passes = e->mc_fused_passes;
+    return NTF_OK;
+}
 extern "C" int ntf_range_fallbacks(ntf_engine* e, int64_t* steps) {
     if (!e || !steps) return NTF_EINVAL;
     HIPCHK(e, hipSetDevice(e->cfg.device));
@@ -1836,6 +1849,92 @@ static int range_raised(ntf_engine* e, bool& raised) {
     return NTF_OK;
 }
 
+// Ring plan of the fused-MC inference arm (include/opentf_amd.h): per expert, a pass takes the two fp16 planes of sigma * eps (4 h bytes) and its bias operand (4),
+// a range the two planes of mu (4 h) once.  As many passes per launch as fit over ONE 256-expert range first - only a group of all passes never re-reads the running
+// sums - then the longest range (a multiple of 256, the tile of the dzT layout) that keeps that group inside the budget.
+static_assert(NTF_MC_MAX_GROUP == kMcMaxGroup && NTF_MC_TILE_GROUP == MC_G, "include/opentf_amd.h and ntf_fused.h disagree");
+extern "C" int ntf_infer_mc_plan(int64_t experts, int32_t h, int32_t passes, int64_t budget_bytes, int32_t* passes_per_group, int64_t* experts_per_range) {
+    if (experts <= 0 || h <= 0 || passes <= 0 || budget_bytes <= 0 || !passes_per_group || !experts_per_range) return NTF_EINVAL;
+    const int64_t per_pass = 4 * (int64_t)h + 4, mu = 4 * (int64_t)h;      // bytes per expert
+    const int64_t per256 = budget_bytes / 256;                              // bytes per expert the budget allows over one 256-expert range
+    if (per256 < per_pass + mu) return NTF_EINVAL;
+    const int64_t g = std::min<int64_t>(std::min<int64_t>(passes, NTF_MC_MAX_GROUP), (per256 - mu) / per_pass);
+    const int64_t fit = budget_bytes / (g * per_pass + mu) / 256 * 256, all = (experts + 255) / 256 * 256;
+    *passes_per_group = (int32_t)g;
+    *experts_per_range = std::min(fit, all);
+    return NTF_OK;
+}
+
+// The MC passes of one inference call inside k_out_probs_mc.  Per group of passes: the hidden layers of every pass (the step numbers step0 + p of the per-pass path)
+// into per-pass h images; per range of the experts the producer once per pass into that pass's ring slot (counter base shifted by the range: what the whole layer
+// would draw; the planes of mu into the engine's whole-layer image, once per call as on the per-pass path); one launch per (group, range).  The sums of a later group
+// continue the earlier ones through the transposed buffer (pacc).  Once per call: the entropy partials, the transpose.  The caller reads the range flag behind it all.
+static int infer_mc_fused(ntf_engine* e, const int64_t* rows, int32_t B, int passes, bool want_unc) {
+    int r;
+    if ((r = check_ready(e, false))) return r;
+    const int M = e->cfg.dims[e->L];
+    const LayerInfo& lo = e->layers[e->L - 1];
+    const int H = lo.in;
+    int32_t ppg = 0; int64_t range = 0;
+    if (ntf_infer_mc_plan(M, H, passes, e->infer_mc_bytes, &ppg, &range)) FAIL(e, NTF_EINVAL, "NTF_INFER_MC_BYTES holds not even one pass over 256 experts (ntf_infer_mc_plan)");
+    const int nranges = (int)((M + range - 1) / range);
+    const int64_t Bpad_max = fused_ldb(e->cfg.max_batch);
+    int ncg_tot = 0;
+    for (int k = 0; k < nranges; ++k) ncg_tot += fused_mc_ncg(B, (int)(std::min<int64_t>(M, (k + 1) * range) - k * range));
+    if (e->mc_slots < ppg || e->mc_range < range) {      // (exactly the plan's ring: never more than the budget)
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        dfree(e->mc_ring); dfree(e->mc_bp); dfree(e->mc_hz); e->mc_slots = 0; e->mc_range = 0;
+        DM(e, &e->mc_ring, (int64_t)ppg * range * H * 2); DM(e, &e->mc_bp, (int64_t)ppg * range); DM(e, &e->mc_hz, (int64_t)ppg * Bpad_max * H);
+        HIPCHK(e, hipMemsetAsync(e->mc_ring, 0, (size_t)ppg * range * H * 2 * 2, e->st));      // rows behind the layer's last expert stay zero planes
+        e->mc_slots = ppg; e->mc_range = range;
+    }
+    if (e->mc_lossp_cap < Bpad_max * ncg_tot) {
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        dfree(e->mc_lossp); e->mc_lossp_cap = 0;
+        DM(e, &e->mc_lossp, Bpad_max * ncg_tot); e->mc_lossp_cap = Bpad_max * ncg_tot;
+    }
+    const int64_t slot_pl = e->mc_range * H * 2;      // uint16 elements of a ring slot
+    StepCtx c0; c0.B = B; c0.global_B = B; c0.inj = nullptr; c0.train = false; c0.step = e->step;
+    if ((r = stage_rows(e, rows, B, false, &c0.rows_dev))) return r;
+    int32_t* const rflag = range_ptr(e);
+    e->pre_valid = false;   // the passes' operands overwrite any prefetched ones (as infer_pass_fused)
+    if ((r = make_input(e, c0))) return r;
+    for (int p0 = 0; p0 < passes; p0 += ppg) {
+        const int np = std::min<int>(ppg, passes - p0);
+        FusedProbsMc f;
+        f.B = B; f.M = M; f.npass = np; f.mu_b = e->P + lo.off[NTF_P_BIAS]; f.dzT = e->dZout; f.lossp = e->mc_lossp; f.ncg_tot = ncg_tot;
+        f.pscale = 1.0f / (float)passes; f.pacc = p0 > 0; f.w_scale = kW16Scale; f.h_scale = kH16Scale; f.rflag = rflag;
+        StepCtx cs[NTF_MC_MAX_GROUP];
+        for (int k = 0; k < np; ++k) {
+            StepCtx& c = cs[k]; c = c0; c.step = e->step++;
+            if ((r = forward_layers(e, c, true, true))) return r;   // hidden layers only
+            float* hz = e->mc_hz + (int64_t)k * Bpad_max * H;
+            { Scope t(e, F_OUT_FUSED_AUX); launch_fused_prep_hz(e->st, e->act[e->L - 1], B, H, hz, kH16Scale, rflag); }
+            f.pass[k].hz = hz; f.pass[k].wp_pl = e->mc_ring + k * slot_pl; f.pass[k].bp = e->mc_bp + k * e->mc_range;
+            f.pass[k].s_in = sign_spec(e, c, e->L - 1, T_S_IN, lo.in); f.pass[k].s_out = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out);
+        }
+        for (int k = 0; k < nranges; ++k) {
+            const int64_t c_lo = k * range, c_hi = std::min<int64_t>(M, c_lo + range);
+            const int64_t pl0 = c_lo / 32 * 64 * H;      // the planes of 32-expert tile c_lo / 32 (fused_planes_elems layout)
+            { Scope t(e, F_FLIPOUT_OPERAND);
+              for (int q = 0; q < np; ++q) {
+                  NormalSpec ew = normal_spec(e, cs[q], e->L - 1, T_EPS_W), eb = normal_spec(e, cs[q], e->L - 1, T_EPS_B);
+                  ew.qbase += c_lo * H / 4; eb.qbase += c_lo / 4;
+                  launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT] + c_lo * H, nullptr, (c_hi - c_lo) * H, ew, nullptr, 0.0, e->d_kl,
+                                         e->mc_ring + q * slot_pl, p0 == 0 && q == 0 ? e->pl_mu + pl0 : nullptr, e->P + lo.off[NTF_P_WEIGHT] + c_lo * H, H, kW16Scale, rflag);
+                  launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS] + c_lo, nullptr, c_hi - c_lo, eb, e->mc_bp + q * e->mc_range, 0.0, e->d_kl);
+              } }
+            f.c_lo = (int)c_lo; f.c_hi = (int)c_hi; f.mu_pl = e->pl_mu + pl0;
+            { Scope t(e, F_OUT_FUSED_FWD); launch_fused_probs_mc(e->st, f); }
+            f.cg_off += fused_mc_ncg(B, (int)(c_hi - c_lo));
+        }
+    }
+    Scope t(e, F_INFER);
+    if (want_unc) launch_fused_ent_slots(e->st, e->mc_lossp, B, ncg_tot, 1.0f / (float)passes, e->ent_mc);
+    launch_fused_probs_finish(e->st, B, H, M, e->fws, e->dZout, e->Pbuf, nullptr, 1.f, true);
+    return NTF_OK;
+}
+
 static int infer_probs(ntf_engine* e, const int64_t* rows, int32_t B, int32_t nmc, const ntf_inject* inj_per_mc, bool want_unc) {
     const int M = e->cfg.dims[e->L];
     if (!e->Pbuf) DM(e, &e->Pbuf, (int64_t)e->cfg.max_batch * M);
@@ -1844,14 +1943,19 @@ static int infer_probs(ntf_engine* e, const int64_t* rows, int32_t B, int32_t nm
     if (infer_fused(e)) {     // fused forward kernel: no dense logits, MC mean accumulated on the fly
         const uint64_t step0 = e->step;
         bool split = infer_split(e);      // the split-product kernel (H = 128); without planes, and behind a raised range flag, the exact-f32 one
+        // NTF_INFER_MC=1: the passes of a Flipout call inside k_out_probs_mc (injected noise, one pass, Fnn and every other width / arithmetic: the per-pass loop)
+        bool mc = e->infer_mc && split && e->cfg.bayesian && passes > 1 && !inj_per_mc && e->pl_wp && range_ptr(e);
         for (int arm = 0; arm < 2; ++arm) {
             if (split && range_ptr(e)) HIPCHK(e, hipMemsetAsync(e->d_range, 0, 4, e->st));
-            for (int p = 0; p < passes; ++p) { int r = infer_pass_fused(e, rows, B, inj_per_mc ? &inj_per_mc[p] : nullptr, p, passes, want_unc, false, split); if (r) return r; }
+            if (mc) { int r = infer_mc_fused(e, rows, B, passes, want_unc); if (r) return r; }
+            else for (int p = 0; p < passes; ++p) { int r = infer_pass_fused(e, rows, B, inj_per_mc ? &inj_per_mc[p] : nullptr, p, passes, want_unc, false, split); if (r) return r; }
             bool raised = false; if (split) { int r = range_raised(e, raised); if (r) return r; }
             if (!raised) {
+                if (mc) e->mc_fused_passes += passes;
                 if (want_unc) { Scope t(e, F_INFER); launch_row_entropy(e->st, e->Pbuf, B, M, e->ent_mean); }
                 return NTF_OK;
             }
+            mc = false;
             e->step = step0;   // an operand left the fp16 window: the same passes (same generator keys) again on the exact-f32 kernel (NTF_INFER_F32=0: the generic chain below)
             split = false;
             if (want_unc) HIPCHK(e, hipMemsetAsync(e->ent_mc, 0, (size_t)B * 4, e->st));

@@ -96,4 +96,27 @@ void launch_fused_out_dw(hipStream_t st, const FusedDw& f);
 void launch_fused_probs_finish(hipStream_t st, int B, int H, int M, void* ws, const float* PT, float* P, float* ent_rows, float scale, bool transpose,
                                float unpack_inv_scale = 0.f);
 
+
+// Fused-MC inference (NTF_INFER_MC=1; Flipout, H = 128, fp16x3): k_out_probs_mc runs up to kMcMaxGroup Monte-Carlo passes over a range of the experts in ONE
+// launch, the running sums of MC_G 32-expert tiles in registers across the passes - the transposed buffer is written once per launch instead of read and
+// written once per pass.
+constexpr int kMcMaxGroup = 16;   // = NTF_MC_MAX_GROUP (include/opentf_amd.h)
+constexpr int MC_G = 4;           // tiles per tile group = NTF_MC_TILE_GROUP: 64 registers of running sums a lane (k_out_probs_mc: 365 registers, no spill; 8 tiles spill 70)
+struct FusedMcPass { const float* hz = nullptr; const uint16_t* wp_pl = nullptr; const float* bp = nullptr; SignSpec s_in, s_out; };   // hz: launch_fused_prep_hz image; wp_pl / bp: this pass's sigma * eps planes / bias operand of the range
+struct FusedProbsMc {
+    int B = 0, M = 0;                 // M: the (shard's) whole output layer - dzT, mu_b and the s_out hash keep its numbering
+    int c_lo = 0, c_hi = 0;           // the launch's experts [c_lo, c_hi), c_lo a multiple of 256, c_hi <= M; mu_pl and the passes' wp_pl / bp start at c_lo
+    int npass = 0; FusedMcPass pass[kMcMaxGroup];
+    const float* mu_b = nullptr; const uint16_t* mu_pl = nullptr;
+    float* dzT = nullptr;
+    float* lossp = nullptr; int cg_off = 0, ncg_tot = 0;   // entropy partials [rup(B, 128)][ncg_tot]: this launch's column groups are cg_off .. cg_off + fused_mc_ncg(B, c_hi - c_lo) - 1
+    float pscale = 1.f; int pacc = 0;                      // pacc: an earlier launch (earlier passes) left sums in dzT and partials in lossp - continue both
+    float w_scale = 1.f, h_scale = 1.f;
+    int* rflag = nullptr;
+};
+int fused_mc_ncg(int B, int experts);
+void launch_fused_prep_hz(hipStream_t st, const float* h, int B, int H, float* hz, float h_scale, int* rflag);   // hz [rup(B, 128), H] = h, zero rows behind B; range-checked like k_prep_h
+void launch_fused_probs_mc(hipStream_t st, const FusedProbsMc& f);
+void launch_fused_ent_slots(hipStream_t st, const float* lossp, int B, int ncg_tot, float scale, float* ent_rows);   // ent_rows[i] += scale * sum of row i's ncg_tot partials
+
 }  // namespace ntf

@@ -1650,4 +1650,15 @@ void launch_fused_probs_finish(hipStream_t st, int B, int H, int M, void* ws_, c
     if (transpose) hipLaunchKernelGGL(k_transpose_pt, dim3((M + 31) / 32, g.Bpad / 32), dim3(256), 0, st, PT, M, g.Bpad, B, P, unpack_inv_scale);
 }
 
+// ---- the fused-MC inference arm (k_out_probs_mc, ntf_fused_mc.hip): its column groups, h images and entropy slots
+int fused_mc_ncg(int B, int experts) { return geom(B, experts).NCG; }      // one workgroup per CU
+void launch_fused_prep_hz(hipStream_t st, const float* h, int B, int H, float* hz, float h_scale, int* rflag) {
+    const int Bpad = rup(B, BM), n = Bpad * (H / 32);
+    hipLaunchKernelGGL(k_prep_h, dim3((n + 63) / 64), dim3(64), 0, st, SignSpec(), 0, h, B, H, H, Bpad, (uint32_t*)nullptr, (float*)nullptr, hz,
+                       rflag ? 65504.f / h_scale : 0.f, rflag);
+}
+void launch_fused_ent_slots(hipStream_t st, const float* lossp, int B, int ncg_tot, float scale, float* ent_rows) {
+    hipLaunchKernelGGL(k_ent_slots, dim3((B + 255) / 256), dim3(256), 0, st, lossp, B, ncg_tot, scale, ent_rows);
+}
+
 }  // namespace ntf

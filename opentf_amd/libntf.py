@@ -14,6 +14,9 @@ import numpy as np
 
 NTF_ABI_VERSION = 1
 NTF_MAX_LAYERS = 8
+NTF_MC_MAX_GROUP = 16     # Monte-Carlo passes per fused-MC launch at most (include/opentf_amd.h)
+NTF_MC_TILE_GROUP = 4     # 32-expert tiles a workgroup of that kernel carries across the passes
+NTF_EINVAL = -1
 INPUT_DENSE, INPUT_MEANPOOL, INPUT_MULTIHOT = 0, 1, 2
 NSD = {None: 0, "": 0, "None": 0, "uniform": 1, "unigram": 2, "unigram_b": 3}
 P_WEIGHT, P_BIAS, P_RHO_WEIGHT, P_RHO_BIAS = 0, 1, 2, 3
@@ -87,6 +90,8 @@ SYMBOLS = {
     "ntf_forward": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
     "ntf_logits": (C.c_int, [_P, _P, _I32, _P, _P]),
     "ntf_forward_topk": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "ntf_infer_mc_plan": (C.c_int, [_I64, _I32, _I32, _I64, C.POINTER(_I32), C.POINTER(_I64)]),
+    "ntf_mc_fused_passes": (C.c_int, [_P, C.POINTER(_I64)]),
     "ntf_gather_meanpool": (C.c_int, [_P, _P, _I64, _P]),
     "ntf_grad_buffer": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I64)]),
     "ntf_moment_buffers": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_I64)]),
@@ -143,6 +148,18 @@ def _ptr(a):
 
 def _f32(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+
+
+def infer_mc_plan(experts, h, passes, budget_bytes):
+    """ntf_infer_mc_plan: (passes per fused-MC launch, experts per launch) under a ring budget in bytes, or None when not even one pass over 256 experts fits
+    (or an argument is not positive).  Needs no GPU."""
+    g, r = C.c_int32(), C.c_int64()
+    rc = lib().ntf_infer_mc_plan(int(experts), int(h), int(passes), int(budget_bytes), C.byref(g), C.byref(r))
+    if rc == NTF_EINVAL:
+        return None
+    if rc != 0:
+        raise NtfError(f"ntf_infer_mc_plan failed ({rc})")
+    return g.value, r.value
 
 
 class DeviceView:
@@ -306,6 +323,12 @@ class Engine:
         """steps / inference calls that ran on the exact-f32 kernels because an operand left the fp16x3 window"""
         n = C.c_int64()
         self._ck(lib().ntf_range_fallbacks(self._h, C.byref(n)))
+        return n.value
+
+    def mc_fused_passes(self):
+        """Monte-Carlo passes served by fused-MC launches (NTF_INFER_MC=1) whose call was not redone behind a raised range flag"""
+        n = C.c_int64()
+        self._ck(lib().ntf_mc_fused_passes(self._h, C.byref(n)))
         return n.value
 
     def prefetched_steps(self):
