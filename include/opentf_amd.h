@@ -276,6 +276,26 @@ int ntf_skill_coverage(int device, const int32_t* topk_idx, int64_t n, int32_t K
                        int64_t n_skill_rows, const int64_t* rows, const int64_t* cov_indptr, const int32_t* cov_indices, int64_t n_experts,
                        const int32_t* cutoffs, int32_t n_cut, float* out_cov);
 
+/* ---- micro-averaged ROC AUC of the eval stage on the device                                                      src/evl/metric.py:36-41
+ * `roc_auc_score(Y.toarray(), Y_.toarray(), average='micro')` as the Mann-Whitney statistic with mid-ranks over all n * M (score, label)
+ * pairs, in integers: out_counts = { P, N, U2 } with P = positives, N = n * M - P, U2 = sum over positives of (2 * #negatives scored lower
+ * + #negatives scored equal); *out_auc = (double)U2 / (2.0 * (double)P * (double)N).  Scores are f32 compared as real numbers: -0.0 ties
+ * with +0.0, denormals are distinct values, +-inf are ordinary values.  The truth row of instance i is rows[i] (NULL: i) of the CSR.
+ * ntf_auc_micro_dense: scores host, row-major [n, M], ld >= M floats per row (the padding is never read).  ntf_auc_micro_csr: scores as
+ * CSR (int64 indptr [n+1], int32 indices, f32 values); an entry that is not stored scores 0.0, stored values may be 0.0 or negative.
+ * chunk_bytes: device staging budget for score data per upload - the scores are streamed in chunks of whole rows (dense, M * 4 bytes each)
+ * or of stored entries (CSR: their f32 values, 4 bytes each; the column ids stay on the host) of at most that size; 0 = NTF_AUC_CHUNK_BYTES.
+ * A budget below one row / one entry is refused.
+ * NTF_EINVAL (out_counts / out_auc untouched): a null pointer or non-positive size, ld < M, a rows value outside [0, n_truth_rows), a
+ * truth or score column outside [0, M), indices not strictly increasing inside a row, a NaN score, P == 0 or N == 0, or 2 * P * N >= 2^64. */
+#define NTF_AUC_CHUNK_BYTES ((int64_t)256 << 20)
+int ntf_auc_micro_dense(int device, const float* scores, int64_t n, int64_t M, int64_t ld,
+                        const int64_t* truth_indptr, const int32_t* truth_indices, int64_t n_truth_rows, const int64_t* rows,
+                        int64_t chunk_bytes, uint64_t out_counts[3], double* out_auc);
+int ntf_auc_micro_csr(int device, const int64_t* s_indptr, const int32_t* s_indices, const float* s_values, int64_t n, int64_t M,
+                      const int64_t* truth_indptr, const int32_t* truth_indices, int64_t n_truth_rows, const int64_t* rows,
+                      int64_t chunk_bytes, uint64_t out_counts[3], double* out_auc);
+
 /* ---- member-skill co-occurrence on the device                                                 src/cmn/team.py:302-337
  * `Team.gen_skill_coverage`: C = member^T . skill over the teams NOT listed in skip_rows (the reference empties the test teams' rows,
  * team.py:327-331), as scipy computes it on the two uint8 matrices: counts wrap mod 256, entries whose wrapped count is 0 are not stored.

@@ -1,0 +1,300 @@
+// Micro-averaged ROC AUC of the reference's eval stage on the device (reference src/evl/metric.py:36-41: sklearn's
+// roc_auc_score(Y.toarray(), Y_.toarray(), average='micro')) as an exact integer statistic: the Mann-Whitney U with mid-ranks over all
+// n * M (score, label) pairs, U2 = sum over positives of (2 #negatives scored lower + #negatives scored equal), AUC = U2 / (2 P N).
+//
+// The positives are few (nnz of the truth rows), the scores are many (n * M).  The host gathers the positives' scores, maps them to
+// monotone u32 keys and reduces them to G sorted distinct keys v[0, G).  They cut the key axis into 2 G + 1 buckets: bucket 2 g holds the
+// keys strictly between v[g - 1] and v[g], bucket 2 g + 1 the keys equal to v[g].  The device streams every score once and counts it
+// into its bucket (k_auc_count: the only pass over the n * M scores); the host finishes in integers from the 2 G + 1 counts.  Integer
+// adds commute, so the result does not depend on how the counting is scheduled.
+#include "../../include/opentf_amd.h"
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+namespace ntf {
+
+constexpr int AUC_THREADS = 256;
+constexpr int AUC_MAX_BLOCKS = 2048;      // 256 CUs x 8; the rest of a chunk is walked grid-stride
+constexpr int AUC_PIVOTS = 2048;          // sampled keys held in LDS: the top 11 levels of the search never leave the CU
+constexpr int AUC_LDS_BUCKETS = 4096;     // up to this many buckets a workgroup counts in LDS and adds to the global counters once
+
+// f32 bits -> u32 key whose unsigned order is the order of the values as real numbers: -0.0 becomes +0.0, negatives have all bits flipped,
+// non-negatives get the top bit.  Built from the bits alone: denormals stay distinct (an f32 add could flush them).  NaN: *nan is raised.
+__host__ __device__ __forceinline__ uint32_t auc_key(uint32_t u, uint32_t& nan) {
+    nan |= (uint32_t)((u & 0x7fffffffu) > 0x7f800000u);
+    u = (u << 1) ? u : 0u;
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+
+// A thread's two pending (bucket, count) pairs.  `run` is the bucket of the elements just seen; `hot` is a bucket that repeated before and is
+// kept for the thread's whole walk, so that a value most of the matrix holds (the exact zeros of a saturated or top-K-like prediction) costs
+// one add per thread, not one per run.  A run that ends with a count of 1 (distinct real values) never displaces `hot`.
+struct AucPending { uint32_t hot_b, hot_n, run_b, run_n; };
+
+template <bool LDS_HIST>
+__device__ __forceinline__ void auc_flush(uint32_t b, uint32_t c, uint32_t* hist, unsigned long long* cnt) {
+    if (!c) return;
+    if (LDS_HIST) atomicAdd(&hist[b], c); else atomicAdd(&cnt[b], (unsigned long long)c);
+}
+
+template <bool LDS_HIST>
+__device__ __forceinline__ void auc_add(AucPending& p, uint32_t b, uint32_t* hist, unsigned long long* cnt) {
+    if (b == p.hot_b) { ++p.hot_n; return; }
+    if (b == p.run_b) { ++p.run_n; return; }
+    if (p.run_n > 1) {                   // the run repeated: it becomes the kept bucket, the old one is added
+        auc_flush<LDS_HIST>(p.hot_b, p.hot_n, hist, cnt);
+        p.hot_b = p.run_b; p.hot_n = p.run_n;
+    } else {
+        auc_flush<LDS_HIST>(p.run_b, p.run_n, hist, cnt);
+    }
+    p.run_b = b; p.run_n = 1;
+}
+
+// bucket of key k: g = #{ v[j] < k } by a branchless lower bound - first over the pivots in LDS (piv[i] = v[(i + 1) * stride - 1], S of them,
+// step0 = the largest power of two <= S or 0), then `stride / 2 .. 1` over v itself (global, L2-resident; none when stride == 1)
+__device__ __forceinline__ uint32_t auc_bucket(uint32_t k, const uint32_t* piv, uint32_t S, uint32_t step0, const uint32_t* __restrict__ v, uint32_t G,
+                                               uint32_t stride) {
+    uint32_t c = 0;
+    for (uint32_t s = step0; s; s >>= 1) { const uint32_t t = c + s; c = (t <= S && piv[min(t, S) - 1] < k) ? t : c; }
+    uint32_t g = c * stride;
+    for (uint32_t s = stride >> 1; s; s >>= 1) { const uint32_t t = g + s; g = (t <= G && v[min(t, G) - 1] < k) ? t : g; }
+    const uint32_t at = min(g, G - 1), vg = stride == 1 ? piv[at] : v[at];   // (stride == 1: the pivots are v itself)
+    const uint32_t eq = (g < G && vg == k) ? 1u : 0u;
+    return 2u * g + eq;
+}
+
+// x [L] f32 bits, 16-byte aligned.  cnt [2 G + 1] u64 bucket counters, *nan_flag: set when a NaN was seen.
+template <bool LDS_HIST>
+__global__ __launch_bounds__(AUC_THREADS) void k_auc_count(const uint32_t* __restrict__ x, int64_t L, const uint32_t* __restrict__ v, uint32_t G,
+                                                           const uint32_t* __restrict__ pivots, uint32_t S, uint32_t step0, uint32_t stride,
+                                                           unsigned long long* __restrict__ cnt, uint32_t* __restrict__ nan_flag) {
+    __shared__ uint32_t piv[AUC_PIVOTS];
+    __shared__ uint32_t hist[LDS_HIST ? AUC_LDS_BUCKETS : 1];
+    const uint32_t nb = 2u * G + 1u;
+    for (uint32_t i = threadIdx.x; i < S; i += AUC_THREADS) piv[i] = pivots[i];
+    if (LDS_HIST) for (uint32_t i = threadIdx.x; i < nb; i += AUC_THREADS) hist[i] = 0u;
+    __syncthreads();
+
+    AucPending p = {0xffffffffu, 0u, 0xffffffffu, 0u};
+    uint32_t nan = 0u;
+    const int64_t nvec = L >> 2, nthreads = (int64_t)gridDim.x * AUC_THREADS;
+    const uint4* __restrict__ x4 = reinterpret_cast<const uint4*>(x);
+    // two 16-byte loads in flight per thread and round
+    for (int64_t i = (int64_t)blockIdx.x * AUC_THREADS + threadIdx.x; i < nvec; i += 2 * nthreads) {
+        const int64_t j = i + nthreads;
+        const uint4 a = x4[i];
+        const bool two = j < nvec;
+        const uint4 b = two ? x4[j] : make_uint4(0u, 0u, 0u, 0u);
+        const uint32_t e[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            if (q < 4 || two) auc_add<LDS_HIST>(p, auc_bucket(auc_key(e[q], nan), piv, S, step0, v, G, stride), hist, cnt);
+        }
+    }
+    // the 0..3 scores behind the last whole vector
+    if (blockIdx.x == 0 && threadIdx.x < (uint32_t)(L & 3))
+        auc_add<LDS_HIST>(p, auc_bucket(auc_key(x[(nvec << 2) + threadIdx.x], nan), piv, S, step0, v, G, stride), hist, cnt);
+    auc_flush<LDS_HIST>(p.hot_b, p.hot_n, hist, cnt);
+    auc_flush<LDS_HIST>(p.run_b, p.run_n, hist, cnt);
+    if (nan) atomicOr(nan_flag, 1u);
+    if (LDS_HIST) {
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < nb; i += AUC_THREADS) if (hist[i]) atomicAdd(&cnt[i], (unsigned long long)hist[i]);
+    }
+}
+
+}  // namespace ntf
+
+using namespace ntf;
+
+namespace {
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) hipFree(p); }
+    bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess; }
+    bool put(const void* host, size_t bytes) { return alloc(bytes) && (!bytes || hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) == hipSuccess); }
+};
+
+double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// the truth side of both entries: validates it and lists the positives as (instance, column)
+struct Truth {
+    std::vector<int64_t> inst;
+    std::vector<int32_t> col;
+};
+bool read_truth(int64_t n, int64_t M, const int64_t* t_indptr, const int32_t* t_indices, int64_t n_truth_rows, const int64_t* rows, Truth& t) {
+    if (!t_indptr || n_truth_rows < 1 || (!rows && n > n_truth_rows)) return false;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t r = rows ? rows[i] : i;
+        if (r < 0 || r >= n_truth_rows) return false;
+        const int64_t b = t_indptr[r], e = t_indptr[r + 1];
+        if (b < 0 || e < b || (e > b && !t_indices)) return false;
+        for (int64_t j = b; j < e; ++j) {
+            const int32_t c = t_indices[j];
+            if (c < 0 || c >= M || (j > b && c <= t_indices[j - 1])) return false;
+            t.inst.push_back(i); t.col.push_back(c);
+        }
+    }
+    return true;
+}
+
+// Everything behind the positives' scores: the key table, the stream over `n_chunks` uploads, the integer finish.
+// next_chunk(k, dev, &count) uploads chunk k into `dev` and reports its number of scores.  implicit_zeros: scores of 0.0 that are not in any chunk.
+template <class Upload>
+int auc_run(int device, const std::vector<uint32_t>& pos_keys, unsigned __int128 total, uint64_t implicit_zeros, size_t stage_bytes, int64_t n_chunks,
+            Upload next_chunk, uint64_t out_counts[3], double* out_auc) {
+    const uint64_t P = pos_keys.size();
+    if (P == 0 || (unsigned __int128)P >= total) return NTF_EINVAL;                       // one class only
+    const unsigned __int128 N128 = total - P;
+    if (N128 >> 64 || ((unsigned __int128)2 * P * N128) >> 64) return NTF_EINVAL;
+    const uint64_t N = (uint64_t)N128;
+
+    std::vector<uint32_t> v(pos_keys);
+    std::sort(v.begin(), v.end());
+    std::vector<uint64_t> pos_eq;
+    size_t G = 0;
+    for (size_t i = 0; i < v.size(); ++i) {
+        if (G && v[G - 1] == v[i]) { ++pos_eq[G - 1]; continue; }
+        v[G++] = v[i]; pos_eq.push_back(1);
+    }
+    v.resize(G);
+    uint32_t stride = 1;
+    while (G / stride > (size_t)AUC_PIVOTS) stride <<= 1;
+    const uint32_t S = (uint32_t)(G / stride);
+    std::vector<uint32_t> piv(S);
+    for (uint32_t i = 0; i < S; ++i) piv[i] = v[(size_t)(i + 1) * stride - 1];
+    uint32_t step0 = 0;
+    if (S) for (step0 = 1; step0 * 2 <= S; step0 <<= 1) {}
+    const size_t nb = 2 * G + 1;
+
+    if (hipSetDevice(device) != hipSuccess) return NTF_EHIP;
+    DevBuf dv, dpiv, dcnt, dflag, dx;
+    if (!dv.put(v.data(), G * 4) || !dpiv.put(piv.data(), (size_t)S * 4) || !dcnt.alloc(nb * 8) || !dflag.alloc(4) || !dx.alloc((stage_bytes + 15) & ~(size_t)15))
+        return NTF_ENOMEM;
+    if (hipMemset(dcnt.p, 0, nb * 8) != hipSuccess || hipMemset(dflag.p, 0, 4) != hipSuccess) return NTF_EHIP;
+    const bool lds_hist = nb <= (size_t)AUC_LDS_BUCKETS;
+    double upload_ms = 0.0, kernel_ms = 0.0;                                               // NTF_AUC_TIMING=1: reported on stderr (profiles/auc_time.py)
+    int64_t streamed = 0;
+    for (int64_t k = 0; k < n_chunks; ++k) {
+        int64_t L = 0;
+        auto t0 = std::chrono::steady_clock::now();
+        if (!next_chunk(k, dx.p, &L)) return NTF_EHIP;
+        upload_ms += ms_since(t0);
+        if (L <= 0) continue;
+        streamed += L;
+        t0 = std::chrono::steady_clock::now();
+        // (a workgroup's LDS counters are 32-bit: it sees at most L / blocks + 1024 scores of a chunk, far below 2^32 for any chunk that fits in HBM)
+        const int64_t want = ((L >> 2) + 2 * AUC_THREADS - 1) / (2 * AUC_THREADS);
+        const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>(want, 1), AUC_MAX_BLOCKS);
+        if (lds_hist)
+            hipLaunchKernelGGL(k_auc_count<true>, dim3(blocks), dim3(AUC_THREADS), 0, 0, (const uint32_t*)dx.p, L, (const uint32_t*)dv.p, (uint32_t)G,
+                               (const uint32_t*)dpiv.p, S, step0, stride, (unsigned long long*)dcnt.p, (uint32_t*)dflag.p);
+        else
+            hipLaunchKernelGGL(k_auc_count<false>, dim3(blocks), dim3(AUC_THREADS), 0, 0, (const uint32_t*)dx.p, L, (const uint32_t*)dv.p, (uint32_t)G,
+                               (const uint32_t*)dpiv.p, S, step0, stride, (unsigned long long*)dcnt.p, (uint32_t*)dflag.p);
+        if (hipGetLastError() != hipSuccess) return NTF_EHIP;
+        if (hipStreamSynchronize(nullptr) != hipSuccess) return NTF_EHIP;                  // the next upload reuses the staging buffer
+        kernel_ms += ms_since(t0);
+    }
+    if (const char* t = std::getenv("NTF_AUC_TIMING"); t && t[0] == '1')
+        std::fprintf(stderr, "ntf_auc: %lld scores in %lld chunk(s), G = %zu (%s counters): upload %.3f ms, kernel %.3f ms (launch + wait; %.1f GB/s of scores)\n",
+                     (long long)streamed, (long long)n_chunks, G, lds_hist ? "LDS" : "global", upload_ms, kernel_ms, kernel_ms > 0 ? streamed * 4e-6 / kernel_ms : 0.0);
+    std::vector<uint64_t> cnt(nb);
+    uint32_t flag = 0;
+    if (hipMemcpy(cnt.data(), dcnt.p, nb * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&flag, dflag.p, 4, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
+    if (flag) return NTF_EINVAL;                                                           // a NaN score
+    if (implicit_zeros) {
+        uint32_t nan = 0;
+        const uint32_t kz = auc_key(0u, nan);
+        const size_t g = std::lower_bound(v.begin(), v.end(), kz) - v.begin();
+        cnt[2 * g + ((g < G && v[g] == kz) ? 1 : 0)] += implicit_zeros;
+    }
+    // cnt[2 g] = all scores strictly between v[g - 1] and v[g], cnt[2 g + 1] = all scores equal to v[g], the positives among them included
+    unsigned __int128 u2 = 0, below = 0, seen = 0;
+    for (size_t g = 0; g < G; ++g) {
+        if (cnt[2 * g + 1] < pos_eq[g]) return NTF_EHIP;                                   // (cannot happen: every positive is one of the scores)
+        const uint64_t neg_eq = cnt[2 * g + 1] - pos_eq[g];
+        below += cnt[2 * g];
+        u2 += (unsigned __int128)pos_eq[g] * (2 * below + neg_eq);
+        below += neg_eq;
+        seen += (unsigned __int128)cnt[2 * g] + cnt[2 * g + 1];
+    }
+    seen += cnt[2 * G];
+    if (seen != total || u2 >> 64) return NTF_EHIP;                                        // (every score was counted exactly once)
+    out_counts[0] = P; out_counts[1] = N; out_counts[2] = (uint64_t)u2;
+    *out_auc = (double)(uint64_t)u2 / (2.0 * (double)P * (double)N);
+    return NTF_OK;
+}
+}  // namespace
+
+extern "C" int ntf_auc_micro_dense(int device, const float* scores, int64_t n, int64_t M, int64_t ld, const int64_t* truth_indptr,
+                                   const int32_t* truth_indices, int64_t n_truth_rows, const int64_t* rows, int64_t chunk_bytes, uint64_t out_counts[3],
+                                   double* out_auc) {
+    if (!scores || n < 1 || M < 1 || ld < M || chunk_bytes < 0 || !out_counts || !out_auc) return NTF_EINVAL;
+    if (chunk_bytes == 0) chunk_bytes = NTF_AUC_CHUNK_BYTES;
+    const int64_t rows_per_chunk = std::min<int64_t>(chunk_bytes / 4 / M, n);
+    if (rows_per_chunk < 1) return NTF_EINVAL;
+    Truth t;
+    if (!read_truth(n, M, truth_indptr, truth_indices, n_truth_rows, rows, t)) return NTF_EINVAL;
+    std::vector<uint32_t> keys(t.col.size());
+    uint32_t nan = 0;
+    for (size_t j = 0; j < keys.size(); ++j) {
+        uint32_t u;
+        std::memcpy(&u, scores + t.inst[j] * ld + t.col[j], 4);
+        keys[j] = auc_key(u, nan);
+    }
+    if (nan) return NTF_EINVAL;
+    const int64_t n_chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+    auto upload = [&](int64_t k, void* dev, int64_t* L) {
+        const int64_t r0 = k * rows_per_chunk, nr = std::min(rows_per_chunk, n - r0);
+        *L = nr * M;
+        if (ld == M) return hipMemcpy(dev, scores + r0 * ld, (size_t)nr * M * 4, hipMemcpyHostToDevice) == hipSuccess;
+        // rows land back to back on the device: the padding behind a row is never read, and every chunk starts 16-byte aligned
+        return hipMemcpy2D(dev, (size_t)M * 4, scores + r0 * ld, (size_t)ld * 4, (size_t)M * 4, (size_t)nr, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    return auc_run(device, keys, (unsigned __int128)n * M, 0, (size_t)rows_per_chunk * M * 4, n_chunks, upload, out_counts, out_auc);
+}
+
+extern "C" int ntf_auc_micro_csr(int device, const int64_t* s_indptr, const int32_t* s_indices, const float* s_values, int64_t n, int64_t M,
+                                 const int64_t* truth_indptr, const int32_t* truth_indices, int64_t n_truth_rows, const int64_t* rows, int64_t chunk_bytes,
+                                 uint64_t out_counts[3], double* out_auc) {
+    if (!s_indptr || n < 1 || M < 1 || chunk_bytes < 0 || !out_counts || !out_auc) return NTF_EINVAL;
+    if (chunk_bytes == 0) chunk_bytes = NTF_AUC_CHUNK_BYTES;
+    if (chunk_bytes < 4) return NTF_EINVAL;
+    const int64_t e0 = s_indptr[0], e1 = s_indptr[n], nnz = e1 - e0;
+    if (e0 < 0 || nnz < 0 || (nnz > 0 && (!s_indices || !s_values))) return NTF_EINVAL;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t b = s_indptr[i], e = s_indptr[i + 1];
+        if (e < b || e > e1) return NTF_EINVAL;
+        for (int64_t j = b; j < e; ++j)
+            if (s_indices[j] < 0 || s_indices[j] >= M || (j > b && s_indices[j] <= s_indices[j - 1])) return NTF_EINVAL;
+    }
+    Truth t;
+    if (!read_truth(n, M, truth_indptr, truth_indices, n_truth_rows, rows, t)) return NTF_EINVAL;
+    std::vector<uint32_t> keys(t.col.size());
+    uint32_t nan = 0;
+    for (size_t j = 0; j < keys.size(); ++j) {
+        const int32_t* b = s_indices + s_indptr[t.inst[j]];
+        const int32_t* e = s_indices + s_indptr[t.inst[j] + 1];
+        const int32_t* f = std::lower_bound(b, e, t.col[j]);
+        uint32_t u = 0;                                                                   // not stored: 0.0
+        if (f != e && *f == t.col[j]) std::memcpy(&u, s_values + (f - s_indices), 4);
+        keys[j] = auc_key(u, nan);
+    }
+    if (nan) return NTF_EINVAL;
+    const int64_t per_chunk = std::max<int64_t>(std::min<int64_t>(chunk_bytes / 4, nnz), 1);
+    const int64_t n_chunks = (nnz + per_chunk - 1) / per_chunk;
+    auto upload = [&](int64_t k, void* dev, int64_t* L) {
+        const int64_t b = k * per_chunk;
+        *L = std::min(per_chunk, nnz - b);
+        return hipMemcpy(dev, s_values + e0 + b, (size_t)*L * 4, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    const unsigned __int128 total = (unsigned __int128)n * M;
+    if ((total - (unsigned __int128)nnz) >> 64) return NTF_EINVAL;
+    return auc_run(device, keys, total, (uint64_t)(total - (unsigned __int128)nnz), (size_t)per_chunk * 4, n_chunks, upload, out_counts, out_auc);
+}

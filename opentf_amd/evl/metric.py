@@ -2,18 +2,22 @@
 
 Same function names, arguments and returned DataFrames as the reference (`calculate_metrics` 5-35, `calculate_skill_coverage`
 44-73); the reference builds python dicts for pytrec_eval row by row, here the ranked top-K lists go through
-`ntf_rank_metrics` / `ntf_skill_coverage` of libopentf_amd.so.  `calculate_auc_roc` stays sklearn on the host, as in the reference.
+`ntf_rank_metrics` / `ntf_skill_coverage` of libopentf_amd.so.  `calculate_auc_roc` takes the host routes by default (sklearn as in the reference for dense
+predictions, `micro_auc_sparse` for sparse ones); with a device ordinal - `score_predictions` passes one when NTF_AUC_DEVICE=1 - the micro-averaged AUC is
+`micro_auc_device`: one streaming pass over the scores on the GPU (`ntf_auc_micro_dense` / `ntf_auc_micro_csr`), exact in integers.  The curve stays sklearn.
 Ties in the scores are ranked by ascending expert id (trec_eval: descending document name) — irrelevant for real-valued model
 outputs, stated here because it is the one place the two can differ.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import scipy.sparse as sp
 
 TREC = ("P", "recall", "ndcg_cut", "map_cut", "success")
+_ONE_CLASS = "Only one class present in y_true. ROC AUC score is not defined in that case."     # sklearn's message
 
 
 def _ptr(a):
@@ -91,7 +95,7 @@ def micro_auc_sparse(Y, Y_):
     total = n * M
     P = int((Y.data != 0).sum())
     if P == 0 or P == total:
-        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+        raise ValueError(_ONE_CLASS)
     Yb = Y.copy(); Yb.data = (Yb.data != 0).astype(np.int8); Yb.eliminate_zeros(); Yb.sort_indices()
     S = Y_.copy(); S.sum_duplicates(); S.sort_indices()
     # label of every stored score: flat keys row * M + col looked up among the positives' keys
@@ -116,10 +120,47 @@ def micro_auc_sparse(Y, Y_):
     return U / (float(P) * float(total - P))
 
 
-def calculate_auc_roc(Y, Y_, curve=False):
+def micro_auc_device(Y, Y_, device=0, chunk_bytes=0, return_counts=False):
+    """Micro-averaged ROC AUC on the device: what `micro_auc_sparse` / sklearn's `roc_auc_score(Y.toarray(), Y_.toarray(), average='micro')`
+    (src/evl/metric.py:36-41) compute, from one streaming pass over the scores (`ntf_auc_micro_csr` for a scipy sparse `Y_`, whose unstored entries
+    score 0; `ntf_auc_micro_dense` for a dense f32 or f16 array) - no dense truth matrix, no sort of the n * M pairs.  The library returns the integers
+    P, N and U2 = sum over positives of (2 #negatives scored lower + #negatives scored equal); the AUC is U2 / (2 P N), one division in f64.  Dense
+    input of any other dtype is refused: a cast to f32 could merge values that sklearn keeps apart.  `chunk_bytes`: device staging budget per upload
+    (0: the library's default, NTF_AUC_CHUNK_BYTES).  return_counts: -> (auc, (P, N, U2)) with Python ints."""
+    assert Y.shape == Y_.shape, f"Shape mismatch between truth Y {Y.shape} vs preds Y_ {Y_.shape}!"
+    if not sp.issparse(Y_):
+        Y_ = np.asarray(Y_)
+        if Y_.dtype not in (np.float32, np.float16):
+            raise TypeError(f"micro_auc_device takes dense scores as float32 or float16, not {Y_.dtype}: a cast could merge values that are distinct")
+    Yb = sp.csr_matrix(Y).copy(); Yb.data = (Yb.data != 0).astype(np.int8); Yb.eliminate_zeros(); Yb.sort_indices()
+    n, M = Yb.shape
+    if Yb.nnz == 0 or Yb.nnz == n * M:
+        raise ValueError(_ONE_CLASS)
+    from .. import libntf
+    ip, ix = np.ascontiguousarray(Yb.indptr, dtype=np.int64), np.ascontiguousarray(Yb.indices, dtype=np.int32)
+    counts, auc = np.zeros(3, dtype=np.uint64), C.c_double()
+    if sp.issparse(Y_):
+        S = sp.csr_matrix(Y_).copy(); S.sum_duplicates(); S.sort_indices()
+        sip, six = np.ascontiguousarray(S.indptr, dtype=np.int64), np.ascontiguousarray(S.indices, dtype=np.int32)
+        sv = np.ascontiguousarray(S.data, dtype=np.float32)
+        rc = libntf.lib().ntf_auc_micro_csr(int(device), _ptr(sip), _ptr(six), _ptr(sv), n, M, _ptr(ip), _ptr(ix), n, None, int(chunk_bytes), _ptr(counts), C.byref(auc))
+        name = "ntf_auc_micro_csr"
+    else:
+        D = np.ascontiguousarray(Y_, dtype=np.float32)      # f16 -> f32 is exact
+        rc = libntf.lib().ntf_auc_micro_dense(int(device), _ptr(D), n, M, M, _ptr(ip), _ptr(ix), n, None, int(chunk_bytes), _ptr(counts), C.byref(auc))
+        name = "ntf_auc_micro_dense"
+    if rc != 0:
+        raise libntf.NtfError(f"{name} failed ({rc})" + (": a NaN score, or an argument outside the contract" if rc == libntf.NTF_EINVAL else ""))
+    return (auc.value, tuple(int(c) for c in counts)) if return_counts else auc.value
+
+
+def calculate_auc_roc(Y, Y_, curve=False, device=None):
     """src/evl/metric.py:36-41.  Sparse predictions (the top-K `.pred` files) go through `micro_auc_sparse`; dense ones, and the curve
-    itself, through sklearn as in the reference."""
+    itself, through sklearn as in the reference.  `device` (an ordinal; None: the host routes above): without the curve, sparse and dense
+    f32 predictions go through `micro_auc_device` instead."""
     assert Y.shape == Y_.shape
+    if device is not None and not curve and (sp.issparse(Y_) or np.asarray(Y_).dtype == np.float32):
+        return micro_auc_device(Y, Y_, device=device), None
     if sp.issparse(Y_) and not curve:
         return micro_auc_sparse(Y, Y_), None
     from sklearn import metrics as skm
@@ -180,7 +221,8 @@ def score_predictions(teamsvecs, rows, Y_, spec, device=0):
         df, df_mean = calculate_metrics(Y, Y_, spec.topK, spec.per_instance, spec.trec, device=device)
         inst_parts.append(df); mean_parts.append(df_mean)
     if spec.auc:
-        auc, roc = calculate_auc_roc(Y, Y_, curve=(spec.auc == "aucroc+"))
+        on_device = os.environ.get("NTF_AUC_DEVICE", "0") == "1"      # read per call; off: the host routes, as before the device entry existed
+        auc, roc = calculate_auc_roc(Y, Y_, curve=(spec.auc == "aucroc+"), device=device if on_device else None)
         mean_parts.append(pd.DataFrame({"mean": [auc]}, index=pd.Index(["aucroc"], name="metrics")))
     if spec.skc:
         X = teamsvecs["skill"] if sp.issparse(teamsvecs["skill"]) else teamsvecs["original_skill"]

@@ -101,6 +101,8 @@ SYMBOLS = {
     "ntf_kernel_times": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int]),
     "ntf_rank_metrics": (C.c_int, [C.c_int, _P, _I64, _I32, _P, _P, _I64, _P, _P, _I32, _P]),
     "ntf_skill_coverage": (C.c_int, [C.c_int, _P, _I64, _I32, _P, _P, _I64, _P, _P, _P, _I64, _P, _I32, _P]),
+    "ntf_auc_micro_dense": (C.c_int, [C.c_int, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
+    "ntf_auc_micro_csr": (C.c_int, [C.c_int, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
     "ntf_skill_cooccurrence": (C.c_int, [C.c_int, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "ntf_csr_result_fetch": (C.c_int, [_P, _P, _P, _P, _P]),
     "ntf_csr_result_free": (None, [_P]),
