@@ -65,7 +65,7 @@ struct ntf_engine {
     int64_t* s_indptr = nullptr; int32_t* s_indices = nullptr; int64_t s_rows = 0;
     float* table = nullptr; int64_t n_skills = 0; int table_d = 0; int32_t s_max_col = -1;
     float* Xall = nullptr; int64_t x_rows = 0;
-    float* al_prob = nullptr; int32_t* al_alias = nullptr; double* al_weight = nullptr; double al_total = 0; int64_t al_n = 0;
+    float* al_prob = nullptr; int32_t* al_alias = nullptr; double* al_weight = nullptr; double al_total = 0; int64_t al_n = 0; int al_weighted = 0;   // (al_weighted: columns with weight > 0)
     // per-step buffers
     int64_t* d_rows = nullptr; int64_t* d_order = nullptr; int64_t order_cap = 0; std::vector<int64_t> h_order;
     // sampled negatives [B, ns] of a step live in one of TWO buffers, by step parity (as the fused workspace does): a train step's head prefetch runs the NEXT batch's
@@ -458,6 +458,8 @@ static int upload_alias(ntf_engine* e, const double* w, int64_t n) {
     HIPCHK(e, hipMemcpy(e->al_alias, alias.data(), n * 4, hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(e->al_weight, w, n * 8, hipMemcpyHostToDevice));
     e->al_total = total;
+    e->al_weighted = 0;
+    for (int64_t i = 0; i < n; ++i) e->al_weighted += w[i] > 0.0 ? 1 : 0;
     return NTF_OK;
 }
 extern "C" int ntf_set_unigram(ntf_engine* e, const double* freq, int64_t n) {
@@ -735,7 +737,7 @@ static int sample_negatives(ntf_engine* e, const StepCtx& c) {
         launch_ns_uniform(e->st, c.rows_dev, c.B, M, e->cfg.ns, e->m_indptr, e->m_indices, k0, k1, (uint32_t)c.step, c.row0, e->d_neg_set[c.step & 1]);
     } else if (e->cfg.nsd == NTF_NSD_UNIGRAM) {
         if (!e->al_prob) FAIL(e, NTF_ESTATE, "unigram table not set (ntf_set_unigram)");
-        launch_ns_alias(e->st, c.rows_dev, c.B, M, e->cfg.ns, e->m_indptr, e->m_indices, e->al_prob, e->al_alias, e->al_weight, e->al_total,
+        launch_ns_alias(e->st, c.rows_dev, c.B, M, e->cfg.ns, e->m_indptr, e->m_indices, e->al_prob, e->al_alias, e->al_weight, e->al_total, e->al_weighted,
                         k0, k1, (uint32_t)c.step, c.row0, e->d_neg_set[c.step & 1]);
     } else if (e->cfg.nsd == NTF_NSD_UNIGRAM_B) {
         const char* d = static_cast<const char*>(e->ub_dev[c.ub]);

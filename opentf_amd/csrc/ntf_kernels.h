@@ -95,7 +95,7 @@ void launch_ns_uniform(hipStream_t st, const int64_t* rows, int B, int M, int ns
 // row's negatives have zero total weight
 void launch_ns_alias(hipStream_t st, const int64_t* rows, int B, int M, int ns, const int64_t* m_indptr,
                      const int32_t* m_indices, const float* prob, const int32_t* alias, const double* weight,
-                     double total_weight, uint32_t k0, uint32_t k1, uint32_t step, uint32_t row0, int64_t* out);
+                     double total_weight, int n_weighted /* columns with weight > 0 */, uint32_t k0, uint32_t k1, uint32_t step, uint32_t row0, int64_t* out);
 
 // the same over a sparse support (unigram_b: the experts of the current batch): cols sorted ascending, tables indexed by support slot
 void launch_ns_alias_sparse(hipStream_t st, const int64_t* rows, int B, int M, int ns, const int64_t* m_indptr, const int32_t* m_indices,

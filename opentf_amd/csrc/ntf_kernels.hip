@@ -556,10 +556,12 @@ __global__ void k_ns_uniform(const int64_t* __restrict__ rows, int B, int M, int
     const int npos = (int)(m_indptr[team + 1] - m_indptr[team]);
     int64_t* o = out + (int64_t)i * ns;
     RowSet rs; rs.init(mi, npos, o);
+    const int nneg = M - npos;      // the row's negatives (its CSR entries are distinct): once all are picked no candidate can pass - without this bound a row with fewer
+                                    // than ns negatives spent 4 x 4096 rejected candidates, each a scan of its positives, on every further pick (seconds at M = 300)
     uint32_t ctr = 0;
     for (int q = 0; q < ns; ++q) {
         int pick = -1;
-        for (int tries = 0; tries < 4096 && pick < 0; ++tries) {
+        for (int tries = 0; tries < 4096 && pick < 0 && q < nneg; ++tries) {
             const uint4 r = philox4x32(make_uint4((uint32_t)i + row0, ctr++, step, 0x4e533031u), make_uint2(k0, k1));
             const uint32_t cand[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
@@ -582,7 +584,7 @@ void launch_ns_uniform(hipStream_t st, const int64_t* rows, int B, int M, int ns
 
 __global__ void k_ns_alias(const int64_t* __restrict__ rows, int B, int M, int ns, const int64_t* __restrict__ m_indptr,
                            const int32_t* __restrict__ m_indices, const float* __restrict__ prob, const int32_t* __restrict__ alias,
-                           const double* __restrict__ weight, double total_weight, uint32_t k0, uint32_t k1, uint32_t step, uint32_t row0,
+                           const double* __restrict__ weight, double total_weight, int n_weighted, uint32_t k0, uint32_t k1, uint32_t step, uint32_t row0,
                            int64_t* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
@@ -592,12 +594,13 @@ __global__ void k_ns_alias(const int64_t* __restrict__ rows, int B, int M, int n
     int64_t* o = out + (int64_t)i * ns;
     RowSet rs; rs.init(mi, npos, o);
     double negw = total_weight;
-    for (int p = 0; p < npos; ++p) negw -= weight[mi[p]];
+    int nadm = n_weighted;          // admissible experts of the row: columns with weight (n_weighted of them) that are not its members; once all are picked no candidate can pass
+    for (int p = 0; p < npos; ++p) { const double wp = weight[mi[p]]; negw -= wp; nadm -= (wp > 0.0) ? 1 : 0; }
     const bool fallback = !(negw > 1e-12 * total_weight);  // all sampling weight sits on the row's members (fnn.py:67-69)
     uint32_t ctr = 0;
     for (int q = 0; q < ns; ++q) {
         int pick = -1;
-        for (int tries = 0; tries < 8192 && pick < 0; ++tries) {
+        for (int tries = 0; tries < 8192 && pick < 0 && (fallback || q < nadm); ++tries) {
             const uint4 r = philox4x32(make_uint4((uint32_t)i + row0, ctr++, step, 0x4e533032u), make_uint2(k0, k1));
             for (int u = 0; u < 2 && pick < 0; ++u) {
                 const uint32_t a = u ? r.z : r.x, b = u ? r.w : r.y;
@@ -619,10 +622,10 @@ __global__ void k_ns_alias(const int64_t* __restrict__ rows, int B, int M, int n
     }
 }
 void launch_ns_alias(hipStream_t st, const int64_t* rows, int B, int M, int ns, const int64_t* m_indptr, const int32_t* m_indices,
-                     const float* prob, const int32_t* alias, const double* weight, double total_weight, uint32_t k0, uint32_t k1,
+                     const float* prob, const int32_t* alias, const double* weight, double total_weight, int n_weighted, uint32_t k0, uint32_t k1,
                      uint32_t step, uint32_t row0, int64_t* out) {
     hipLaunchKernelGGL(k_ns_alias, dim3((B + 63) / 64), dim3(64), 0, st, rows, B, M, ns, m_indptr, m_indices, prob, alias, weight,
-                       total_weight, k0, k1, step, row0, out);
+                       total_weight, n_weighted, k0, k1, step, row0, out);
 }
 
 // unigram_b: the per-batch frequency table has support only on the experts of the batch (<= a few thousand of M): the alias
@@ -639,16 +642,17 @@ __global__ void k_ns_alias_sparse(const int64_t* __restrict__ rows, int B, int M
     int64_t* o = out + (int64_t)i * ns;
     RowSet rs; rs.init(mi, npos, o);
     double negw = total_weight;
+    int nadm = nsup;                // admissible experts of the row: at most the support slots that are not its members; once that many are picked no candidate can pass
     for (int p = 0; p < npos; ++p) {
         int lo = 0, hi = nsup;
         while (lo < hi) { const int mid = (lo + hi) >> 1; if (cols[mid] < mi[p]) lo = mid + 1; else hi = mid; }
-        if (lo < nsup && cols[lo] == mi[p]) negw -= (double)weight[lo];
+        if (lo < nsup && cols[lo] == mi[p]) { negw -= (double)weight[lo]; --nadm; }
     }
     const bool fallback = !(negw > 1e-9 * total_weight) || nsup == 0;  // every sampling weight sits on the row's members (fnn.py:67-69)
     uint32_t ctr = 0;
     for (int q = 0; q < ns; ++q) {
         int pick = -1;
-        for (int tries = 0; tries < 8192 && pick < 0; ++tries) {
+        for (int tries = 0; tries < 8192 && pick < 0 && (fallback || q < nadm); ++tries) {
             const uint4 r = philox4x32(make_uint4((uint32_t)i + row0, ctr++, step, 0x4e533033u), make_uint2(k0, k1));
             for (int u = 0; u < 2 && pick < 0; ++u) {
                 const uint32_t a = u ? r.z : r.x, b = u ? r.w : r.y;

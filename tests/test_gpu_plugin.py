@@ -79,6 +79,31 @@ def test_learn_and_test_reproduce_the_reference_run(nsd, tmp_path):
             np.testing.assert_allclose(pr["y_pred"].numpy(), g[f"f{k}.y_pred"], rtol=1e-3, atol=1e-5)
 
 
+@pytest.mark.parametrize("weights", [(3, 0.5), None], ids=["tpw3-tnw0.5", "absent"])
+def test_learn_hands_the_loss_weights_and_ns_to_the_engine(weights, tmp_path):
+    """tpw, tnw and ns of the model's config reach ntf_engine_create as they stand; a config without tpw / tnw trains at 1 and 1"""
+    from opentf_amd import libntf
+    from opentf_amd.mdl.fnn import Fnn
+    cfg = Cfg(b=5, e=1, ns=9, lr=0.01, es=2, h=[16], spe=0, l="bce", nsd="uniform")
+    if weights: cfg.update(tpw=weights[0], tnw=weights[1])
+    tv, splits = _toy("dblp")
+    seen = []
+    orig = libntf.Engine.__init__
+    def spy(self, dims, *a, **k):
+        seen.append((k.get("tpw"), k.get("tnw"), k.get("ns")))
+        return orig(self, dims, *a, **k)
+    libntf.Engine.__init__ = spy
+    try:
+        m = Fnn(str(tmp_path), "cuda:0", 0, cfg)
+        m.writer = Scalars
+        m.learn(tv, splits, None)
+    finally:
+        libntf.Engine.__init__ = orig
+    assert seen and all(s == ((3.0, 0.5, 9) if weights else (1.0, 1.0, 9)) for s in seen), seen
+    ck = torch.load(f"{m.output}/f0.pt", map_location="cpu", weights_only=False)
+    assert np.isfinite(ck["t_loss"]) and np.isfinite(ck["v_loss"])
+
+
 def test_bnn_files_layout_topk_and_per_epoch(tmp_path):
     from opentf_amd.mdl.bnn import Bnn
     lay = json.load(open(os.path.join(GOLDEN, "g8_layout.json")))

@@ -30,6 +30,7 @@ pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
 KINK_C = 8.0            # rounding scale of a pre-activation: KINK_C * sqrt(fan-in so far) * 2^-24 * sum of |terms|
 FUSED_H = (32, 64, 128, 256)
+FUSED_OUT_H = FUSED_H + (96, 160, 192, 224)      # every last hidden width with fused output-layer kernels (FUSED_H: those with all three engine modes here)
 GENERIC_OUT = ("out_fwd_gemm", "out_bwd_dw_gemm", "out_bwd_da_gemm")
 FUSED_OUT = ("out_fused_fwd_loss_dh", "out_fused_dw_adam")
 
@@ -101,14 +102,14 @@ def _kink_units(sd, X, noise):
     return out
 
 
-def _oracle(pb):
+def _oracle(pb, tpw=10.0, tnw=1.0):
     """logits, loss, every gradient and the parameters after one Adam step, in float64"""
     sd = {k: v.double() for k, v in pb["sd"].items()}
     X, y, nz = pb["X"].double(), pb["y"].double(), _d64(pb["noise"])
     with torch.no_grad():
         logits = O.model_forward(sd, X, nz).numpy()
         kinks = _kink_units(sd, X, nz)
-    loss, grads = O.loss_and_grads(sd, X, y, pb["neg"], 10.0, 1.0, nz)
+    loss, grads = O.loss_and_grads(sd, X, y, pb["neg"], tpw, tnw, nz)
     new = {k: v.clone() for k, v in sd.items()}
     O.Adam(new, 1e-3).step(new, grads)
     return {"logits": logits, "loss": loss, "grads": {k: v.numpy() for k, v in grads.items()}, "new": {k: v.numpy() for k, v in new.items()},
@@ -193,9 +194,9 @@ def _check_inference(e, pb, orc, rows, tag):
         assert (np.abs(picked - vals) <= rowtol).all(), (tag, K, "top-K ids")
 
 
-def _make(pb, dims, B, bayesian, mode, fuse_adam):
+def _make(pb, dims, B, bayesian, mode, fuse_adam, tpw=10.0, tnw=1.0):
     e = _engine(dims, bayesian=bayesian, input_mode=libntf.INPUT_MULTIHOT if pb["multihot"] else libntf.INPUT_DENSE, max_batch=B, ns=pb["ns"],
-                nsd="uniform" if pb["ns"] else None, tpw=10.0, tnw=1.0, lr=1e-3, fused=mode != "generic", mfma="f32" if mode == "f32" else None,
+                nsd="uniform" if pb["ns"] else None, tpw=tpw, tnw=tnw, lr=1e-3, fused=mode != "generic", mfma="f32" if mode == "f32" else None,
                 fuse_adam=fuse_adam)
     if pb["multihot"]:
         ip, ix = (np.asarray(a) for a in _csr(pb["X"].numpy()))
@@ -212,12 +213,13 @@ def _csr(dense):
     return m.indptr.astype(np.int64), m.indices.astype(np.int32)
 
 
-def _run(pb, orc, dims, B, bayesian, mode, inference=True):
-    """one injected step on both sides, from identical state.  Returns the kernel families the default fused step ran."""
+def _run(pb, orc, dims, B, bayesian, mode, inference=True, tpw=10.0, tnw=1.0, after_backward=None):
+    """one injected step on both sides, from identical state (orc: _oracle(pb, tpw, tnw)).  after_backward(engine): further checks on the engine that
+    ran backward().  Returns the kernel families the default fused step ran."""
     tag = (dims, B, bayesian, mode)
     rows = np.arange(B)
     inj = _inject(pb["neg"], pb["noise"])
-    e = _make(pb, dims, B, bayesian, mode, 0)
+    e = _make(pb, dims, B, bayesian, mode, 0, tpw, tnw)
     try:
         _check_logits(e.logits(rows, inject=inj), orc["logits"], tag)
         if inference: _check_inference(e, pb, orc, rows, tag)
@@ -226,9 +228,10 @@ def _run(pb, orc, dims, B, bayesian, mode, inference=True):
         loss = e.backward(rows, inject=inj)
         assert abs(loss - orc["loss"]) <= 2e-5 * abs(orc["loss"]), (tag, "loss", loss, orc["loss"])
         _check_grads(e.grads(), orc["grads"], orc["kinks"], tag)
+        if after_backward is not None: after_backward(e)
     finally:
         e.close()
-    e = _make(pb, dims, B, bayesian, mode, 1)      # the plugin's default: the output layer's Adam in the dW epilogue
+    e = _make(pb, dims, B, bayesian, mode, 1, tpw, tnw)      # the plugin's default: the output layer's Adam in the dW epilogue
     try:
         e.kernel_times(True)
         loss = e.train_step(rows, inject=inj)
@@ -237,7 +240,7 @@ def _run(pb, orc, dims, B, bayesian, mode, inference=True):
         _check_params(e.state_dict(), orc["new"], orc["kinks"], tag)
     finally:
         e.close()
-    fused = mode != "generic" and dims[-2] in FUSED_H and len(dims) > 2
+    fused = mode != "generic" and len(dims) > 2 and dims[-2] in FUSED_OUT_H
     if len(dims) > 2:
         for fam in (FUSED_OUT if fused else GENERIC_OUT):
             assert kt[fam][1] > 0, (tag, fam, "did not run")
@@ -331,18 +334,20 @@ def test_large_batch_with_a_hidden_to_hidden_layer(bayesian):
         assert kt[fam][1] > 0, (fam, kt[fam])
 
 
-def test_expert_shards_at_B8000_against_the_f64_oracle():
-    """B = 8 000, [128, 128, 2 x 2 048] cut into two expert shards stepped through ntf_step_staged_ep (d(hidden) summed between phases 1 and 2)
+def _expert_shard_step(dims, B, tpw, tnw, ns, labels=None, seed=31, t0=17, before_compare=None):
+    """a Bnn model whose output layer is cut into two expert shards, stepped through ntf_step_staged_ep (d(hidden) summed between phases 1 and 2)
     on the device's own draws: each shard's output-layer gradient and updated parameters against the oracle's columns of that shard, the
-    replicated hidden layer's gradient and parameters (after the exchange) against the whole oracle"""
-    dims, B, seed, t0 = [128, 128, 4096], 8000, 31, 17
-    pb = _problem(dims, B, True, seed, 5)
+    replicated hidden layer's gradient and parameters (after the exchange) against the whole oracle.  labels = (member CSR, dense y): these
+    rows in place of _problem's; before_compare(pb, orc): the caller's conditions on the oracle's side, before any device value is compared."""
+    H, M = dims[-2], dims[-1]
+    pb = _problem(dims, B, True, seed, ns)
+    if labels is not None: pb["member"], pb["y"] = labels
     order = np.arange(B, dtype=np.int64)
-    shards = expert_shards(dims[-1], 2)
-    assert shards == [(0, 2048), (2048, 4096)]
+    shards = expert_shards(M, 2)
+    assert shards == [(0, M // 2), (M // 2, M)]
     engines = []
     for s in shards:
-        e = libntf.Engine(dims, bayesian=True, input_mode=libntf.INPUT_DENSE, max_batch=B, ns=5, nsd="uniform", tpw=10.0, tnw=1.0, lr=1e-3,
+        e = libntf.Engine(dims, bayesian=True, input_mode=libntf.INPUT_DENSE, max_batch=B, ns=ns, nsd="uniform", tpw=tpw, tnw=tnw, lr=1e-3,
                           seed=seed, fuse_adam=0, expert_shard=s, ep_world=2)
         e.set_dense_input(pb["X"].numpy()); e.set_member(pb["member"]); e.load_state_dict(pb["sd"])
         e.set_seed(seed, t0); e.stage_order(order); e.epoch_loss()
@@ -351,8 +356,8 @@ def test_expert_shards_at_B8000_against_the_f64_oracle():
         for e in engines:
             e.step_staged_ep(0, B, 1); e.synchronize()
         dh = [e.dh_tensor() for e in engines]
-        tot = torch.stack([d[: B * 128] for d in dh]).sum(0)
-        for d in dh: d[: B * 128].copy_(tot)
+        tot = torch.stack([d[: B * H] for d in dh]).sum(0)
+        for d in dh: d[: B * H].copy_(tot)
         torch.cuda.synchronize()
         for e in engines:
             e.step_staged_ep(0, B, 2); e.step_staged_ep(0, B, 3)
@@ -371,8 +376,11 @@ def test_expert_shards_at_B8000_against_the_f64_oracle():
     noise = [{k: torch.from_numpy(v) for k, v in noises[0][0].items()},
              {k: torch.from_numpy(noises[0][1][k] if k == "s_in" else np.concatenate([n[1][k] for n in noises], axis=out[k])) for k in noises[0][1]}]
     pb["noise"], pb["neg"] = noise, torch.from_numpy(negs[0].astype(np.int64))
-    assert bool((pb["y"][torch.arange(B).unsqueeze(1), pb["neg"]] == 0).all())
-    orc = _oracle(pb)
+    assert all(len(set(r.tolist())) == ns for r in negs[0]) and negs[0].min() >= 0 and negs[0].max() < M, "picks not distinct ids in [0, M)"
+    enough = (M - pb["y"].sum(1)) >= ns            # rows with at least ns negatives: non-members only (src/mdl/fnn.py:48-56)
+    assert bool((pb["y"][torch.arange(B).unsqueeze(1), pb["neg"]] == 0)[enough].all())
+    orc = _oracle(pb, tpw, tnw)
+    if before_compare is not None: before_compare(pb, orc)
     assert abs(loss - orc["loss"]) <= 2e-5 * abs(orc["loss"]), (loss, orc["loss"])
     kinks = orc["kinks"]
     for si, (lo, hi) in enumerate(shards):
@@ -382,6 +390,13 @@ def test_expert_shards_at_B8000_against_the_f64_oracle():
             ref = {k: orc["grads"][k][sl]}
             _check_grads({k: grads[si][k]}, ref, kk, ("shard", si))
             _check_params({k: states[si][k]}, {k: orc["new"][k][sl]}, kk, ("shard", si))
+
+
+def test_expert_shards_at_B8000_against_the_f64_oracle():
+    """B = 8 000, [128, 128, 2 x 2 048] cut into two expert shards stepped through ntf_step_staged_ep (d(hidden) summed between phases 1 and 2)
+    on the device's own draws: each shard's output-layer gradient and updated parameters against the oracle's columns of that shard, the
+    replicated hidden layer's gradient and parameters (after the exchange) against the whole oracle"""
+    _expert_shard_step([128, 128, 4096], 8000, 10.0, 1.0, 5)
 
 
 # ------------------------------------------------------------------------------------------ C. ntf_k_gemm_f32
