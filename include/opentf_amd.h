@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define NTF_ABI_VERSION 1
+#define NTF_ABI_VERSION 2
 #define NTF_MAX_LAYERS 8
 
 enum { NTF_OK = 0, NTF_EINVAL = -1, NTF_EHIP = -2, NTF_ESTATE = -3, NTF_ENOMEM = -4 };
@@ -295,6 +295,28 @@ int ntf_auc_micro_dense(int device, const float* scores, int64_t n, int64_t M, i
 int ntf_auc_micro_csr(int device, const int64_t* s_indptr, const int32_t* s_indices, const float* s_values, int64_t n, int64_t M,
                       const int64_t* truth_indptr, const int32_t* truth_indices, int64_t n_truth_rows, const int64_t* rows,
                       int64_t chunk_bytes, uint64_t out_counts[3], double* out_auc);
+
+/* ---- scoring a prediction set where it is produced: the three sections above on the engine's own probabilities      src/mdl/ntf.py:32-92
+ * Scores the prediction set rows[0, n) in batches rows[o, o + B) (the last one may be shorter; B in [1, max_batch]) without a prediction file, a host sort or an
+ * upload: the truth of instance i is row rows[i] of the resident member CSR (ntf_set_member_csr).  Whole-model engines only (NTF_ESTATE on an expert shard).
+ * The matrix that is scored is the one the eval stage reads from the `.pred` file test() writes:
+ *   K >= 1 (K <= min(M, 2048)): the top-K-sparsified prediction - a row's K largest probabilities in ntf_forward_topk's order (ties to the lower id), every other
+ *     entry 0.0: what ntf_auc_micro_csr computes on that file.  The ranked list of a row is its K stored ids; cutoffs above K behave as in ntf_rank_metrics.
+ *   K == 0: the dense probabilities - what ntf_auc_micro_dense computes on the concatenated ntf_forward outputs.  The ranked list of a row is its top
+ *     max(cutoffs), which must be <= min(M, 2048).
+ * out_metrics [n, 5 * n_cut] (or NULL): ntf_rank_metrics' layout and definitions over the cutoffs (at most 8, each >= 1).  out_counts = { P, N, U2 } and
+ * *out_auc = U2 / (2 P N) (both or neither NULL): the integers of the AUC section above.  out_vals / out_idx [n, K_out] (either may be NULL; K_out = 0 when both
+ * are): the first K_out ranked entries of every row, K_out <= K (dense: <= max(cutoffs)) - for ntf_skill_coverage or a `.pred` file without a second inference.
+ * Generators: the call takes the step indices a loop of ntf_forward_topk (K >= 1) / ntf_forward (K == 0) calls over the same batches would take from the engine's
+ * current step, produces bit-identical probabilities, and leaves the step counter where that loop would.  No injected noise.
+ * Top-K mode infers once, into an [n, K] device store (n * K * 8 bytes; NTF_ENOMEM when it does not fit).  Dense mode holds no [n, M] store: when the AUC is asked
+ * for it runs the inference twice from the same steps (the second sweep feeds the counting kernel) and relies on the replay being bit-identical.  Every positive must
+ * be found among the counted scores and exactly n * M scores must be counted; a replay that is not bit-identical (whatever the inference arm: NTF_INFER_MC,
+ * NTF_INFER_F32, a range fallback, the generic chain) fails these checks and the call returns NTF_EHIP - the AUC is refused, never approximated.
+ * NTF_EINVAL, every output untouched: a null or non-positive argument outside the above, a row id out of range, K > min(M, 2048), n_cut > 8 or a cutoff < 1, a dense
+ * call whose largest cutoff exceeds min(M, 2048), nothing asked for, a NaN probability, and with the AUC asked for P == 0, N == 0 or 2 P N >= 2^64. */
+int ntf_score_rows(ntf_engine* e, const int64_t* rows, int64_t n, int32_t B, int32_t nmc, int32_t K, const int32_t* cutoffs, int32_t n_cut,
+                   float* out_metrics, uint64_t out_counts[3], double* out_auc, int32_t K_out, float* out_vals, int32_t* out_idx);
 
 /* ---- member-skill co-occurrence on the device                                                 src/cmn/team.py:302-337
  * `Team.gen_skill_coverage`: C = member^T . skill over the teams NOT listed in skip_rows (the reference empties the test teams' rows,

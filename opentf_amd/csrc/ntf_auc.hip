@@ -8,6 +8,7 @@
 // into its bucket (k_auc_count: the only pass over the n * M scores); the host finishes in integers from the 2 G + 1 counts.  Integer
 // adds commute, so the result does not depend on how the counting is scheduled.
 #include "../../include/opentf_amd.h"
+#include "ntf_kernels.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -108,6 +109,168 @@ __global__ __launch_bounds__(AUC_THREADS) void k_auc_count(const uint32_t* __res
     }
 }
 
+
+// The positives' keys of a batch of rows, one wave per row: the lanes walk the row's truth columns (CSR row rows[i], global expert ids), key j of row i goes to
+// keys[slot[i] + j] (slot: the host's prefix sum over the truth rows' lengths).  Plain vector loads and stores; a NaN raises *nan_flag as auc_key does.
+// Dense form: the score of column c is P[i, c] of the row-major [B, M] probabilities.
+__global__ __launch_bounds__(64) void k_score_pos_keys_dense(const uint32_t* __restrict__ P, int M, const int64_t* __restrict__ rows, const int64_t* __restrict__ t_indptr,
+                                                             const int32_t* __restrict__ t_indices, const int64_t* __restrict__ slot, uint32_t* __restrict__ keys,
+                                                             uint32_t* __restrict__ nan_flag) {
+    const int64_t i = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t trow = rows[i], tb = t_indptr[trow];
+    const int R = (int)(t_indptr[trow + 1] - tb);
+    uint32_t nan = 0u;
+    for (int j = lane; j < R; j += 64) keys[slot[i] + j] = auc_key(P[i * M + t_indices[tb + j]], nan);
+    if (nan) atomicOr(nan_flag, 1u);
+}
+
+// Top-K form: the score of column c is the stored value whose id is c, 0.0 when c is not among the row's K stored ids.  Per 64 truth columns (one per lane) the wave
+// scans the stored ids in 64-wide windows (one id per lane): truth column t of the chunk is broadcast, a ballot finds the lane holding it.
+__global__ __launch_bounds__(64) void k_score_pos_keys_topk(const uint32_t* __restrict__ vals, const int32_t* __restrict__ idx, int K, const int64_t* __restrict__ rows,
+                                                            const int64_t* __restrict__ t_indptr, const int32_t* __restrict__ t_indices,
+                                                            const int64_t* __restrict__ slot, uint32_t* __restrict__ keys, uint32_t* __restrict__ nan_flag) {
+    const int64_t i = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t trow = rows[i], tb = t_indptr[trow];
+    const int R = (int)(t_indptr[trow + 1] - tb);
+    uint32_t nan = 0u;
+    for (int jb = 0; jb < R; jb += 64) {
+        const int nt = min(64, R - jb);                                  // truth columns of this chunk (wave-uniform)
+        const int c_mine = lane < nt ? t_indices[tb + jb + lane] : -1;
+        int found = -1;                                                  // position of this lane's truth column among the stored ids
+        for (int base = 0; base < K; base += 64) {
+            const int id = base + lane < K ? idx[i * K + base + lane] : -2;
+            for (int t = 0; t < nt; ++t) {
+                const int c = __shfl(c_mine, t, 64);
+                const unsigned long long hit = __ballot(id == c);
+                if (hit && lane == t) found = base + (int)__ffsll((long long)hit) - 1;
+            }
+        }
+        if (lane < nt) keys[slot[i] + jb + lane] = auc_key(found >= 0 ? vals[i * K + found] : 0u, nan);
+    }
+    if (nan) atomicOr(nan_flag, 1u);
+}
+
+void launch_score_pos_keys_dense(hipStream_t st, const float* P, int B, int M, const int64_t* rows, const int64_t* t_indptr, const int32_t* t_indices,
+                                 const int64_t* slot, uint32_t* keys, uint32_t* nan_flag) {
+    hipLaunchKernelGGL(k_score_pos_keys_dense, dim3((unsigned)B), dim3(64), 0, st, (const uint32_t*)P, M, rows, t_indptr, t_indices, slot, keys, nan_flag);
+}
+void launch_score_pos_keys_topk(hipStream_t st, const float* vals, const int32_t* idx, int64_t n, int K, const int64_t* rows, const int64_t* t_indptr,
+                                const int32_t* t_indices, const int64_t* slot, uint32_t* keys, uint32_t* nan_flag) {
+    hipLaunchKernelGGL(k_score_pos_keys_topk, dim3((unsigned)n), dim3(64), 0, st, (const uint32_t*)vals, idx, K, rows, t_indptr, t_indices, slot, keys, nan_flag);
+}
+
+// ---- the key table, the count launch and the integer finish, shared by the two host-fed entries below (auc_run) and ntf_score_rows (device-resident scores)
+struct AucState {
+    std::vector<uint32_t> v;            // sorted distinct keys of the positives
+    std::vector<uint64_t> pos_eq;       // positives per distinct key
+    uint64_t P = 0, N = 0;
+    unsigned __int128 total = 0;
+    uint32_t S = 0, step0 = 0, stride = 1;
+    bool lds_hist = false;
+    uint32_t *dv = nullptr, *dpiv = nullptr, *dflag = nullptr;
+    unsigned long long* dcnt = nullptr;
+};
+
+void auc_free(AucState* s) {
+    if (!s) return;
+    if (s->dv) hipFree(s->dv);
+    if (s->dpiv) hipFree(s->dpiv);
+    if (s->dflag) hipFree(s->dflag);
+    if (s->dcnt) hipFree(s->dcnt);
+    delete s;
+}
+
+int auc_check(uint64_t P, int64_t n, int64_t M, uint64_t* N_out) {
+    const unsigned __int128 total = (unsigned __int128)n * M;
+    if (P == 0 || (unsigned __int128)P >= total) return NTF_EINVAL;                       // one class only
+    const unsigned __int128 N128 = total - P;
+    if (N128 >> 64 || ((unsigned __int128)2 * P * N128) >> 64) return NTF_EINVAL;
+    if (N_out) *N_out = (uint64_t)N128;
+    return NTF_OK;
+}
+
+int auc_open(hipStream_t st, const uint32_t* pos_keys, size_t n_pos, int64_t n, int64_t M, AucState** out) {
+    uint64_t N = 0;
+    if (int r = auc_check(n_pos, n, M, &N)) return r;
+    AucState* s = new AucState;
+    s->P = n_pos; s->N = N; s->total = (unsigned __int128)n * M;
+    std::vector<uint32_t>& v = s->v;
+    v.assign(pos_keys, pos_keys + n_pos);
+    std::sort(v.begin(), v.end());
+    size_t G = 0;
+    for (size_t i = 0; i < v.size(); ++i) {
+        if (G && v[G - 1] == v[i]) { ++s->pos_eq[G - 1]; continue; }
+        v[G++] = v[i]; s->pos_eq.push_back(1);
+    }
+    v.resize(G);
+    while (G / s->stride > (size_t)AUC_PIVOTS) s->stride <<= 1;
+    s->S = (uint32_t)(G / s->stride);
+    std::vector<uint32_t> piv(s->S);
+    for (uint32_t i = 0; i < s->S; ++i) piv[i] = v[(size_t)(i + 1) * s->stride - 1];
+    if (s->S) for (s->step0 = 1; s->step0 * 2 <= s->S; s->step0 <<= 1) {}
+    const size_t nb = 2 * G + 1;
+    s->lds_hist = nb <= (size_t)AUC_LDS_BUCKETS;
+    auto put = [](uint32_t** d, const void* host, size_t bytes) {
+        return hipMalloc((void**)d, bytes ? bytes : 16) == hipSuccess && (!bytes || hipMemcpy(*d, host, bytes, hipMemcpyHostToDevice) == hipSuccess);
+    };
+    if (!put(&s->dv, v.data(), G * 4) || !put(&s->dpiv, piv.data(), (size_t)s->S * 4) || hipMalloc((void**)&s->dcnt, nb * 8) != hipSuccess ||
+        hipMalloc((void**)&s->dflag, 16) != hipSuccess) { auc_free(s); return NTF_ENOMEM; }
+    if (hipMemsetAsync(s->dcnt, 0, nb * 8, st) != hipSuccess || hipMemsetAsync(s->dflag, 0, 4, st) != hipSuccess) { auc_free(s); return NTF_EHIP; }
+    *out = s;
+    return NTF_OK;
+}
+
+// queues one k_auc_count pass over x [L] (device, 16-byte aligned) on `st`
+int auc_count(AucState* s, hipStream_t st, const float* x, int64_t L) {
+    if (L <= 0) return NTF_OK;
+    // (a workgroup's LDS counters are 32-bit: it sees at most L / blocks + 1024 scores of a chunk, far below 2^32 for any chunk that fits in HBM)
+    const int64_t want = ((L >> 2) + 2 * AUC_THREADS - 1) / (2 * AUC_THREADS);
+    const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>(want, 1), AUC_MAX_BLOCKS);
+    const uint32_t G = (uint32_t)s->v.size();
+    if (s->lds_hist)
+        hipLaunchKernelGGL(k_auc_count<true>, dim3(blocks), dim3(AUC_THREADS), 0, st, (const uint32_t*)x, L, (const uint32_t*)s->dv, G,
+                           (const uint32_t*)s->dpiv, s->S, s->step0, s->stride, s->dcnt, s->dflag);
+    else
+        hipLaunchKernelGGL(k_auc_count<false>, dim3(blocks), dim3(AUC_THREADS), 0, st, (const uint32_t*)x, L, (const uint32_t*)s->dv, G,
+                           (const uint32_t*)s->dpiv, s->S, s->step0, s->stride, s->dcnt, s->dflag);
+    return hipGetLastError() == hipSuccess ? NTF_OK : NTF_EHIP;
+}
+
+// waits for the passes queued on `st`, then finishes in integers.  NTF_EINVAL: a NaN score.  NTF_EHIP: a positive that is not among the counted scores, or
+// scores counted that are not exactly n * M - for scores the caller produced twice (ntf_score_rows, dense), a second production that was not bit-identical.
+int auc_finish(AucState* s, hipStream_t st, uint64_t implicit_zeros, uint64_t out_counts[3], double* out_auc) {
+    const std::vector<uint32_t>& v = s->v;
+    const size_t G = v.size(), nb = 2 * G + 1;
+    std::vector<uint64_t> cnt(nb);
+    uint32_t flag = 0;
+    if (hipStreamSynchronize(st) != hipSuccess) return NTF_EHIP;
+    if (hipMemcpy(cnt.data(), s->dcnt, nb * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&flag, s->dflag, 4, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
+    if (flag) return NTF_EINVAL;                                                           // a NaN score
+    if (implicit_zeros) {
+        uint32_t nan = 0;
+        const uint32_t kz = auc_key(0u, nan);
+        const size_t g = std::lower_bound(v.begin(), v.end(), kz) - v.begin();
+        cnt[2 * g + ((g < G && v[g] == kz) ? 1 : 0)] += implicit_zeros;
+    }
+    // cnt[2 g] = all scores strictly between v[g - 1] and v[g], cnt[2 g + 1] = all scores equal to v[g], the positives among them included
+    unsigned __int128 u2 = 0, below = 0, seen = 0;
+    for (size_t g = 0; g < G; ++g) {
+        if (cnt[2 * g + 1] < s->pos_eq[g]) return NTF_EHIP;                                // (cannot happen: every positive is one of the scores)
+        const uint64_t neg_eq = cnt[2 * g + 1] - s->pos_eq[g];
+        below += cnt[2 * g];
+        u2 += (unsigned __int128)s->pos_eq[g] * (2 * below + neg_eq);
+        below += neg_eq;
+        seen += (unsigned __int128)cnt[2 * g] + cnt[2 * g + 1];
+    }
+    seen += cnt[2 * G];
+    if (seen != s->total || u2 >> 64) return NTF_EHIP;                                     // (every score was counted exactly once)
+    out_counts[0] = s->P; out_counts[1] = s->N; out_counts[2] = (uint64_t)u2;
+    *out_auc = (double)(uint64_t)u2 / (2.0 * (double)s->P * (double)s->N);
+    return NTF_OK;
+}
+
 }  // namespace ntf
 
 using namespace ntf;
@@ -143,41 +306,19 @@ bool read_truth(int64_t n, int64_t M, const int64_t* t_indptr, const int32_t* t_
     return true;
 }
 
-// Everything behind the positives' scores: the key table, the stream over `n_chunks` uploads, the integer finish.
+// Everything behind the positives' scores: the key table, the stream over `n_chunks` uploads, the integer finish (auc_open / auc_count / auc_close below).
 // next_chunk(k, dev, &count) uploads chunk k into `dev` and reports its number of scores.  implicit_zeros: scores of 0.0 that are not in any chunk.
 template <class Upload>
-int auc_run(int device, const std::vector<uint32_t>& pos_keys, unsigned __int128 total, uint64_t implicit_zeros, size_t stage_bytes, int64_t n_chunks,
+int auc_run(int device, const std::vector<uint32_t>& pos_keys, int64_t n, int64_t M, uint64_t implicit_zeros, size_t stage_bytes, int64_t n_chunks,
             Upload next_chunk, uint64_t out_counts[3], double* out_auc) {
-    const uint64_t P = pos_keys.size();
-    if (P == 0 || (unsigned __int128)P >= total) return NTF_EINVAL;                       // one class only
-    const unsigned __int128 N128 = total - P;
-    if (N128 >> 64 || ((unsigned __int128)2 * P * N128) >> 64) return NTF_EINVAL;
-    const uint64_t N = (uint64_t)N128;
-
-    std::vector<uint32_t> v(pos_keys);
-    std::sort(v.begin(), v.end());
-    std::vector<uint64_t> pos_eq;
-    size_t G = 0;
-    for (size_t i = 0; i < v.size(); ++i) {
-        if (G && v[G - 1] == v[i]) { ++pos_eq[G - 1]; continue; }
-        v[G++] = v[i]; pos_eq.push_back(1);
-    }
-    v.resize(G);
-    uint32_t stride = 1;
-    while (G / stride > (size_t)AUC_PIVOTS) stride <<= 1;
-    const uint32_t S = (uint32_t)(G / stride);
-    std::vector<uint32_t> piv(S);
-    for (uint32_t i = 0; i < S; ++i) piv[i] = v[(size_t)(i + 1) * stride - 1];
-    uint32_t step0 = 0;
-    if (S) for (step0 = 1; step0 * 2 <= S; step0 <<= 1) {}
-    const size_t nb = 2 * G + 1;
-
+    if (int r0 = auc_check(pos_keys.size(), n, M, nullptr)) return r0;
     if (hipSetDevice(device) != hipSuccess) return NTF_EHIP;
-    DevBuf dv, dpiv, dcnt, dflag, dx;
-    if (!dv.put(v.data(), G * 4) || !dpiv.put(piv.data(), (size_t)S * 4) || !dcnt.alloc(nb * 8) || !dflag.alloc(4) || !dx.alloc((stage_bytes + 15) & ~(size_t)15))
-        return NTF_ENOMEM;
-    if (hipMemset(dcnt.p, 0, nb * 8) != hipSuccess || hipMemset(dflag.p, 0, 4) != hipSuccess) return NTF_EHIP;
-    const bool lds_hist = nb <= (size_t)AUC_LDS_BUCKETS;
+    AucState* s = nullptr;
+    int r = auc_open(nullptr, pos_keys.data(), pos_keys.size(), n, M, &s);
+    if (r) return r;
+    struct Guard { AucState* s; ~Guard() { auc_free(s); } } guard{s};
+    DevBuf dx;
+    if (!dx.alloc((stage_bytes + 15) & ~(size_t)15)) return NTF_ENOMEM;
     double upload_ms = 0.0, kernel_ms = 0.0;                                               // NTF_AUC_TIMING=1: reported on stderr (profiles/auc_time.py)
     int64_t streamed = 0;
     for (int64_t k = 0; k < n_chunks; ++k) {
@@ -188,47 +329,14 @@ int auc_run(int device, const std::vector<uint32_t>& pos_keys, unsigned __int128
         if (L <= 0) continue;
         streamed += L;
         t0 = std::chrono::steady_clock::now();
-        // (a workgroup's LDS counters are 32-bit: it sees at most L / blocks + 1024 scores of a chunk, far below 2^32 for any chunk that fits in HBM)
-        const int64_t want = ((L >> 2) + 2 * AUC_THREADS - 1) / (2 * AUC_THREADS);
-        const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>(want, 1), AUC_MAX_BLOCKS);
-        if (lds_hist)
-            hipLaunchKernelGGL(k_auc_count<true>, dim3(blocks), dim3(AUC_THREADS), 0, 0, (const uint32_t*)dx.p, L, (const uint32_t*)dv.p, (uint32_t)G,
-                               (const uint32_t*)dpiv.p, S, step0, stride, (unsigned long long*)dcnt.p, (uint32_t*)dflag.p);
-        else
-            hipLaunchKernelGGL(k_auc_count<false>, dim3(blocks), dim3(AUC_THREADS), 0, 0, (const uint32_t*)dx.p, L, (const uint32_t*)dv.p, (uint32_t)G,
-                               (const uint32_t*)dpiv.p, S, step0, stride, (unsigned long long*)dcnt.p, (uint32_t*)dflag.p);
-        if (hipGetLastError() != hipSuccess) return NTF_EHIP;
+        if ((r = auc_count(s, nullptr, (const float*)dx.p, L))) return r;
         if (hipStreamSynchronize(nullptr) != hipSuccess) return NTF_EHIP;                  // the next upload reuses the staging buffer
         kernel_ms += ms_since(t0);
     }
     if (const char* t = std::getenv("NTF_AUC_TIMING"); t && t[0] == '1')
         std::fprintf(stderr, "ntf_auc: %lld scores in %lld chunk(s), G = %zu (%s counters): upload %.3f ms, kernel %.3f ms (launch + wait; %.1f GB/s of scores)\n",
-                     (long long)streamed, (long long)n_chunks, G, lds_hist ? "LDS" : "global", upload_ms, kernel_ms, kernel_ms > 0 ? streamed * 4e-6 / kernel_ms : 0.0);
-    std::vector<uint64_t> cnt(nb);
-    uint32_t flag = 0;
-    if (hipMemcpy(cnt.data(), dcnt.p, nb * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&flag, dflag.p, 4, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
-    if (flag) return NTF_EINVAL;                                                           // a NaN score
-    if (implicit_zeros) {
-        uint32_t nan = 0;
-        const uint32_t kz = auc_key(0u, nan);
-        const size_t g = std::lower_bound(v.begin(), v.end(), kz) - v.begin();
-        cnt[2 * g + ((g < G && v[g] == kz) ? 1 : 0)] += implicit_zeros;
-    }
-    // cnt[2 g] = all scores strictly between v[g - 1] and v[g], cnt[2 g + 1] = all scores equal to v[g], the positives among them included
-    unsigned __int128 u2 = 0, below = 0, seen = 0;
-    for (size_t g = 0; g < G; ++g) {
-        if (cnt[2 * g + 1] < pos_eq[g]) return NTF_EHIP;                                   // (cannot happen: every positive is one of the scores)
-        const uint64_t neg_eq = cnt[2 * g + 1] - pos_eq[g];
-        below += cnt[2 * g];
-        u2 += (unsigned __int128)pos_eq[g] * (2 * below + neg_eq);
-        below += neg_eq;
-        seen += (unsigned __int128)cnt[2 * g] + cnt[2 * g + 1];
-    }
-    seen += cnt[2 * G];
-    if (seen != total || u2 >> 64) return NTF_EHIP;                                        // (every score was counted exactly once)
-    out_counts[0] = P; out_counts[1] = N; out_counts[2] = (uint64_t)u2;
-    *out_auc = (double)(uint64_t)u2 / (2.0 * (double)P * (double)N);
-    return NTF_OK;
+                     (long long)streamed, (long long)n_chunks, s->v.size(), s->lds_hist ? "LDS" : "global", upload_ms, kernel_ms, kernel_ms > 0 ? streamed * 4e-6 / kernel_ms : 0.0);
+    return auc_finish(s, nullptr, implicit_zeros, out_counts, out_auc);
 }
 }  // namespace
 
@@ -257,7 +365,7 @@ extern "C" int ntf_auc_micro_dense(int device, const float* scores, int64_t n, i
         // rows land back to back on the device: the padding behind a row is never read, and every chunk starts 16-byte aligned
         return hipMemcpy2D(dev, (size_t)M * 4, scores + r0 * ld, (size_t)ld * 4, (size_t)M * 4, (size_t)nr, hipMemcpyHostToDevice) == hipSuccess;
     };
-    return auc_run(device, keys, (unsigned __int128)n * M, 0, (size_t)rows_per_chunk * M * 4, n_chunks, upload, out_counts, out_auc);
+    return auc_run(device, keys, n, M, 0, (size_t)rows_per_chunk * M * 4, n_chunks, upload, out_counts, out_auc);
 }
 
 extern "C" int ntf_auc_micro_csr(int device, const int64_t* s_indptr, const int32_t* s_indices, const float* s_values, int64_t n, int64_t M,
@@ -296,5 +404,5 @@ extern "C" int ntf_auc_micro_csr(int device, const int64_t* s_indptr, const int3
     };
     const unsigned __int128 total = (unsigned __int128)n * M;
     if ((total - (unsigned __int128)nnz) >> 64) return NTF_EINVAL;
-    return auc_run(device, keys, total, (uint64_t)(total - (unsigned __int128)nnz), (size_t)per_chunk * 4, n_chunks, upload, out_counts, out_auc);
+    return auc_run(device, keys, n, M, (uint64_t)(total - (unsigned __int128)nnz), (size_t)per_chunk * 4, n_chunks, upload, out_counts, out_auc);
 }

@@ -2008,6 +2008,126 @@ extern "C" int ntf_forward_topk(ntf_engine* e, const int64_t* rows, int32_t B, i
     return copy_unc(e, B, pred_unc, model_unc);
 }
 
+// ------------------------------------------------------------------------------------------ scoring a prediction set inside the engine
+namespace {
+// device / AUC resources of one ntf_score_rows call
+struct ScoreBufs {
+    int64_t *rows = nullptr, *slot = nullptr;
+    float *vals = nullptr, *metrics = nullptr;
+    int32_t* idx = nullptr;
+    uint32_t *keys = nullptr, *nan = nullptr;
+    AucState* auc = nullptr;
+    ~ScoreBufs() { hipFree(rows); hipFree(slot); hipFree(vals); hipFree(metrics); hipFree(idx); hipFree(keys); hipFree(nan); auc_free(auc); }
+};
+}  // namespace
+
+// include/opentf_amd.h.  Top-K mode: one sweep of inference into an [n, K] store, everything else from the store.  Dense mode: sweep 1 gathers the positives' keys
+// and the ranked lists, sweep 2 replays the same steps (the range fallback's idiom: e->step back to the first step, same generator keys) and counts Pbuf batch by
+// batch - no [n, M] store.  The outputs are written behind the last check only.
+extern "C" int ntf_score_rows(ntf_engine* e, const int64_t* rows, int64_t n, int32_t B, int32_t nmc, int32_t K, const int32_t* cutoffs, int32_t n_cut,
+                              float* out_metrics, uint64_t out_counts[3], double* out_auc, int32_t K_out, float* out_vals, int32_t* out_idx) {
+    if (!e) return NTF_EINVAL;
+    if (e->ep) FAIL(e, NTF_ESTATE, "score_rows: an expert shard scores nothing on its own (whole-model engines only)");
+    const int M = e->cfg.dims[e->L];
+    const int kcap = std::min(M, 2048);
+    const bool want_auc = out_counts != nullptr, want_out = out_vals || out_idx;
+    if (!rows || n < 1 || B < 1 || B > e->cfg.max_batch || nmc < 1) FAIL(e, NTF_EINVAL, "score_rows: bad rows / n / B / nmc (B must be in [1, max_batch])");
+    if (K < 0 || K > kcap) FAIL(e, NTF_EINVAL, "score_rows: K must be 0 (dense) or in [1, min(M, 2048)]");
+    if (want_auc != (out_auc != nullptr)) FAIL(e, NTF_EINVAL, "score_rows: out_counts and out_auc go together");
+    if (n_cut < 0 || n_cut > 8 || (n_cut > 0 && !cutoffs) || (out_metrics && n_cut < 1)) FAIL(e, NTF_EINVAL, "score_rows: between 1 and 8 cutoffs");
+    int kmax = 0;
+    for (int q = 0; q < n_cut; ++q) { if (cutoffs[q] < 1) FAIL(e, NTF_EINVAL, "score_rows: a cutoff below 1"); kmax = std::max(kmax, cutoffs[q]); }
+    if (K == 0 && kmax > kcap) FAIL(e, NTF_EINVAL, "score_rows: a dense call ranks max(cutoffs) experts per row, at most min(M, 2048)");
+    const int R = K ? K : ((out_metrics || want_out) ? kmax : 0);      // width of the ranked lists kept on the device
+    if (want_out ? (K_out < 1 || K_out > R) : K_out != 0) FAIL(e, NTF_EINVAL, "score_rows: K_out must be in [1, K] (dense: [1, max(cutoffs)]) with out_vals / out_idx, 0 without");
+    if (!out_metrics && !want_auc && !want_out) FAIL(e, NTF_EINVAL, "score_rows: nothing asked for");
+    if (!e->m_indptr) FAIL(e, NTF_ESTATE, "score_rows: member CSR not set");
+    const int64_t limit = row_limit(e);
+    std::vector<int64_t> slot(n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        if (rows[i] < 0 || rows[i] >= limit) FAIL(e, NTF_EINVAL, "score_rows: row id out of range");
+        const int64_t b = e->h_m_indptr[rows[i]], en = e->h_m_indptr[rows[i] + 1];
+        for (int64_t j = b + 1; j < en; ++j) if (e->h_m_indices[j] <= e->h_m_indices[j - 1]) FAIL(e, NTF_EINVAL, "score_rows: truth columns not strictly increasing inside a row");
+        slot[i + 1] = slot[i] + (en - b);
+    }
+    const int64_t n_pos = slot[n];
+    if (want_auc) {   // one class only, or 2 P N past 64 bits
+        const unsigned __int128 total = (unsigned __int128)n * M;
+        if (n_pos == 0 || (unsigned __int128)n_pos >= total || ((unsigned __int128)2 * n_pos * (total - n_pos)) >> 64) FAIL(e, NTF_EINVAL, "score_rows: the AUC needs both classes and 2 P N < 2^64");
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    int r;
+    if ((r = check_ready(e, false))) return r;
+
+    ScoreBufs sb;
+    std::vector<uint32_t> h_keys(want_auc ? n_pos : 0);
+    DM(e, &sb.rows, n);
+    HIPCHK(e, hipMemcpy(sb.rows, rows, (size_t)n * 8, hipMemcpyHostToDevice));
+    if (R) { DM(e, &sb.vals, n * R); DM(e, &sb.idx, n * R); }
+    if (out_metrics) DM(e, &sb.metrics, n * 5 * n_cut);
+    if (want_auc) {
+        DM(e, &sb.slot, n + 1); DM(e, &sb.keys, n_pos); DM(e, &sb.nan, 4);
+        HIPCHK(e, hipMemcpy(sb.slot, slot.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemsetAsync(sb.nan, 0, 4, e->st));
+    }
+    // the positives' keys on the host + the key table; a NaN among them ends the call
+    auto open_auc = [&]() -> int {
+        uint32_t flag = 0;
+        HIPCHK(e, hipMemcpyAsync(h_keys.data(), sb.keys, (size_t)n_pos * 4, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(e, hipMemcpyAsync(&flag, sb.nan, 4, hipMemcpyDeviceToHost, e->st));
+        HIPCHK(e, hipStreamSynchronize(e->st));
+        if (flag) FAIL(e, NTF_EINVAL, "score_rows: a NaN probability");
+        const int rc = auc_open(e->st, h_keys.data(), (size_t)n_pos, n, M, &sb.auc);
+        if (rc) FAIL(e, rc, "score_rows: the AUC key table could not be built");
+        return NTF_OK;
+    };
+
+    const uint64_t step0 = e->step;
+    for (int64_t o = 0; o < n; o += B) {
+        const int b = (int)std::min<int64_t>(B, n - o);
+        if ((r = infer_probs(e, rows + o, b, nmc, nullptr, false))) return r;
+        Scope t(e, F_INFER);
+        if (R) launch_topk_rows(e->st, e->Pbuf, b, M, R, sb.vals + o * R, sb.idx + o * R, nullptr);
+        if (want_auc && K == 0) launch_score_pos_keys_dense(e->st, e->Pbuf, b, M, sb.rows + o, e->m_indptr, e->m_indices, sb.slot + o, sb.keys, sb.nan);
+    }
+    const uint64_t step1 = e->step;
+    uint64_t counts[3] = {0, 0, 0};
+    double auc = 0.0;
+    if (want_auc && K > 0) {
+        { Scope t(e, F_INFER); launch_score_pos_keys_topk(e->st, sb.vals, sb.idx, n, K, sb.rows, e->m_indptr, e->m_indices, sb.slot, sb.keys, sb.nan); }
+        if ((r = open_auc())) return r;
+        if ((r = auc_count(sb.auc, e->st, sb.vals, n * K))) FAIL(e, r, "score_rows: the count launch failed");
+        r = auc_finish(sb.auc, e->st, (uint64_t)n * (uint64_t)(M - K), counts, &auc);
+        if (r) FAIL(e, r, r == NTF_EINVAL ? "score_rows: a NaN probability" : "score_rows: the AUC counts do not add up");
+    } else if (want_auc) {
+        if ((r = open_auc())) return r;
+        e->step = step0;       // sweep 2: the same steps, the same generator keys
+        for (int64_t o = 0; o < n; o += B) {
+            const int b = (int)std::min<int64_t>(B, n - o);
+            if ((r = infer_probs(e, rows + o, b, nmc, nullptr, false))) return r;
+            if ((r = auc_count(sb.auc, e->st, e->Pbuf, (int64_t)b * M))) FAIL(e, r, "score_rows: the count launch failed");
+        }
+        if (e->step != step1) FAIL(e, NTF_EHIP, "score_rows: the second sweep took other steps than the first");
+        r = auc_finish(sb.auc, e->st, 0, counts, &auc);
+        // (NTF_EHIP: a positive's key of sweep 1 is not among the scores of sweep 2, or they are not n * M - the replay was not bit-identical; never an approximate count)
+        if (r) FAIL(e, r, r == NTF_EINVAL ? "score_rows: a NaN probability" : "score_rows: the second inference sweep did not reproduce the first bit for bit; the AUC is refused");
+    }
+    if (out_metrics) { Scope t(e, F_INFER); launch_rank_metrics(e->st, sb.idx, n, R, e->m_indptr, e->m_indices, sb.rows, cutoffs, n_cut, sb.metrics); }
+    HIPCHK(e, hipGetLastError());
+    // nothing has been written so far: the copies below are the call's only stores into the caller's buffers
+    std::vector<float> h_metrics(out_metrics ? (size_t)n * 5 * n_cut : 0), h_vals(out_vals ? (size_t)n * K_out : 0);
+    std::vector<int32_t> h_idx(out_idx ? (size_t)n * K_out : 0);
+    if (out_metrics) HIPCHK(e, hipMemcpyAsync(h_metrics.data(), sb.metrics, h_metrics.size() * 4, hipMemcpyDeviceToHost, e->st));
+    if (out_vals) HIPCHK(e, hipMemcpy2DAsync(h_vals.data(), (size_t)K_out * 4, sb.vals, (size_t)R * 4, (size_t)K_out * 4, (size_t)n, hipMemcpyDeviceToHost, e->st));
+    if (out_idx) HIPCHK(e, hipMemcpy2DAsync(h_idx.data(), (size_t)K_out * 4, sb.idx, (size_t)R * 4, (size_t)K_out * 4, (size_t)n, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (out_metrics) memcpy(out_metrics, h_metrics.data(), h_metrics.size() * 4);
+    if (out_vals) memcpy(out_vals, h_vals.data(), h_vals.size() * 4);
+    if (out_idx) memcpy(out_idx, h_idx.data(), h_idx.size() * 4);
+    if (want_auc) { out_counts[0] = counts[0]; out_counts[1] = counts[1]; out_counts[2] = counts[2]; *out_auc = auc; }
+    return NTF_OK;
+}
+
 extern "C" int ntf_gather_meanpool(ntf_engine* e, const int64_t* rows, int64_t n, float* out_host) {
     if (!e || n < 1) return NTF_EINVAL;
     if (!e->table || !e->s_indptr) FAIL(e, NTF_ESTATE, "skill CSR / table not set");

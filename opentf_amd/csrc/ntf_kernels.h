@@ -2,6 +2,7 @@
 // (ntf_kernels.hip, ntf_fused.hip).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace ntf {
@@ -132,6 +133,23 @@ void launch_sigmoid_acc(hipStream_t st, const float* Act, int64_t n_rows, int M,
 void launch_row_entropy(hipStream_t st, const float* P, int n_rows, int M, float* ent);
 void launch_topk_rows(hipStream_t st, const float* P, int n_rows, int M, int K, float* vals, int32_t* idx, void* workspace);
 size_t topk_workspace_bytes(int n_rows, int M, int K);
+
+// ---- scoring a prediction set where it is produced (ntf_score_rows, ntf_engine.hip): the eval-stage kernels on device-resident data
+// ranking metrics (ntf_metrics.hip, k_rank_metrics) of n ranked lists topk [n, K] against the CSR truth rows rows[i]; every pointer is device memory; n_cut <= 8
+void launch_rank_metrics(hipStream_t st, const int32_t* topk, int64_t n, int K, const int64_t* t_indptr, const int32_t* t_indices, const int64_t* rows,
+                         const int32_t* cutoffs, int n_cut, float* out);
+// the positives' AUC keys (ntf_auc.hip, k_score_pos_keys_*): key j of row i -> keys[slot[i] + j]; *nan_flag raised on a NaN
+void launch_score_pos_keys_dense(hipStream_t st, const float* P, int B, int M, const int64_t* rows, const int64_t* t_indptr, const int32_t* t_indices,
+                                 const int64_t* slot, uint32_t* keys, uint32_t* nan_flag);
+void launch_score_pos_keys_topk(hipStream_t st, const float* vals, const int32_t* idx, int64_t n, int K, const int64_t* rows, const int64_t* t_indptr,
+                                const int32_t* t_indices, const int64_t* slot, uint32_t* keys, uint32_t* nan_flag);
+// micro-averaged ROC AUC over n * M scores (ntf_auc.hip): key table of the positives -> any number of count passes over device-resident scores -> integer finish.
+// All three return NTF_* codes; auc_free releases the state (after auc_finish too).
+struct AucState;
+int auc_open(hipStream_t st, const uint32_t* pos_keys, size_t n_pos, int64_t n, int64_t M, AucState** out);
+int auc_count(AucState* s, hipStream_t st, const float* x /*16-byte aligned*/, int64_t L);
+int auc_finish(AucState* s, hipStream_t st, uint64_t implicit_zeros, uint64_t out_counts[3], double* out_auc);
+void auc_free(AucState* s);
 
 // test hooks for the device generators
 void launch_fill_normal(hipStream_t st, NormalSpec s, int64_t n, float* out);

@@ -94,6 +94,13 @@ __global__ __launch_bounds__(64) void k_skill_coverage(const int32_t* __restrict
     if (lane == 0) for (int q = 0; q < cut.n; ++q) out[i * cut.n + q] = covered[q] / (float)nreq;
 }
 
+void launch_rank_metrics(hipStream_t st, const int32_t* topk, int64_t n, int K, const int64_t* t_indptr, const int32_t* t_indices, const int64_t* rows,
+                         const int32_t* cutoffs, int n_cut, float* out) {
+    Cutoffs c; c.n = n_cut;
+    for (int q = 0; q < MAX_CUT; ++q) c.k[q] = q < n_cut ? cutoffs[q] : 0;
+    hipLaunchKernelGGL(k_rank_metrics, dim3((unsigned)n), dim3(64), 0, st, topk, K, t_indptr, t_indices, rows, c, out);
+}
+
 }  // namespace ntf
 
 using namespace ntf;

@@ -5,6 +5,8 @@ Same function names, arguments and returned DataFrames as the reference (`calcul
 `ntf_rank_metrics` / `ntf_skill_coverage` of libopentf_amd.so.  `calculate_auc_roc` takes the host routes by default (sklearn as in the reference for dense
 predictions, `micro_auc_sparse` for sparse ones); with a device ordinal - `score_predictions` passes one when NTF_AUC_DEVICE=1 - the micro-averaged AUC is
 `micro_auc_device`: one streaming pass over the scores on the GPU (`ntf_auc_micro_dense` / `ntf_auc_micro_csr`), exact in integers.  The curve stays sklearn.
+`score_engine` (NTF_EVAL_ENGINE=1 in `Ntf.evaluate`) returns `score_predictions`' tables without a prediction matrix at all: the model's engine infers the rows and scores them
+where they are (`Engine.score_rows`, `ntf_score_rows`).
 Ties in the scores are ranked by ascending expert id (trec_eval: descending document name) — irrelevant for real-valued model
 outputs, stated here because it is the one place the two can differ.
 """
@@ -76,11 +78,17 @@ def calculate_metrics(Y, Y_, topK=None, per_instance=False, metrics=("P_2,5", "r
     rc = libntf.lib().ntf_rank_metrics(int(device), _ptr(top), n, top.shape[1], _ptr(ip), _ptr(ix), n, None, _ptr(cu), len(cuts), _ptr(out))
     if rc != 0:
         raise libntf.NtfError(f"ntf_rank_metrics failed ({rc})")
+    return _metric_frames(out, cuts, metrics, per_instance)
+
+
+def _metric_frames(out, cuts, metrics, per_instance):
+    """(per-instance table or None, mean table) from k_rank_metrics' [n, 5 * len(cuts)] output over the sorted cutoffs `cuts`"""
+    import pandas as pd
     cols, data = [], []
-    for f in fams:  # the reference's column order: family by family, each over its cutoffs
+    for f in [f for f in TREC if _cutoffs(metrics, f)]:  # the reference's column order: family by family, each over its cutoffs
         for k in _cutoffs(metrics, f):
             cols.append(f"{f}_{k}"); data.append(out[:, TREC.index(f) * len(cuts) + cuts.index(k)].astype(np.float64))
-    df = pd.DataFrame(np.stack(data, axis=1), columns=cols, index=[f"q{i}" for i in range(n)])
+    df = pd.DataFrame(np.stack(data, axis=1), columns=cols, index=[f"q{i}" for i in range(out.shape[0])])
     df_mean = df.mean().to_frame("mean").rename_axis("metrics")
     return (df if per_instance else None), df_mean
 
@@ -172,18 +180,23 @@ def calculate_auc_roc(Y, Y_, curve=False, device=None):
     return auc, None
 
 
-def calculate_skill_coverage(X, Y_, expertskillvecs, per_instance=False, topks="2,5,10", device=0):
+def calculate_skill_coverage(X, Y_, expertskillvecs, per_instance=False, topks="2,5,10", device=0, ranked=None):
+    """`ranked` [n, K] int32 (optional, K >= min(max(topks), experts)): the ranked expert ids themselves, as in `calculate_metrics`; Y_ may then be None."""
     import pandas as pd
     from .. import libntf
-    assert X.shape[0] == Y_.shape[0]
+    assert X.shape[0] == (Y_.shape[0] if ranked is None else np.asarray(ranked).shape[0])
     X = sp.csr_matrix(X); X.sort_indices()
     cov = sp.csr_matrix(expertskillvecs); cov.sort_indices()
     cuts = [int(k) for k in topks.split(",")]
-    n, E = Y_.shape
+    n, E = (Y_.shape if ranked is None else (X.shape[0], cov.shape[0]))
     empty = np.nonzero(np.diff(X.indptr) == 0)[0]
     if len(empty):  # 0 / 0 in the reference (ZeroDivisionError, src/evl/metric.py:69); a NaN here would silently poison the mean
         raise libntf.NtfError(f"skill coverage is undefined for instance {int(empty[0])}: it has no required skill ({len(empty)} such instance(s))")
-    top = _ranked_topk(Y_, min(max(cuts), E))
+    if ranked is not None:
+        top = np.ascontiguousarray(np.asarray(ranked)[:, :min(max(cuts), E)], dtype=np.int32)
+        assert top.shape == (n, min(max(cuts), E)), f"ranked ids {np.asarray(ranked).shape} cover fewer than the {min(max(cuts), E)} ranks the cutoffs need"
+    else:
+        top = _ranked_topk(Y_, min(max(cuts), E))
     out = np.zeros((n, len(cuts)), dtype=np.float32)
     cu = np.ascontiguousarray(cuts, dtype=np.int32)
     xs, xi = np.ascontiguousarray(X.indptr, dtype=np.int64), np.ascontiguousarray(X.indices, dtype=np.int32)
@@ -233,3 +246,75 @@ def score_predictions(teamsvecs, rows, Y_, spec, device=0):
     mean = pd.concat(mean_parts, axis=0) if mean_parts else pd.DataFrame(columns=["mean"])
     mean.index.name = "metrics"
     return inst, mean, roc
+
+
+def eval_engine_enabled():
+    """NTF_EVAL_ENGINE=1 (read per call, off by default): `Ntf.evaluate` scores a model's predictions inside its engine (`score_engine`) instead of reading `.pred` files"""
+    return os.environ.get("NTF_EVAL_ENGINE", "0") == "1"
+
+
+def _engine_plan(spec, M):
+    """How `score_engine` asks `Engine.score_rows` for what `spec` wants at M experts: (K, cutoffs of the call, K_out, reason).  K >= 1: the top-K-sparsified
+    prediction test() writes with that topK, 0: the dense one.  `reason` (a string; the rest is None then) says why the spec stays with the file route."""
+    if spec.auc == "aucroc+":
+        return None, None, None, "aucroc+ keeps the ROC curve, which stays with sklearn"
+    topK = int(spec.topK) if spec.topK else 0
+    K = topK if 0 < topK < M else 0                 # test(): a topK of M or more, or none, writes the dense matrix
+    if K > 2048:
+        return None, None, None, f"topK = {K} is above the 2048 ranks the device ranks per row"
+    cap = min(M, 2048)
+    trec = sorted({k for f in TREC for k in _cutoffs(spec.trec, f)})
+    skc = [int(k) for k in spec.skc.replace("skill_coverage_", "").split(",")] if spec.skc else []
+    k_skc = min(max(skc), M) if skc else 0
+    cuts = list(trec)
+    if K == 0:
+        if trec and max(trec) > cap:
+            return None, None, None, f"a dense prediction is ranked {cap} deep at most, the cutoffs ask for {max(trec)}"
+        if k_skc and (not cuts or k_skc > max(cuts)): cuts = sorted(set(cuts) | {k_skc})     # the ranked list of a dense call is max(cutoffs) wide
+        if cuts and max(cuts) > cap:
+            return None, None, None, f"a dense prediction is ranked {cap} deep at most, skill coverage asks for {k_skc}"
+    elif k_skc > K:
+        return None, None, None, f"skill coverage over {k_skc} ranks needs more than the {K} stored experts of a row"
+    if len(cuts) > 8:
+        return None, None, None, "more than 8 distinct cutoffs in one call"
+    return K, cuts, k_skc, None
+
+
+def score_engine(engine, teamsvecs, rows, spec, nmc, batch, device=0):
+    """`score_predictions` without a prediction matrix: the engine (its parameters loaded, its seed set by the caller) infers `rows` in batches of `batch` and scores
+    them where they are (`Engine.score_rows`: ranking metrics, exact integer micro AUC); the ranked ids come back only when the spec asks for skill coverage, which
+    `ntf_skill_coverage` then computes from them.  Same (per-instance table, mean table, None) triple, column and row order as `score_predictions` on the `.pred`
+    file test() writes with topK = spec.topK.  Raises for a spec `_engine_plan` leaves to the file route."""
+    import pandas as pd
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+    member = teamsvecs["member"]
+    M = member.shape[1]
+    K, cuts, k_out, reason = _engine_plan(spec, M)
+    if reason:
+        raise ValueError(f"score_engine: {reason}")
+    if spec.auc:
+        P = int((sp.csr_matrix(member[rows]).data != 0).sum())
+        if P == 0 or P == len(rows) * M:
+            raise ValueError(_ONE_CLASS)
+    res = engine.score_rows(rows, batch, nmc=nmc, K=K, cutoffs=cuts, auc=bool(spec.auc), K_out=k_out)
+    inst_parts, mean_parts = [], []
+    if spec.trec:
+        trec = sorted({k for f in TREC for k in _cutoffs(spec.trec, f)})
+        out = res.metrics
+        if cuts != trec:     # a cutoff added for the width of the ranked list: its columns are dropped
+            keep = [m * len(cuts) + cuts.index(k) for m in range(5) for k in trec]
+            out = np.ascontiguousarray(out[:, keep])
+        df, df_mean = _metric_frames(out, trec, spec.trec, spec.per_instance)
+        inst_parts.append(df); mean_parts.append(df_mean)
+    if spec.auc:
+        mean_parts.append(pd.DataFrame({"mean": [res.auc]}, index=pd.Index(["aucroc"], name="metrics")))
+    if spec.skc:
+        X = teamsvecs["skill"] if sp.issparse(teamsvecs["skill"]) else teamsvecs["original_skill"]
+        df, df_mean = calculate_skill_coverage(X[rows], None, teamsvecs["skillcoverage"], spec.per_instance, topks=spec.skc.replace("skill_coverage_", ""),
+                                               device=device, ranked=res.idx)
+        inst_parts.append(df); mean_parts.append(df_mean)
+    inst_parts = [d.reset_index(drop=True) for d in inst_parts if d is not None and not d.empty]
+    inst = pd.concat(inst_parts, axis=1) if inst_parts else pd.DataFrame()
+    mean = pd.concat(mean_parts, axis=0) if mean_parts else pd.DataFrame(columns=["mean"])
+    mean.index.name = "metrics"
+    return inst, mean, None

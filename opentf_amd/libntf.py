@@ -12,7 +12,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-NTF_ABI_VERSION = 1
+NTF_ABI_VERSION = 2
 NTF_MAX_LAYERS = 8
 NTF_MC_MAX_GROUP = 16     # Monte-Carlo passes per fused-MC launch at most (include/opentf_amd.h)
 NTF_MC_TILE_GROUP = 4     # 32-expert tiles a workgroup of that kernel carries across the passes
@@ -103,6 +103,7 @@ SYMBOLS = {
     "ntf_skill_coverage": (C.c_int, [C.c_int, _P, _I64, _I32, _P, _P, _I64, _P, _P, _P, _I64, _P, _I32, _P]),
     "ntf_auc_micro_dense": (C.c_int, [C.c_int, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
     "ntf_auc_micro_csr": (C.c_int, [C.c_int, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
+    "ntf_score_rows": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _P, _P]),
     "ntf_skill_cooccurrence": (C.c_int, [C.c_int, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "ntf_csr_result_fetch": (C.c_int, [_P, _P, _P, _P, _P]),
     "ntf_csr_result_free": (None, [_P]),
@@ -178,6 +179,14 @@ def gemm_f32(m, n, k, A, sam, sak, B, sbk, sbn, C_, ldc, stream=None):
     rc = lib().ntf_k_gemm_f32(stream, int(m), int(n), int(k), A, int(sam), int(sak), B, int(sbk), int(sbn), C_, int(ldc))
     if rc != 0:
         raise NtfError(f"ntf_k_gemm_f32 failed ({rc})")
+
+
+class ScoreResult:
+    """what `Engine.score_rows` returns; a field that was not asked for is None"""
+    __slots__ = ("metrics", "counts", "auc", "vals", "idx")
+
+    def __init__(self, metrics, counts, auc, vals, idx):
+        self.metrics, self.counts, self.auc, self.vals, self.idx = metrics, counts, auc, vals, idx
 
 
 class Engine:
@@ -562,6 +571,21 @@ class Engine:
         mu = np.empty(B, dtype=np.float32) if uncertainty else None
         self._ck(lib().ntf_forward_topk(self._h, _ptr(r), B, int(nmc), int(K), _ptr(vals), _ptr(idx), _ptr(pu), _ptr(mu)))
         return (vals, idx, pu, mu) if uncertainty else (vals, idx)
+
+    def score_rows(self, rows, batch, nmc=1, K=0, cutoffs=(), auc=False, K_out=0):
+        """ntf_score_rows: the prediction set `rows`, inferred in batches of `batch`, scored on the device against the resident member CSR.  K >= 1: the
+        top-K-sparsified prediction (what test() writes with topK = K), K == 0: the dense one.  -> ScoreResult: metrics [n, 5 * len(cutoffs)] f32 in
+        ntf_rank_metrics' layout (None without cutoffs), counts (P, N, U2) as Python ints and auc = U2 / (2 P N) (None unless auc), vals / idx [n, K_out]
+        (None unless K_out).  Takes the generator steps the forward / forward_topk loop over the same batches would take."""
+        r = self._rows(rows); n = len(r)
+        cu = np.ascontiguousarray(np.asarray(cutoffs, dtype=np.int32).reshape(-1))
+        metrics = np.zeros((n, 5 * len(cu)), dtype=np.float32) if len(cu) else None
+        counts, a = (np.zeros(3, dtype=np.uint64), C.c_double()) if auc else (None, None)
+        vals = np.zeros((n, int(K_out)), dtype=np.float32) if K_out else None
+        idx = np.zeros((n, int(K_out)), dtype=np.int32) if K_out else None
+        self._ck(lib().ntf_score_rows(self._h, _ptr(r), n, int(batch), int(nmc), int(K), _ptr(cu) if len(cu) else None, len(cu), _ptr(metrics), _ptr(counts),
+                                      C.byref(a) if auc else None, int(K_out), _ptr(vals), _ptr(idx)))
+        return ScoreResult(metrics, tuple(int(c) for c in counts) if auc else None, a.value if auc else None, vals, idx)
 
     def gather_meanpool(self, rows=None, n=None, to_host=True):
         r = None if rows is None else self._rows(rows)

@@ -57,6 +57,12 @@ def dist_rank():
     return d.get_rank() if d.is_available() and d.is_initialized() else 0
 
 
+def _dist_world():
+    import torch
+    d = torch.distributed
+    return d.get_world_size() if d.is_available() and d.is_initialized() else 1
+
+
 def _dist_barrier():
     import torch
     d = torch.distributed
@@ -95,6 +101,19 @@ def _pred_jobs(output, splits, on_train, per_epoch):
             epoch_files = [(int(m.group(1)), n) for n in names for m in [re.match(rf"f{k}\.{pred_set}\.e(\d+)\.pred$", n)] if m]
             for _, n in sorted(epoch_files):
                 yield _PredJob(pred_set, k, f"{output}/{n}", False)
+
+
+def _ckpt_jobs(output, splits, on_train, per_epoch, names=None):
+    """the same jobs from the checkpoints learn() left, as test() enumerates them (`f{k}.pt`, with per_epoch also `f{k}.e{e}.pt`): (job, checkpoint path) pairs in
+    `_pred_jobs`' order, `job.path` being the prediction file test() writes for that checkpoint and set - the stem of the csv files, whether or not it exists"""
+    import re
+    names = (os.listdir(output) if names is None else list(names)) if per_epoch else []
+    for pred_set in (("test", "train", "valid") if on_train else ("test",)):
+        for k in splits["folds"].keys():
+            yield _PredJob(pred_set, k, f"{output}/f{k}.{pred_set}.pred", True), f"{output}/f{k}.pt"
+            epochs = sorted({int(m.group(1)) for n in names for m in [re.match(rf"f{k}\.e(\d+)\.pt$", n)] if m})
+            for e in epochs:
+                yield _PredJob(pred_set, k, f"{output}/f{k}.{pred_set}.e{e}.pred", False), f"{output}/f{k}.e{e}.pt"
 
 
 def _read_pred(path):
@@ -145,7 +164,9 @@ class Ntf:
         """Eval stage: scores the `.pred` files test() wrote and leaves the files the reference's stage leaves (src/mdl/ntf.py:32-92): per prediction file
         `<file>.eval.mean.csv` (+ `.eval.instance.csv`, `.eval.roc.pkl`), per prediction set `{set}.pred.eval.mean.csv` (mean / std over the folds' final files) and
         `{set}.pred.eval.instance_mean.csv`.  A thin driver: `_pred_jobs` lists the files, `evl.metric.score_predictions` does the arithmetic (rank metrics and skill
-        coverage on the device), `_FoldTable` keeps what the set-level files need.  Mounted in the reference tree the plugin inherits the reference's own evaluate()
+        coverage on the device), `_FoldTable` keeps what the set-level files need.  With NTF_EVAL_ENGINE=1 in the environment (read per call, off by default) a model that
+        owns an engine scores every checkpoint `_ckpt_jobs` lists inside the engine instead (`evl.metric.score_engine`: inference plus a few kernels per checkpoint, no
+        `.pred` file read, sorted or uploaded) and writes the same csv files.  Mounted in the reference tree the plugin inherits the reference's own evaluate()
         instead."""
         from ..evl import metric
         assert os.path.isdir(self.output), f"No folder for {self.output} exist!"
@@ -153,9 +174,20 @@ class Ntf:
             _dist_barrier(); return
         spec = metric.EvalSpec.from_cfg(evalcfg)
         tables = {}
-        for job in _pred_jobs(self.output, splits, bool(cfg_get(evalcfg, "on_train")), bool(cfg_get(evalcfg, "per_epoch"))):
+        on_train, per_epoch = bool(cfg_get(evalcfg, "on_train")), bool(cfg_get(evalcfg, "per_epoch"))
+        engine = self._eval_engine(teamsvecs, spec) if metric.eval_engine_enabled() else None     # NTF_EVAL_ENGINE=1, read per call
+        jobs = _ckpt_jobs(self.output, splits, on_train, per_epoch) if engine is not None else ((j, None) for j in _pred_jobs(self.output, splits, on_train, per_epoch))
+        loaded = None
+        for job, ckpt in jobs:
             rows = splits["test"] if job.pred_set == "test" else splits["folds"][job.fold][job.pred_set]
-            inst, mean, roc = metric.score_predictions(teamsvecs, rows, _read_pred(job.path), spec)
+            if engine is not None:      # no prediction file: the checkpoint's own inference, scored where it is produced
+                if ckpt != loaded:
+                    import torch
+                    engine.load_state_dict(torch.load(ckpt, map_location="cpu", weights_only=False)["model_state_dict"]); loaded = ckpt
+                engine.set_seed(int(self.seed or 0), 0)
+                inst, mean, roc = metric.score_engine(engine, teamsvecs, rows, spec, int(cfg_get(self.cfg, "nmc", 1) or 1) if self.is_bayesian else 1, int(cfg_get(self.cfg, "b")))
+            else:
+                inst, mean, roc = metric.score_predictions(teamsvecs, rows, _read_pred(job.path), spec)
             if roc is not None:   # the (fpr, tpr) pair plot_roc consumes (src/mdl/ntf.py:67-69)
                 import pickle
                 with open(f"{job.path}.eval.roc.pkl", "wb") as f: pickle.dump(roc, f)
@@ -164,7 +196,23 @@ class Ntf:
             if job.final: tables.setdefault(job.pred_set, _FoldTable()).add(mean, inst if spec.per_instance else None)
         for pred_set, t in tables.items():
             t.write(f"{self.output}/{pred_set}.pred.eval", len(splits["folds"]))
+        if engine is not None: self._release(engine)
         _dist_barrier()   # rank 0 wrote: the other ranks (waiting at the top) may go on
+
+    def _eval_engine(self, teamsvecs, spec):
+        """The whole-model engine evaluate() scores in under NTF_EVAL_ENGINE=1, or None (one log line says why) when this model or this spec stays with the `.pred`
+        files: a model without an engine of its own, a torchrun run, and what `evl.metric._engine_plan` leaves to the file route (aucroc+, a topK above 2048, ..)."""
+        import logging
+        from ..evl import metric
+        log = logging.getLogger(__name__)
+        reason = None
+        if not callable(getattr(self, "_engine", None)): reason = f"{self.__class__.__name__} owns no engine"
+        elif _dist_world() > 1: reason = "a torchrun run scores its prediction files"
+        else: reason = metric._engine_plan(spec, int(teamsvecs["member"].shape[1]))[3]
+        if reason:
+            log.info(f"NTF_EVAL_ENGINE=1: {reason}; evaluate() reads the .pred files")
+            return None
+        return self._engine(teamsvecs, int(cfg_get(self.cfg, "b")), train=False)[0]
 
     def adila(self, teamsvecs, splits, faircfg):
         raise NotImplementedError("adila() is the reference's fairness stage (src/mdl/ntf.py:108-134); see INTEGRATION.md")
