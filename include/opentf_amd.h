@@ -372,6 +372,28 @@ int  ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32_t negativ
                          const int64_t* order, const double* progress, double* mean_loss, double* device_ms);
 int  ntf_d2v_get(ntf_d2v* h, int what, float* host);
 int  ntf_d2v_set(ntf_d2v* h, int what, const float* host);
+/* ntf_d2v_infer: doc vectors of n documents that were NOT in the corpus, against the handle's FROZEN tables                       src/mdl/emb/d2v.py:96-98 (infer_d2v:
+ * gensim's Doc2Vec.infer_vector as the reference's call leaves its defaults), batched: one wave per query, one launch, the epoch loop inside the kernel.
+ * Queries as CSR over VOCABULARY indices (q_ptr [n+1] int64, q_words int32; the host drops out-of-vocabulary words, as gensim does); ids (nullable: i) = what the
+ * random draws of query i are counted by, so a query's vector does not depend on its place in a batch; init / out [n, d] on the host.  For query i:
+ *   v = init[i]; a = alpha; delta = (alpha - min_alpha) / max(epochs - 1, 1)   (double)
+ *   for e in 0 .. epochs-1, with the Philox key of (seed, e) - the CALL's seed, not the handle's:
+ *     kept = the first 10 000 words whose sample_int >= draw(id, raw position, unit 0, KEEP); per kept position pos: b = draw(id, pos, 0, WINDOW) % window,
+ *     lo = max(0, pos - window + b), hi = min(K, pos + window + 1 - b);
+ *     dm = 1: l1 = (v + sum of wv[kept[m]], m in [lo, hi) \ {pos}) * (1.f / (hi - lo)) in ntf_d2v_train_epoch's order of operations;  dm = 0: l1 = v
+ *       (PV-DBOW: infer_vector leaves train_words = False - the window-word units do not run and take no draws);
+ *     work = 0; targets kept[pos] (label 1), then `negative` draws (id, pos, unit 0, NEG0 / NEG1) through cum_table, a draw equal to the word skipped:
+ *       f = l1 . syn1neg[t], skipped when f <= -6 or f >= 6; work += (label - sigmoid_table(f)) * (float)a * syn1neg[t];   v += work
+ *     (syn1neg and the word vectors are NOT updated: learn_hidden = learn_words = False);  a -= delta (successive subtractions in double, gensim's Python loop)
+ *   out[i] = v.  A query with no kept word in an epoch skips that epoch; a query of zero words returns init[i] bit for bit.
+ * The result is a pure function of (words, id, init row, tables, hyper-parameters, seed): bit-identical under any split of a batch, any position in it, and
+ * serial != 0 (one wave walks the queries in order).  No table is written.  The queries and vectors go through buffers the handle keeps and grows (freed by
+ * ntf_d2v_destroy).  NTF_EINVAL (message: ntf_d2v_last_error) and `out` untouched for: a NULL handle / q_ptr / q_words / init / out, n < 1, q_ptr[0] != 0 or not
+ * monotone, a word index outside [0, n_vocab), window / negative outside what ntf_d2v_train_epoch accepts (window 1..255, dm = 0: 1..127; negative 0..8), dm not
+ * 0 or 1, epochs < 1, a non-finite alpha or min_alpha.  device_ms (nullable): device time of the launch. */
+int  ntf_d2v_infer(ntf_d2v* h, int64_t n, const int64_t* q_ptr, const int32_t* q_words, const int64_t* ids /* nullable */,
+                   int32_t dm, int32_t window, int32_t negative, int32_t epochs, double alpha, double min_alpha, uint64_t seed, int32_t serial,
+                   const float* init /* [n, d] host */, float* out /* [n, d] host */, double* device_ms /* nullable */);
 
 /* device generators behind Flipout's eps / signs (dev_out = device pointers), for statistical tests */
 int ntf_k_fill_normal(void* stream, uint64_t seed, uint64_t step, int layer, int64_t n, float* dev_out);

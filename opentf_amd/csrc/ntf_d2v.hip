@@ -31,6 +31,9 @@ struct ntf_d2v {
     double* d_loss = nullptr;     // [sum of -log terms, number of terms]
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint64_t seed = 0;
+    // ntf_d2v_infer: the queries of the last call (CSR, ids) and their vectors [n, dp] (initial on the way in, inferred on the way out); grown on demand
+    int64_t *q_ptr = nullptr, *q_ids = nullptr; int32_t* q_words = nullptr; float* q_vec = nullptr;
+    int64_t q_cap = 0, q_words_cap = 0;
     std::string err;
 };
 static thread_local std::string g_d2v_create_error;
@@ -55,9 +58,10 @@ struct D2vArgs {
     double* loss;
 };
 
-__device__ __forceinline__ uint4 d2v_draw(const D2vArgs& a, int64_t doc, int pos, int unit, int slot) {
-    return philox4x32(make_uint4((uint32_t)doc, (uint32_t)((uint64_t)doc >> 32), ((uint32_t)pos << 8) | (uint32_t)unit, (uint32_t)slot), make_uint2(a.k0, a.k1));
+__device__ __forceinline__ uint4 d2v_draw(uint32_t k0, uint32_t k1, int64_t doc, int pos, int unit, int slot) {
+    return philox4x32(make_uint4((uint32_t)doc, (uint32_t)((uint64_t)doc >> 32), ((uint32_t)pos << 8) | (uint32_t)unit, (uint32_t)slot), make_uint2(k0, k1));
 }
+__device__ __forceinline__ uint4 d2v_draw(const D2vArgs& a, int64_t doc, int pos, int unit, int slot) { return d2v_draw(a.k0, a.k1, doc, pos, unit, slot); }
 // EXP_TABLE lookup of doc2vec_inner.pyx (the table is built in float32: entry i = sigmoid((i / 1000 * 2 - 1) * 6))
 __device__ __forceinline__ float d2v_sigmoid_table(float f) {
     const int i = (int)((f + D2V_MAX_EXP) * (1000.f / D2V_MAX_EXP / 2.f));
@@ -278,16 +282,138 @@ __global__ __launch_bounds__(256, DW > 0 ? 1 : (NV <= 2 ? 6 : 5)) void k_d2v_epo
     if (a.loss && lane == 0 && lcnt > 0.f) { atomicAdd(a.loss, (double)lsum); atomicAdd(a.loss + 1, (double)lcnt); }
 }
 
+// splitmix64 of (seed, epoch) -> the Philox key of a pass (the trainer's host side; ntf_d2v_infer's epoch loop runs inside its kernel)
+__host__ __device__ inline void d2v_key(uint64_t seed, uint64_t epoch, uint32_t& k0, uint32_t& k1) {
+    uint64_t x = seed ^ (epoch * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull);
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    k0 = (uint32_t)x; k1 = (uint32_t)(x >> 32);
+}
+
+// ---- infer_vector (src/mdl/emb/d2v.py:96-98): the vector of a document that was not in the corpus, trained against FROZEN tables.  gensim's infer_vector is train() on one
+// document with learn_words = learn_hidden = False and train_words = False: the doc vector is the only thing that moves, so every query is independent of every other - no
+// atomics, no store to a table, plain cached loads (d2v_ld's agent scope is for rows other waves add to), and the result is a pure function of (words, id, initial vector,
+// tables, seed) whatever wave runs it.  One wave per query, the vector in registers from the initial row to the final store across ALL epochs of the call.
+struct D2vInferArgs {
+    int64_t n, n_vocab; int d, window, negative, serial, dm, epochs;
+    const int64_t* q_ptr; const int32_t* q_words; const int64_t* ids; const uint32_t *sample_int, *cum_table;
+    const float *wv, *syn1neg; float* vec;      // vec [n, d]: the initial vector in, the inferred one out (a row is read and written by its own wave only)
+    double alpha, delta;                         // alpha of the first epoch; (alpha - min_alpha) / max(epochs - 1, 1)
+    uint64_t seed;
+};
+
+// d2v_unit's two-level search of the cumulative table (bisect_left(cum_table, r % cum_table[-1]) through the LDS level), as a function of its own: folding the trainer's copy
+// into it changes the trainer's register allocation, and the trainer's code is to stay as measured
+__device__ __forceinline__ int d2v_table_search(const uint32_t* cum_table, int64_t n_vocab, const uint32_t* __restrict__ top, int top_n, int top_s, uint32_t rk) {
+    const uint32_t v = rk % cum_table[n_vocab - 1];
+    int blo = 0, bhi = top_n;
+    while (blo < bhi) { const int mid = (blo + bhi) >> 1; if (top[mid] < v) blo = mid + 1; else bhi = mid; }
+    int64_t lo = (int64_t)blo * top_s, hi = min((int64_t)(blo + 1) * top_s, n_vocab);
+    if (blo >= top_n) { lo = n_vocab; hi = n_vocab; }        // (v is below cum_table[-1]: never taken)
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (cum_table[mid] < v) lo = mid + 1; else hi = mid; }
+    return (int)lo;
+}
+
+// d2v_unit's frozen twin: the same draws, targets, order of operations and skips; syn1neg is read, never written
+template <int NV>
+__device__ __forceinline__ void d2v_unit_frozen(const D2vInferArgs& a, uint32_t k0, uint32_t k1, const uint32_t* __restrict__ top, int top_n, int top_s, const float (&x)[NV], int word, float alpha,
+                                                int64_t doc, int pos, int lane, float (&w)[NV]) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) w[k] = 0.f;
+    const uint4 r4 = d2v_draw(k0, k1, doc, pos, 0, SLOT_NEG0 + ((lane >> 2) & 1));
+    const uint32_t rk = (lane & 3) == 0 ? r4.x : (lane & 3) == 1 ? r4.y : (lane & 3) == 2 ? r4.z : r4.w;
+    const int tgt = d2v_table_search(a.cum_table, a.n_vocab, top, top_n, top_s, rk);
+    for (int k = 0; k <= a.negative; ++k) {
+        const int t = __builtin_amdgcn_readfirstlane(k == 0 ? word : __shfl(tgt, k - 1, 64));
+        if (k > 0 && t == word) continue;
+        const float label = k == 0 ? 1.f : 0.f;
+        const float* __restrict__ row = a.syn1neg + (int64_t)t * a.d;
+        float rv[NV], f = 0.f;
+#pragma unroll
+        for (int q = 0; q < NV; ++q) { rv[q] = row[lane + 64 * q]; f += x[q] * rv[q]; }
+        f = wave_reduce_sum(f);
+        if (f <= -D2V_MAX_EXP || f >= D2V_MAX_EXP) continue;
+        const float g = (label - d2v_sigmoid_table(f)) * alpha;
+#pragma unroll
+        for (int q = 0; q < NV; ++q) w[q] += g * rv[q];
+    }
+}
+
+// (the trainer's plain-kernel bounds; a query is a chain of dependent row reads, so what hides the latency is waves per SIMD.  The compiler's report for NV = 1 / 2 / 3 / 4:
+//  63 / 67 / 71 / 72 VGPRs, no spill, no scratch, 20 KiB of LDS a workgroup - 8 / 7 / 7 / 7 waves a SIMD by registers, 8 workgroups a CU by LDS)
+template <int NV>
+__global__ __launch_bounds__(256, NV <= 2 ? 6 : 5) void k_d2v_infer(D2vInferArgs a) {
+    __shared__ int s_kept[4][D2V_RING];
+    __shared__ uint32_t s_top[D2V_TOP];
+    const int lane = threadIdx.x & 63, wv_id = threadIdx.x >> 6;
+    int* kept = s_kept[wv_id];
+    const int top_s = (int)((a.n_vocab + D2V_TOP - 1) / D2V_TOP), top_n = (int)((a.n_vocab + top_s - 1) / top_s);
+    for (int k = threadIdx.x; k < top_n; k += blockDim.x) s_top[k] = a.cum_table[min((int64_t)(k + 1) * top_s, a.n_vocab) - 1];
+    __syncthreads();
+    const int64_t first = a.serial ? 0 : (int64_t)blockIdx.x * 4 + wv_id;
+    const int64_t stride = a.serial ? 1 : (int64_t)gridDim.x * 4;
+    if (a.serial && (blockIdx.x != 0 || wv_id != 0)) return;
+    for (int64_t qi = first; qi < a.n; qi += stride) {
+        const int64_t doc = a.ids ? a.ids[qi] : qi;          // what the draws are counted by: a query's vector does not depend on its place in the batch
+        const int64_t p0 = a.q_ptr[qi];
+        const int L = (int)min(a.q_ptr[qi + 1] - p0, (int64_t)0x7fffffff);
+        float dreg[NV];
+        float* drow = a.vec + qi * a.d;
+#pragma unroll
+        for (int q = 0; q < NV; ++q) dreg[q] = drow[lane + 64 * q];
+        double alpha_d = a.alpha;
+        for (int e = 0; e < a.epochs; ++e) {
+            uint32_t k0, k1;
+            d2v_key(a.seed, (uint64_t)e, k0, k1);
+            const float alpha = (float)alpha_d;
+            int K = 0, base = 0;               // as in k_d2v_epoch: kept words compacted so far (<= D2V_MAX_DOC), raw words scanned so far
+            for (int i = 0;; ++i) {
+                while (K < i + a.window + 1 && base < L && K < D2V_MAX_DOC) {
+                    const int p = base + lane;
+                    int wd = 0; bool keep = false;
+                    if (p < L) { wd = a.q_words[p0 + p]; keep = a.sample_int[wd] >= d2v_draw(k0, k1, doc, p, 0, SLOT_KEEP).x; }
+                    const unsigned long long m = __ballot(keep);
+                    const int at = K + __popcll(m & ((1ull << lane) - 1ull));
+                    if (keep && at < D2V_MAX_DOC) kept[at & (D2V_RING - 1)] = wd;
+                    K = min(K + (int)__popcll(m), D2V_MAX_DOC);
+                    base += 64;
+                    __builtin_amdgcn_wave_barrier();
+                }
+                if (i >= K) break;
+                const int b = (int)(d2v_draw(k0, k1, doc, i, 0, SLOT_WINDOW).x % (uint32_t)a.window), word = __builtin_amdgcn_readfirstlane(kept[i & (D2V_RING - 1)]);
+                float work[NV];
+                if (a.dm) {
+                    const int lo = max(0, i - a.window + b), hi = min(K, i + a.window + 1 - b);
+                    float l1[NV];
+#pragma unroll
+                    for (int q = 0; q < NV; ++q) l1[q] = dreg[q];
+                    for (int m = lo; m < hi; ++m) {
+                        if (m == i) continue;
+                        const float* __restrict__ r = a.wv + (int64_t)__builtin_amdgcn_readfirstlane(kept[m & (D2V_RING - 1)]) * a.d;
+#pragma unroll
+                        for (int q = 0; q < NV; ++q) l1[q] += r[lane + 64 * q];
+                    }
+                    const float inv = 1.f / (float)(hi - lo);
+#pragma unroll
+                    for (int q = 0; q < NV; ++q) l1[q] *= inv;
+                    d2v_unit_frozen<NV>(a, k0, k1, s_top, top_n, top_s, l1, word, alpha, doc, i, lane, work);
+                } else      // PV-DBOW: infer_vector leaves train_words = False - the window-word units do not run (and their draws are not taken)
+                    d2v_unit_frozen<NV>(a, k0, k1, s_top, top_n, top_s, dreg, word, alpha, doc, i, lane, work);
+#pragma unroll
+                for (int q = 0; q < NV; ++q) dreg[q] += work[q];
+            }
+            alpha_d -= a.delta;                // gensim's Python loop: one subtraction in double per epoch
+            __builtin_amdgcn_wave_barrier();   // the next epoch refills the ring from slot 0
+        }
+#pragma unroll
+        for (int q = 0; q < NV; ++q) drow[lane + 64 * q] = dreg[q];
+    }
+}
+
 template <typename T> int dalloc(ntf_d2v* h, T** p, int64_t n) {
     *p = nullptr;
     if (n <= 0) return NTF_OK;
     if (hipMalloc((void**)p, (size_t)n * sizeof(T)) != hipSuccess) { h->err = "hipMalloc failed"; return NTF_ENOMEM; }
     return NTF_OK;
-}
-void d2v_key(uint64_t seed, uint64_t epoch, uint32_t& k0, uint32_t& k1) {
-    uint64_t x = seed ^ (epoch * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull);
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-    k0 = (uint32_t)x; k1 = (uint32_t)(x >> 32);
 }
 }  // namespace
 
@@ -295,7 +421,8 @@ extern "C" void ntf_d2v_destroy(ntf_d2v* h) {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->st) hipStreamSynchronize(h->st);
-    for (void* p : {(void*)h->doc_ptr, (void*)h->words, (void*)h->sample_int, (void*)h->cum_table, (void*)h->dv, (void*)h->wv, (void*)h->syn1neg, (void*)h->order, (void*)h->progress, (void*)h->d_loss})
+    for (void* p : {(void*)h->doc_ptr, (void*)h->words, (void*)h->sample_int, (void*)h->cum_table, (void*)h->dv, (void*)h->wv, (void*)h->syn1neg, (void*)h->order, (void*)h->progress, (void*)h->d_loss,
+                    (void*)h->q_ptr, (void*)h->q_ids, (void*)h->q_words, (void*)h->q_vec})
         if (p) hipFree(p);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -393,6 +520,67 @@ extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32
         DCHK(h, hipMemcpy(l, h->d_loss, 16, hipMemcpyDeviceToHost));
         *mean_loss = l[1] > 0 ? l[0] / l[1] : 0.0;
     }
+    return NTF_OK;
+}
+
+extern "C" int ntf_d2v_infer(ntf_d2v* h, int64_t n, const int64_t* q_ptr, const int32_t* q_words, const int64_t* ids, int32_t dm, int32_t window, int32_t negative, int32_t epochs,
+                             double alpha, double min_alpha, uint64_t seed, int32_t serial, const float* init, float* out, double* device_ms) {
+    if (!h) { g_d2v_create_error = "d2v infer: the handle is NULL"; return NTF_EINVAL; }
+    if (!q_ptr || !q_words || !init || !out) DFAIL(h, NTF_EINVAL, "d2v infer: q_ptr, q_words, init and out are required");
+    if (n < 1) DFAIL(h, NTF_EINVAL, "d2v infer: n < 1");
+    if (window < 1 || window > 255 || (!dm && 2 * window > 254)) DFAIL(h, NTF_EINVAL, "d2v infer: window outside 1..255 (dm = 0: 1..127), as ntf_d2v_train_epoch");
+    if (negative < 0 || negative > 8) DFAIL(h, NTF_EINVAL, "d2v infer: negative outside 0..8");
+    if (dm != 0 && dm != 1) DFAIL(h, NTF_EINVAL, "d2v infer: dm is 0 or 1");
+    if (epochs < 1) DFAIL(h, NTF_EINVAL, "d2v infer: epochs < 1");
+    if (!std::isfinite(alpha) || !std::isfinite(min_alpha)) DFAIL(h, NTF_EINVAL, "d2v infer: alpha / min_alpha not finite");
+    if (q_ptr[0] != 0) DFAIL(h, NTF_EINVAL, "d2v infer: q_ptr[0] != 0");
+    for (int64_t i = 0; i < n; ++i) if (q_ptr[i + 1] < q_ptr[i]) DFAIL(h, NTF_EINVAL, "d2v infer: q_ptr not monotone");
+    const int64_t nw = q_ptr[n];
+    for (int64_t p = 0; p < nw; ++p) if (q_words[p] < 0 || q_words[p] >= h->n_vocab) DFAIL(h, NTF_EINVAL, "d2v infer: word index out of the vocabulary");
+    DCHK(h, hipSetDevice(h->device));
+    DCHK(h, hipStreamSynchronize(h->st));
+    const int64_t dp = h->dp; const int d = h->d;
+    if (n > h->q_cap) {
+        for (void* p : {(void*)h->q_ptr, (void*)h->q_ids, (void*)h->q_vec}) if (p) hipFree(p);
+        h->q_ptr = nullptr; h->q_ids = nullptr; h->q_vec = nullptr; h->q_cap = 0;
+        int rc = NTF_OK;
+        auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
+        A(dalloc(h, &h->q_ptr, n + 1)); A(dalloc(h, &h->q_ids, n)); A(dalloc(h, &h->q_vec, n * dp));
+        if (rc != NTF_OK) return rc;
+        h->q_cap = n;
+    }
+    if (std::max<int64_t>(nw, 1) > h->q_words_cap) {
+        if (h->q_words) hipFree(h->q_words);
+        h->q_words = nullptr; h->q_words_cap = 0;
+        const int rc = dalloc(h, &h->q_words, std::max<int64_t>(nw, 1));
+        if (rc != NTF_OK) return rc;
+        h->q_words_cap = std::max<int64_t>(nw, 1);
+    }
+    DCHK(h, hipMemcpy(h->q_ptr, q_ptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+    if (nw) DCHK(h, hipMemcpy(h->q_words, q_words, (size_t)nw * 4, hipMemcpyHostToDevice));
+    if (ids) DCHK(h, hipMemcpy(h->q_ids, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+    if (dp != d) DCHK(h, hipMemset(h->q_vec, 0, (size_t)n * dp * 4));       // the pad columns zero, as the tables'
+    DCHK(h, hipMemcpy2D(h->q_vec, (size_t)dp * 4, init, (size_t)d * 4, (size_t)d * 4, (size_t)n, hipMemcpyHostToDevice));
+    D2vInferArgs a;
+    a.n = n; a.n_vocab = h->n_vocab; a.d = h->dp; a.window = window; a.negative = negative; a.serial = serial ? 1 : 0; a.dm = dm; a.epochs = epochs;
+    a.q_ptr = h->q_ptr; a.q_words = h->q_words; a.ids = ids ? h->q_ids : nullptr; a.sample_int = h->sample_int; a.cum_table = h->cum_table;
+    a.wv = h->wv; a.syn1neg = h->syn1neg; a.vec = h->q_vec;
+    a.alpha = alpha; a.delta = (alpha - min_alpha) / (double)std::max(epochs - 1, 1); a.seed = seed;
+    const int64_t want = (n + 3) / 4;
+    const dim3 grid(serial ? 1u : (unsigned)std::min<int64_t>(want, 256 * 16)), block(serial ? 64 : 256);
+    if (device_ms) { if (!h->ev0) { DCHK(h, hipEventCreate(&h->ev0)); DCHK(h, hipEventCreate(&h->ev1)); } DCHK(h, hipEventRecord(h->ev0, h->st)); }
+    switch (h->dp / 64) {
+        case 1: hipLaunchKernelGGL(k_d2v_infer<1>, grid, block, 0, h->st, a); break;
+        case 2: hipLaunchKernelGGL(k_d2v_infer<2>, grid, block, 0, h->st, a); break;
+        case 3: hipLaunchKernelGGL(k_d2v_infer<3>, grid, block, 0, h->st, a); break;
+        default: hipLaunchKernelGGL(k_d2v_infer<4>, grid, block, 0, h->st, a); break;
+    }
+    if (device_ms) DCHK(h, hipEventRecord(h->ev1, h->st));
+    hipError_t s = hipGetLastError();
+    if (s != hipSuccess) DFAIL(h, NTF_EHIP, std::string("d2v infer kernel launch: ") + hipGetErrorString(s));
+    DCHK(h, hipStreamSynchronize(h->st));
+    if (device_ms) { float ms = 0.f; DCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
+    DCHK(h, hipMemcpy2D(out, (size_t)d * 4, h->q_vec, (size_t)dp * 4, (size_t)d * 4, (size_t)n, hipMemcpyDeviceToHost));
     return NTF_OK;
 }
 

@@ -120,6 +120,7 @@ SYMBOLS = {
     "ntf_d2v_train_epoch": (C.c_int, [_P, _I32, _I32, _I32, C.c_double, C.c_double, _U64, _I32, _P, _P, _P, _P]),
     "ntf_d2v_get": (C.c_int, [_P, C.c_int, _P]),
     "ntf_d2v_set": (C.c_int, [_P, C.c_int, _P]),
+    "ntf_d2v_infer": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, C.c_double, C.c_double, _U64, _I32, _P, _P, _P]),
     "ntf_k_gemm_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _I64, _I64, _P, _I64, _I64, _P, _I64]),
     "ntf_k_fill_normal": (C.c_int, [_P, _U64, _U64, C.c_int, _I64, _P]),
     "ntf_k_fill_sign": (C.c_int, [_P, _U64, _U64, C.c_int, C.c_int, C.c_int, _P]),
@@ -725,6 +726,35 @@ class Doc2Vec:
                                            _ptr(o) if o is not None else None, _ptr(pr) if pr is not None else None, C.byref(loss) if want_loss else None,
                                            C.byref(ms) if want_ms else None))
         return (loss.value if want_loss else None), (ms.value if want_ms else None)
+
+    @classmethod
+    def from_tables(cls, wv, syn1neg, sample_int, cum_table, device=0):
+        """a handle for `infer` only: trained tables and the vocabulary's two tables, no corpus (one empty document stands in for it)"""
+        wv, s1 = _f32(wv), _f32(syn1neg)
+        if s1.shape != wv.shape:
+            raise NtfError("wv and syn1neg do not have the same shape")
+        net = cls(np.zeros(2, np.int64), np.zeros(1, np.int32), sample_int, cum_table, wv, np.zeros((1, wv.shape[1]), np.float32), device=device)
+        net.set_vectors(cls.WV, wv); net.set_vectors(cls.SYN1NEG, s1)
+        return net
+
+    def infer(self, q_ptr, q_words, init, dm, window, epochs, alpha, min_alpha, seed, negative=5, ids=None, serial=False, want_ms=False):
+        """gensim's infer_vector for a batch of documents that were not in the corpus (ntf_d2v_infer): q_ptr / q_words = the queries as CSR over vocabulary
+        indices, init [n, d] their initial vectors, ids (None: 0..n-1) what each query's draws are counted by.  -> [n, d] (, device ms)"""
+        qp = np.ascontiguousarray(q_ptr, dtype=np.int64); qw = np.ascontiguousarray(q_words, dtype=np.int32)
+        n = len(qp) - 1
+        v0 = _f32(init)
+        if v0.ndim != 2 or v0.shape != (n, self.d):
+            raise NtfError(f"init must be [{n}, {self.d}], got {v0.shape}")
+        if len(qp) and len(qw) < int(qp[-1]):
+            raise NtfError("q_words is shorter than q_ptr[-1]")
+        if len(qw) == 0: qw = np.zeros(1, np.int32)
+        qi = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
+        if qi is not None and len(qi) != n:
+            raise NtfError("ids must hold one id per query")
+        out = np.empty((n, self.d), dtype=np.float32); ms = C.c_double()
+        self._ck(lib().ntf_d2v_infer(self._h, n, _ptr(qp), _ptr(qw), _ptr(qi) if qi is not None else None, int(dm), int(window), int(negative), int(epochs),
+                                     float(alpha), float(min_alpha), int(seed) & (2**64 - 1), int(bool(serial)), _ptr(v0), _ptr(out), C.byref(ms) if want_ms else None))
+        return (out, ms.value) if want_ms else out
 
     def vectors(self, what=0):
         out = np.empty((self.n_docs if what == 0 else self.n_vocab, self.d), dtype=np.float32)

@@ -92,13 +92,41 @@ def build_vocab(words, sample=SAMPLE, ns_exponent=NS_EXPONENT):
     order = seen[np.argsort(-cnt[seen], kind="stable")]
     keys, count = uniq[order], cnt[order].astype(np.int64)
     rank = np.empty(len(uniq), dtype=np.int64); rank[order] = np.arange(len(uniq))
+    sample_int, cum = vocab_tables(count, sample, ns_exponent)
+    return keys, count, sample_int, cum, rank[inv].astype(np.int32)
+
+
+def vocab_tables(count, sample=SAMPLE, ns_exponent=NS_EXPONENT):
+    """build_vocab's two tables from the vocabulary counts alone (a loaded model has `count` but no corpus): -> (sample_int [V] uint32, cum_table [V] uint32)"""
+    count = np.asarray(count, dtype=np.int64)
     total = int(count.sum())
     thr = total if not sample else (sample * total if sample < 1.0 else int(sample * (3 + np.sqrt(5)) / 2))
     p = np.minimum((np.sqrt(count / thr) + 1) * (thr / count), 1.0)
     sample_int = (p * (2 ** 32 - 1)).astype(np.uint32)
     pw = count.astype(np.float64) ** ns_exponent
     cum = np.round(np.cumsum(pw) / pw.sum() * (2 ** 31 - 1)).astype(np.uint32)
-    return keys, count, sample_int, cum, rank[inv].astype(np.int32)
+    return sample_int, cum
+
+
+def query_csr(docs, key_to_index):
+    """documents as lists of word keys -> (q_ptr int64, vocabulary indices int32): unknown keys dropped (as gensim's infer_vector drops them), order kept"""
+    idx = [[key_to_index[x] for x in words if x in key_to_index] for words in docs]
+    ptr = np.concatenate([[0], np.cumsum([len(r) for r in idx])]).astype(np.int64)
+    return ptr, np.asarray([x for r in idx for x in r], dtype=np.int32)
+
+
+def infer_seeds(docs):
+    """infer_vec's seed of a document: crc32 of its words joined by blanks (unknown words included) -> [n] int64"""
+    import zlib
+    return np.asarray([zlib.crc32(" ".join(words).encode()) for words in docs], dtype=np.int64)
+
+
+def infer_init(docs, d):
+    """infer_vec's initial vector of each document: default_rng(crc32(' '.join(words))), the first d floats, * 2 - 1, / d -> [n, d] float32"""
+    out = np.empty((len(docs), d), dtype=np.float32)
+    for i, s in enumerate(infer_seeds(docs).tolist()):
+        out[i] = ((np.random.default_rng(s).random(d, dtype=np.float32) * 2 - 1) / d).astype(np.float32)
+    return out
 
 
 def job_progress(doc_ptr, order=None, batch_words=10000):
@@ -280,6 +308,47 @@ class D2v(T2v):
                     work += np.float32((float(k == 0) - 1.0 / (1.0 + np.exp(-f))) * alpha) * m.syn1neg[t]
                 v = v + work
         return v, m.docvecs.most_similar([v])
+
+    def infer_vecs(self, docs, init=None, ids=None):
+        """infer_vec for a batch, on the device (ntf_d2v_infer: gensim's infer_vector against the frozen tables, one wave per document).  docs: a list of word-key
+        lists (['s1', 's5'], as infer_vec takes), or a (doc_ptr, word ids, key) triple as team_documents returns.  Hyper-parameters from self.model as infer_vec reads
+        them; init (None: infer_vec's own rule per document) [n, d]; ids (None: the crc32 infer_vec seeds with) = what a document's draws are counted by, so its vector is
+        a function of its words and the model, not of its place in the batch.  The random streams are the device's Philox words, not infer_vec's numpy stream:
+        the two routes agree in distribution, not value for value.  -> [n, d] float32"""
+        from ... import libntf
+        m = self.model
+        if isinstance(docs, tuple) and len(docs) == 3 and callable(docs[2]):
+            ptr, words, key = docs
+            ptr = np.asarray(ptr); words = np.asarray(words)
+            docs = [[key(int(w)) for w in words[ptr[i]:ptr[i + 1]]] for i in range(len(ptr) - 1)]
+        docs = [list(words) for words in docs]
+        if getattr(m, "count", None) is None:
+            raise RuntimeError("infer_vec: the loaded Doc2Vec file holds no vocabulary counts (wv.expandos['count']): the negative-sampling table cannot be rebuilt")
+        d = int(m.vector_size)
+        if len(docs) == 0: return np.zeros((0, d), dtype=np.float32)
+        q_ptr, q_words = query_csr(docs, m.wv.key_to_index)
+        init = infer_init(docs, d) if init is None else np.ascontiguousarray(init, dtype=np.float32)
+        ids = infer_seeds(docs) if ids is None else np.asarray(ids, dtype=np.int64)
+        if getattr(self, "_infer_net", None) is None:
+            sample = getattr(m, "sample", None)
+            sample_int, cum_table = vocab_tables(m.count, SAMPLE if sample is None else sample, m.ns_exponent)
+            device = parse_devices(self.device)[0] if getattr(self, "device", None) is not None else 0
+            self._infer_net = libntf.Doc2Vec.from_tables(m.wv.vectors, m.syn1neg, sample_int, cum_table, device=device)
+        seed = getattr(m, "seed", None)
+        return self._infer_net.infer(q_ptr, q_words, init, int(m.dm), int(m.window), int(getattr(m, "epochs", 10)), float(getattr(m, "alpha", ALPHA)), float(m.min_alpha),
+                                     int(seed) if seed is not None else 1, negative=int(m.negative), ids=ids)
+
+    def infer_team_vecs(self, teamsvecs, rows=None, time_indexes=None):
+        """the inductive counterpart of get_dense_vecs(..)[rows]: the documents of those teams under the model's embtype (team_documents), inferred against the frozen
+        tables - [len(rows), d], ready for Engine.set_dense_input"""
+        ptr, words, key = team_documents(teamsvecs, cfg_get(self.cfg, "embtype"), time_indexes)
+        rows = np.arange(len(ptr) - 1) if rows is None else np.asarray(rows, dtype=np.int64)
+        return self.infer_vecs([[key(int(w)) for w in words[ptr[i]:ptr[i + 1]]] for i in rows.tolist()])
+
+    def close(self):
+        """frees the device handle infer_vecs keeps"""
+        if getattr(self, "_infer_net", None) is not None:
+            self._infer_net.close(); self._infer_net = None
 
     @staticmethod
     def natsortvecs(d2v_model_wv):
