@@ -337,8 +337,14 @@ void ntf_csr_result_free(ntf_csr_result* r);
  * nodes, loss = -mean log(sigmoid(<start, rest>) + 1e-15) - mean log(1 - sigmoid(.) + 1e-15), dense Adam on embedding.weight [num_nodes, d]
  * (1 <= d <= 256: device rows are padded to a multiple of 64 floats, the pad stays zero; init_weight = the nn.Embedding initial draw, supplied by the host so that a seed reproduces torch's).
  * ntf_n2v_train_batch: one loader batch (gnn.py:416-419).  inj_pos / inj_neg non-NULL: the window rows [n, context] are given instead of
- * generated (parity tests); apply = 0 leaves the gradient in place (ntf_n2v_get(what = 1)) and skips Adam.  walk_length counts NODES per
- * walk (= cfg.wl, as Node2Vec's constructor takes it).  ntf_n2v_edge_bce: v_loss of gnn.py:420-431 before its second division. */
+ * generated (parity tests); apply = 0 leaves the gradient in place (ntf_n2v_get(what = 1)) and skips Adam: a further apply = 0 call ADDS its
+ * gradient to what is there, and ntf_n2v_get(what = 1) reads the sum and clears it.  walk_length counts NODES per
+ * walk (= cfg.wl, as Node2Vec's constructor takes it).  Every accepted call takes the handle's next step index (the Philox counter word of its
+ * walks and negatives: call t of a handle draws what ntf_n2v_walks(step = t) draws); a REFUSED call (NTF_EINVAL: context < 2 or > walk_length,
+ * B < 1, walks_per_node < 1, num_neg < 0, a start node or an injected node id outside [0, num_nodes)) changes nothing - not the step index,
+ * the table, the gradient or the moments - so the draws of later calls do not depend on it.  ntf_n2v_last_windows: the window rows [n, context] of the last accepted
+ * ntf_n2v_train_batch as the device holds them, positive and negative (replay tests: row j * n_walks + r is nodes j .. j + context - 1 of walk r); the sizes come back
+ * through n_pos / n_neg / context, a NULL row pointer asks for the sizes alone; NTF_ESTATE once ntf_n2v_walks or ntf_n2v_edge_bce has reused the scratch.  ntf_n2v_edge_bce: v_loss of gnn.py:420-431 before its second division. */
 typedef struct ntf_n2v ntf_n2v;
 int  ntf_n2v_create(int device, int64_t num_nodes, int32_t d, const int64_t* rowptr, const int32_t* col, const float* init_weight, uint64_t seed, ntf_n2v** out);
 void ntf_n2v_destroy(ntf_n2v* h);
@@ -346,6 +352,7 @@ const char* ntf_n2v_last_error(const ntf_n2v* h);
 int  ntf_n2v_walks(ntf_n2v* h, const int64_t* start, int64_t n, int32_t walk_length, uint64_t step, int64_t* out_host /* [n, walk_length] */);
 int  ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, int32_t walk_length, int32_t context, int32_t walks_per_node, int32_t num_neg, float lr,
                          const int64_t* inj_pos, int64_t n_pos, const int64_t* inj_neg, int64_t n_neg, int32_t apply, float* loss_out);
+int  ntf_n2v_last_windows(ntf_n2v* h, int64_t* n_pos, int64_t* n_neg, int32_t* context, int64_t* pos_rows, int64_t* neg_rows);
 int  ntf_n2v_get(ntf_n2v* h, int what /* 0 embedding.weight, 1 gradient */, float* host /* [num_nodes, d] */);
 int  ntf_n2v_edge_bce(ntf_n2v* h, const int64_t* src, const int64_t* dst, int64_t n, float* mean_bce);
 

@@ -24,6 +24,7 @@ struct ntf_n2v {
     float *W = nullptr, *G = nullptr, *M1 = nullptr, *V2 = nullptr;
     int64_t* d_batch = nullptr; int64_t batch_cap = 0;
     int64_t* d_rows = nullptr; int64_t rows_cap = 0;     // window rows [n_rows, ctx]
+    const int64_t *win_p = nullptr, *win_n = nullptr; int64_t n_win_p = 0, n_win_n = 0; int win_ctx = 0;   // the last batch's window rows inside d_rows (ntf_n2v_last_windows)
     double* d_loss = nullptr;
     int64_t adam_t = 0; uint64_t seed = 0, step = 0;
     std::string err;
@@ -197,6 +198,7 @@ static int stage_batch(ntf_n2v* h, const int64_t* batch, int64_t B) {
     return NTF_OK;
 }
 static int need_rows(ntf_n2v* h, int64_t elems) {
+    h->win_p = h->win_n = nullptr; h->n_win_p = h->n_win_n = 0; h->win_ctx = 0;   // every writer of d_rows comes through here
     if (h->rows_cap < elems) { if (h->d_rows) hipFree(h->d_rows); int r = nalloc(h, &h->d_rows, elems); if (r) return r; h->rows_cap = elems; }
     return NTF_OK;
 }
@@ -229,22 +231,29 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
                                    float lr, const int64_t* inj_pos, int64_t n_pos, const int64_t* inj_neg, int64_t n_neg, int32_t apply, float* loss_out) {
     if (!h || walk_length < 2 || context < 2 || context > walk_length) return NTF_EINVAL;
     NCHK(h, hipSetDevice(h->device));
-    NCHK(h, hipMemsetAsync(h->d_loss, 0, 8, h->st));
-    const uint64_t step = h->step++;
+    // every argument check (and stage_batch, which checks the start nodes) comes before the step index is taken and before anything on the device is touched:
+    // a refused call changes nothing, so the draws of the calls after it are the ones they would have been without it
     int r;
-    if (inj_pos || inj_neg) {   // parity tests: the window rows themselves are given
-        if ((r = need_rows(h, (n_pos + n_neg) * context))) return r;
-        if ((n_pos > 0 && !inj_pos) || (n_neg > 0 && !inj_neg) || n_pos < 0 || n_neg < 0) return NTF_EINVAL;
+    const bool injected = inj_pos || inj_neg;
+    if (injected) {   // parity tests: the window rows themselves are given
+        if ((n_pos > 0 && !inj_pos) || (n_neg > 0 && !inj_neg) || n_pos < 0 || n_neg < 0) NFAIL(h, NTF_EINVAL, "n2v: injected rows missing or a negative row count");
         for (int64_t i = 0; i < n_pos * context; ++i) if (inj_pos[i] < 0 || inj_pos[i] >= h->n) NFAIL(h, NTF_EINVAL, "n2v: injected node out of range");
         for (int64_t i = 0; i < n_neg * context; ++i) if (inj_neg[i] < 0 || inj_neg[i] >= h->n) NFAIL(h, NTF_EINVAL, "n2v: injected node out of range");
+        if ((r = need_rows(h, (n_pos + n_neg) * context))) return r;
+    } else {
+        if (!batch || B < 1 || walks_per_node < 1 || num_neg < 0) NFAIL(h, NTF_EINVAL, "n2v: need a batch of B >= 1 start nodes, walks_per_node >= 1 and num_neg >= 0");
+        if ((r = stage_batch(h, batch, B))) return r;
+    }
+    NCHK(h, hipMemsetAsync(h->d_loss, 0, 8, h->st));
+    const uint64_t step = h->step++;
+    if (injected) {
         if (n_pos) NCHK(h, hipMemcpyAsync(h->d_rows, inj_pos, n_pos * context * 8, hipMemcpyHostToDevice, h->st));
         if (n_neg) NCHK(h, hipMemcpyAsync(h->d_rows + n_pos * context, inj_neg, n_neg * context * 8, hipMemcpyHostToDevice, h->st));
         NCHK(h, hipStreamSynchronize(h->st));
         launch_pairs(h, h->d_rows, n_pos, context, 1);
         launch_pairs(h, h->d_rows + n_pos * context, n_neg, context, 0);
+        h->win_p = h->d_rows; h->win_n = h->d_rows + n_pos * context; h->n_win_p = n_pos; h->n_win_n = n_neg;
     } else {
-        if (!batch || B < 1 || walks_per_node < 1 || num_neg < 0) return NTF_EINVAL;
-        if ((r = stage_batch(h, batch, B))) return r;
         const int nw = walk_length + 1 - context;
         const int64_t pw = (int64_t)B * walks_per_node, ng = pw * num_neg;
         // scratch: [pos walks | neg walks | pos windows | neg windows]
@@ -262,7 +271,9 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
             hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((ng * nw * context + 255) / 256)), dim3(256), 0, h->st, rw_n, ng, walk_length, context, win_n);
             launch_pairs(h, win_n, ng * nw, context, 0);
         }
+        h->win_p = win_p; h->win_n = win_n; h->n_win_p = pw * nw; h->n_win_n = ng * nw;
     }
+    h->win_ctx = context;
     if (apply) {
         h->adam_t += 1;
         const double b1 = 0.9, b2 = 0.999;
@@ -288,6 +299,17 @@ extern "C" int ntf_n2v_get(ntf_n2v* h, int what, float* host) {   // what: 0 = e
     NCHK(h, hipStreamSynchronize(h->st));
     NCHK(h, hipMemcpy2D(host, (size_t)h->d_user * 4, what ? h->G : h->W, (size_t)h->d * 4, (size_t)h->d_user * 4, (size_t)h->n, hipMemcpyDeviceToHost));
     if (what) NCHK(h, hipMemsetAsync(h->G, 0, (size_t)h->n * h->d * 4, h->st));   // reading the gradient consumes it
+    return NTF_OK;
+}
+
+extern "C" int ntf_n2v_last_windows(ntf_n2v* h, int64_t* n_pos, int64_t* n_neg, int32_t* context, int64_t* pos_rows, int64_t* neg_rows) {
+    if (!h || !n_pos || !n_neg || !context) return NTF_EINVAL;
+    if (!h->win_ctx) NFAIL(h, NTF_ESTATE, "n2v: no batch since the scratch was last reused (ntf_n2v_walks and ntf_n2v_edge_bce write over the window rows)");
+    *n_pos = h->n_win_p; *n_neg = h->n_win_n; *context = h->win_ctx;
+    NCHK(h, hipSetDevice(h->device));
+    if (pos_rows && h->n_win_p) NCHK(h, hipMemcpyAsync(pos_rows, h->win_p, h->n_win_p * h->win_ctx * 8, hipMemcpyDeviceToHost, h->st));
+    if (neg_rows && h->n_win_n) NCHK(h, hipMemcpyAsync(neg_rows, h->win_n, h->n_win_n * h->win_ctx * 8, hipMemcpyDeviceToHost, h->st));
+    NCHK(h, hipStreamSynchronize(h->st));
     return NTF_OK;
 }
 

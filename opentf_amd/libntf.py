@@ -113,6 +113,7 @@ SYMBOLS = {
     "ntf_n2v_walks": (C.c_int, [_P, _P, _I64, _I32, _U64, _P]),
     "ntf_n2v_train_batch": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _I64, _P, _I64, _I32, _P]),
     "ntf_n2v_get": (C.c_int, [_P, C.c_int, _P]),
+    "ntf_n2v_last_windows": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ntf_n2v_edge_bce": (C.c_int, [_P, _P, _P, _I64, _P]),
     "ntf_d2v_create": (C.c_int, [C.c_int, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _U64, C.POINTER(_P)]),
     "ntf_d2v_destroy": (None, [_P]),
@@ -670,6 +671,14 @@ class Node2Vec:
         assert p.shape[1] == n.shape[1]
         self._ck(lib().ntf_n2v_train_batch(self._h, None, 0, max(p.shape[1], 2), p.shape[1], 1, 1, float(lr), _ptr(p), len(p), _ptr(n), len(n), int(apply), C.byref(loss)))
         return loss.value
+
+    def last_windows(self):
+        """(positive, negative) window rows [n, context] of the last accepted batch, as the device held them"""
+        n_pos, n_neg, ctx = C.c_int64(), C.c_int64(), C.c_int32()
+        self._ck(lib().ntf_n2v_last_windows(self._h, C.byref(n_pos), C.byref(n_neg), C.byref(ctx), None, None))
+        pos = np.empty((n_pos.value, ctx.value), dtype=np.int64); neg = np.empty((n_neg.value, ctx.value), dtype=np.int64)
+        self._ck(lib().ntf_n2v_last_windows(self._h, C.byref(n_pos), C.byref(n_neg), C.byref(ctx), _ptr(pos), _ptr(neg)))
+        return pos, neg
 
     def weight(self):
         out = np.empty((self.num_nodes, self.d), dtype=np.float32)

@@ -9,7 +9,10 @@ by node-type offsets, member-team edges of the test / validation teams removed).
 Pinning: no value-level fixture of PyG's outputs exists in the reference tree (random walks under torch's RNG).  What the reference's
 authors committed - three trained toy-dblp tables with their `t_loss` / `v_loss` (tests/golden/g14_n2v_dblp.npz) - pins the loss
 NORMALISATION and the training schedule in distribution: tests/test_n2v.py requires this restatement, run with the committed
-hyper-parameters, to end at the committed loss level.  Parity status: pinned in distribution, not bit-level.
+hyper-parameters, to end at the committed loss level.  Parity status: against PyG pinned in distribution, not bit-level.  The device kernels
+against THIS restatement: loss and every gradient element against its float64 form inside derived f32 bars, the f32 saturation of
+`1 - sigmoid`, Adam over steps, and the device's native walks, negatives and window rows replayed bit for bit from its Philox counters
+(tests/test_gpu_n2v_parity.py, tests/test_n2v_parity_host.py).
 """
 from __future__ import annotations
 
