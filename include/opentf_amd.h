@@ -402,6 +402,39 @@ int  ntf_d2v_infer(ntf_d2v* h, int64_t n, const int64_t* q_ptr, const int32_t* q
                    int32_t dm, int32_t window, int32_t negative, int32_t epochs, double alpha, double min_alpha, uint64_t seed, int32_t serial,
                    const float* init /* [n, d] host */, float* out /* [n, d] host */, double* device_ms /* nullable */);
 
+/* ---- batched cosine nearest-neighbour search over a resident table                    src/mdl/emb/d2v.py:96-98 (infer_d2v: docvecs.most_similar of the inferred vector)
+ * What KeyedVectors.most_similar does one query a call on the host, for a batch, over any [n_rows, d] f32 table (doc2vec's doc vectors, node2vec's embedding.weight):
+ * ntf_knn_create uploads the table once (rows padded on the device to a multiple of 32 floats, the pad exact zeros) and computes its reciprocal row norms;
+ * ntf_knn_query returns, per query, the topn most similar rows.  [n, n_rows] is never formed.
+ * Similarity, all in f32:  sim(i, q) = (dot(i, q) * rq) * rt_i, rounded after each product, where
+ *   dot(i, q) = one k-ordered fmaf chain from 0 over k = 0 .. d-1: acc = fmaf(t_i[k], q[k], acc) (what v_mfma_f32_32x32x2_f32 computes; pad columns add exact zeros);
+ *   rt_i, rq  = 1.f / sqrtf(n2) (IEEE square root, then IEEE division) of n2 = the k-ordered chain acc = fmaf(v[k], v[k], acc) from 0 over the row's / the query's d values.
+ *   A row or query with n2 < FLT_MIN (zero included) has r = 0 and sim exactly +0.0f with everything; -0.0f is returned as +0.0f and ties with it.
+ * The bits of sim(i, q) depend on row i's and the query's values alone - not on where either sits in a tile, a range, a group or a batch.
+ * Ranking: the topn largest sims of a query first-largest-first; equal sims (compared as f32 values) by ascending row id; out_sims holds the values the ranking used.
+ * exclude[q] (exclude nullable; -1: none) is a row id never returned for query q (gensim drops the keys of a most_similar(positive=[key]) call the same way).
+ * When fewer than topn rows are eligible the trailing slots hold id -1 and sim -inf.
+ * Limits: 1 <= d <= 256, 1 <= n_rows <= 2^31 - 1, 1 <= n, 1 <= topn <= 2048.
+ * Memory: beyond the table, its n_rows reciprocal norms and what is per query (the queries, their norms, exclusions, results and one running candidate list of topn
+ * 8-byte entries for each query of a group), the device holds only the sims workspace, which never exceeds workspace_bytes (0 = NTF_KNN_WORKSPACE_BYTES).
+ * The smallest unit of work is 32 queries x 256 table rows of f32 sims = 32 KiB.  The queries are walked in groups of 32 g, the table in ranges of 256 r rows:
+ *   g = min(max(workspace_bytes / 8 MiB, 1), 32, ceil(n / 32));   r = min(workspace_bytes / (gw * 32 KiB), 1024, ceil(n_rows / 256))     (integer divisions)
+ * where gw = g rounded up to a multiple of c, and c = 4 (d <= 128 and min(32 g, n) > 64), 2 (min(32 g, n) > 32) or 1 is how many 32-query tiles a workgroup of the sims
+ * kernel keeps resident: the workspace is 32 gw x 256 r x 4 bytes <= workspace_bytes (g > 1 only from 16 MiB on, so r >= 1).  The handle keeps no larger workspace from an earlier call.  Per range the sims of the group go to the workspace, each query's topn of the range are selected and merged into its
+ * running list by the 64-bit composite (order-preserving key of the sim << 32 | 0x7fffffff - id) - a total order, so the result is bit-identical for every budget.
+ * Purity: no table is written; the result of query q is a pure function of (table, query row, topn, exclude[q]): bit-identical under any split or permutation of
+ * a batch and under any workspace_bytes.  device_ms (nullable): device time of the sims / selection kernels of the call.
+ * NTF_EINVAL (message: ntf_knn_last_error; of a failed create: ntf_knn_last_error(NULL)) with every output untouched for: a null pointer (exclude and device_ms
+ * excepted) or a size outside the limits; a non-finite value in the table (create) or in a query; a table row (create) or a query whose f32 n2 overflows; an exclude
+ * value outside [-1, n_rows); workspace_bytes negative or below the 32 KiB unit.  No HIP device: NTF_EHIP from create (there is no CPU fallback). */
+#define NTF_KNN_WORKSPACE_BYTES ((int64_t)256 << 20)
+typedef struct ntf_knn ntf_knn;
+int  ntf_knn_create(int device, const float* table /* [n_rows, d] host */, int64_t n_rows, int32_t d, ntf_knn** out);
+void ntf_knn_destroy(ntf_knn* h);
+const char* ntf_knn_last_error(const ntf_knn* h);
+int  ntf_knn_query(ntf_knn* h, const float* queries /* [n, d] host */, int64_t n, int32_t topn, const int64_t* exclude /* [n] nullable */,
+                   int64_t workspace_bytes, int32_t* out_idx /* [n, topn] */, float* out_sims /* [n, topn] */, double* device_ms /* nullable */);
+
 /* device generators behind Flipout's eps / signs (dev_out = device pointers), for statistical tests */
 int ntf_k_fill_normal(void* stream, uint64_t seed, uint64_t step, int layer, int64_t n, float* dev_out);
 int ntf_k_fill_sign(void* stream, uint64_t seed, uint64_t step, int layer, int rows, int cols, float* dev_out);

@@ -1,0 +1,430 @@
+// Batched cosine nearest-neighbour search over a resident [n_rows, d] f32 table on the MI355X (include/opentf_amd.h ntf_knn_*): what
+// KeyedVectors.most_similar (opentf_amd/mdl/emb/d2v.py, the second half of the reference's infer_d2v, src/mdl/emb/d2v.py:96-98) does one query at a time on the host.
+//   k_knn_norms   reciprocal row norms (once per table at create, once per call for the queries)
+//   k_knn_sims    sims of a query group against a row range into the workspace, exact-f32 MFMA (v_mfma_f32_32x32x2_f32): the query chunk resident in LDS,
+//                 the table streamed with 16-byte loads through a wave-private LDS stage that gives the MFMA operand its [row][k] -> lane transpose
+//   k_knn_select  per (query, range): the topn largest of the range by (sim desc, id asc), merged into the query's running list by the same 64-bit composite
+//   k_knn_finish  running lists -> ids and sims
+// [n, n_rows] is never formed: the workspace holds [query group, row range] and is sized by the caller's budget alone.
+#include "../../include/opentf_amd.h"
+#include "ntf_device.h"
+#include "ntf_fused_common.h"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace ntf;
+
+struct ntf_knn {
+    int device = 0, n_cu = 0; hipStream_t st = nullptr;
+    int64_t n_rows = 0; int d = 0, dp = 0;        // dp: the device row stride, d rounded up to the 32-float k-chunk; the columns past d are zero
+    float *table = nullptr, *rinv = nullptr;      // [n_rows, dp], [n_rows]
+    int* flag = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // the last call's queries [n, dp], their reciprocal norms, exclusions, results [n, topn] and running lists [group, topn]; the sims workspace; grown on demand
+    float *q = nullptr, *q_rinv = nullptr, *o_sims = nullptr, *ws = nullptr; int32_t *q_excl = nullptr, *o_idx = nullptr; unsigned long long* run = nullptr;
+    int64_t q_cap = 0, qr_cap = 0, qe_cap = 0, oi_cap = 0, os_cap = 0, run_cap = 0, ws_cap = 0;
+    std::string err;
+};
+static thread_local std::string g_knn_create_error;
+
+#define KCHK(h, call) do { hipError_t _s = (call); if (_s != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(_s); return NTF_EHIP; } } while (0)
+#define KFAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
+
+extern "C" const char* ntf_knn_last_error(const ntf_knn* h) { return h ? h->err.c_str() : g_knn_create_error.c_str(); }
+
+namespace {
+constexpr int KNN_KC = 32;               // k-chunk: floats of a row staged at a time (one 128-B line a row); rows are padded to a multiple of it
+constexpr int KNN_SLD = KNN_KC + 1;      // odd LDS row stride: the fragment reads (32 lanes = 32 rows, same k) hit 32 different banks
+constexpr int KNN_WAVES = 8;             // waves a workgroup, 32 table rows each
+constexpr int KNN_RB = KNN_WAVES * 32;   // table rows a workgroup takes at a time (the row unit of the workspace plan)
+constexpr int KNN_QUNIT = 32;            // the query unit of the workspace plan
+constexpr int KNN_MAX_GROUP = 1024;      // queries a group holds at most
+constexpr int64_t KNN_MAX_RANGE = 262144;   // rows a range holds at most: a selection workgroup walks one (query, range) row of sims
+constexpr int KNN_TOPN_MAX = 2048;
+constexpr int KNN_SAMPLE = 4096;
+
+// ---- reciprocal norms: n2 = one k-ordered fmaf chain from 0, rinv = 1 / sqrt(n2) (IEEE sqrt, IEEE divide), 0 when n2 < FLT_MIN.  flag |= 1: a non-finite value, |= 2: n2 overflows.
+// One thread a row keeps the chain sequential; the rows come through LDS in 32-float chunks so that the global reads are whole 128-B lines (8 lanes a row, 16 bytes each)
+// and the chain's reads - 256 rows at the same k, odd stride - hit different banks.  The pad columns are zeros: fmaf(0, 0, n2) = n2.
+__global__ __launch_bounds__(256) void k_knn_norms(const float* __restrict__ T, int64_t n, int d, int dp, float* __restrict__ rinv, int* __restrict__ flag) {
+    __shared__ float tile[256 * KNN_SLD];
+    const int tid = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * 256, i = i0 + tid;
+    float n2 = 0.f; bool bad = false;
+    for (int k0 = 0; k0 < dp; k0 += KNN_KC) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int r = j * 32 + (tid >> 3), k = (tid & 7) * 4;
+            const float4 v = (i0 + r < n) ? *reinterpret_cast<const float4*>(T + (i0 + r) * dp + k0 + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            float* s = tile + r * KNN_SLD + k;
+            s[0] = v.x; s[1] = v.y; s[2] = v.z; s[3] = v.w;
+        }
+        __syncthreads();
+        for (int k = 0; k < KNN_KC; ++k) { const float v = tile[tid * KNN_SLD + k]; bad |= !(fabsf(v) <= FLT_MAX); n2 = fmaf(v, v, n2); }
+    }
+    if (i >= n) return;
+    if (bad) atomicOr(flag, 1);
+    else if (!(n2 <= FLT_MAX)) atomicOr(flag, 2);
+    rinv[i] = n2 < FLT_MIN ? 0.f : 1.f / sqrtf(n2);
+}
+
+struct KnnSimArgs {
+    const float *T, *rinv_t, *Q, *rinv_q;   // Q / rinv_q: the group's first query
+    float* S;                               // [group, ld] sims of the range
+    int64_t r0, ld; int rr, nq, dp;         // the range [r0, r0 + rr), queries in the group, row stride
+};
+
+// NQT 32-query tiles resident a workgroup (blockIdx.y picks the chunk of the group); blockIdx.x strides over the range's 256-row blocks.
+// MFMA operands: A = queries (lane: query lane & 31, k = 2 s + (lane >> 5)), B = table rows (lane: row lane & 31, same k) - so the accumulator's lane axis is the
+// table row and a store of one accumulator register is two 128-B runs of a query's sims row.  Step s of the chain takes k = 2 s then 2 s + 1: k-ordered from 0.
+template <int NQT>
+__global__ __launch_bounds__(KNN_WAVES * 64) void k_knn_sims(KnnSimArgs a) {
+    extern __shared__ float smem[];
+    const int qld = a.dp + 1;
+    float* Qs = smem;                                         // [NQT * 32][dp + 1]
+    float* rqs = Qs + NQT * 32 * qld;                         // [NQT * 32]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* stage = rqs + NQT * 32 + wave * (32 * KNN_SLD);    // [32][33], private to the wave
+    const int q0 = blockIdx.y * (NQT * 32);
+    for (int e = tid; e < NQT * 32 * a.dp; e += blockDim.x) {
+        const int q = e / a.dp, k = e - q * a.dp;
+        Qs[q * qld + k] = (q0 + q < a.nq) ? a.Q[(int64_t)(q0 + q) * a.dp + k] : 0.f;
+    }
+    for (int q = tid; q < NQT * 32; q += blockDim.x) rqs[q] = (q0 + q < a.nq) ? a.rinv_q[q0 + q] : 0.f;
+    __syncthreads();
+    const int nkc = a.dp / KNN_KC, nrb = (a.rr + KNN_RB - 1) / KNN_RB;
+    const int lrow = lane >> 3, lk = (lane & 7) * 4;          // staging: 8 lanes a row of the chunk, 8 rows an instruction
+    const float* aq = Qs + (lane & 31) * qld + (lane >> 5);
+    const float* bs = stage + (lane & 31) * KNN_SLD + (lane >> 5);
+    for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+        const int w0 = rb * KNN_RB + wave * 32;               // the wave's first row inside the range
+        if (w0 >= a.rr) continue;                             // (no workgroup barrier below)
+        const float* Tw = a.T + (a.r0 + w0) * a.dp;
+        float4 pre[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = j * 8 + lrow;
+            pre[j] = (w0 + r < a.rr) ? *reinterpret_cast<const float4*>(Tw + (int64_t)r * a.dp + lk) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        f32x16 acc[NQT];
+#pragma unroll
+        for (int t = 0; t < NQT; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+        for (int kc = 0; kc < nkc; ++kc) {
+            __builtin_amdgcn_wave_barrier();                  // the previous chunk's fragment reads are issued before the stage is overwritten
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float* s = stage + (j * 8 + lrow) * KNN_SLD + lk;
+                s[0] = pre[j].x; s[1] = pre[j].y; s[2] = pre[j].z; s[3] = pre[j].w;
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (kc + 1 < nkc) {                               // the next chunk's loads fly under this chunk's MFMAs
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int r = j * 8 + lrow;
+                    pre[j] = (w0 + r < a.rr) ? *reinterpret_cast<const float4*>(Tw + (int64_t)r * a.dp + (kc + 1) * KNN_KC + lk) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            }
+            const float* ak = aq + kc * KNN_KC;
+#pragma unroll 4
+            for (int s = 0; s < KNN_KC / 2; ++s) {
+                const float b = bs[2 * s];
+#pragma unroll
+                for (int t = 0; t < NQT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[t * 32 * qld + 2 * s], b, acc[t], 0, 0, 0);
+            }
+        }
+        const int row = w0 + (lane & 31);
+        if (row < a.rr) {
+            const float rt = a.rinv_t[a.r0 + row];
+            // register r of tile t is query 32 t + 8 (r >> 2) + 4 (lane >> 5) + (r & 3); group x range <= 2^28 floats, so the offsets are 32-bit
+            int ldi = (int)a.ld;
+            asm volatile("" : "+v"(ldi));       // kept in a vector register: 64 scalar multiples of it, one per store, do not fit the scalar file
+            int ql = 4 * (lane >> 5), off = (q0 + ql) * ldi + row;
+#pragma unroll
+            for (int t = 0; t < NQT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float rq = rqs[ql];                 // (a query past the group's last has rq = 0: its row of the workspace exists, the workspace holds whole chunks)
+                    float sim = (acc[t][r] * rq) * rt;
+                    if (rq == 0.f || rt == 0.f || sim == 0.f) sim = 0.f;           // a norm below FLT_MIN scores 0 with everything; -0 is returned as +0
+                    a.S[off] = sim;
+                    const int step = (r & 3) == 3 ? 5 : 1;
+                    ql += step; off += step * ldi;
+                }
+        }
+    }
+}
+
+// ---- selection.  f32 bits -> unsigned key in value order (negative values: all bits flipped; others: the sign bit set); every real value's key is >= 1
+__device__ __forceinline__ unsigned knn_key(float v) { const unsigned u = __float_as_uint(v); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float knn_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+__device__ __forceinline__ void knn_bitonic_desc(unsigned long long* keys, int n2, int tid, int nthreads) {
+    for (int size = 2; size <= n2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < n2 / 2; t += nthreads) {
+                const int lo = (t / stride) * stride * 2 + (t % stride), hi = lo + stride;
+                const bool desc = ((lo & size) == 0);
+                const unsigned long long x = keys[lo], y = keys[hi];
+                if ((x < y) == desc) { keys[lo] = y; keys[hi] = x; }
+            }
+            __syncthreads();
+        }
+}
+
+// One workgroup per query of the group: the K largest of its sims row S[q, 0 .. M) by the composite (key << 32) | (0x7fffffff - id), id = r0 + column, the
+// excluded id left out - k_topk_rows' two routes (a sorted sample's threshold, one collecting pass, a bitonic sort; else an exact 3-pass radix selection) on signed
+// values - then merged with the query's running list (first = 0) by the same composite: a total order, so the merge is exact and the order of the ranges free.
+// A composite of 0 is an empty slot.
+__global__ __launch_bounds__(1024) void k_knn_select(const float* __restrict__ S, int64_t ld, int M, int64_t r0, int K, const int32_t* __restrict__ excl,
+                                                     unsigned long long* __restrict__ run, int first) {
+    __shared__ unsigned long long keys[KNN_SAMPLE];
+    __shared__ unsigned hist[2048];
+    __shared__ unsigned s_prefix, s_remaining, s_count, s_wcnt[16];
+    const int64_t i = blockIdx.x;
+    const float* row = S + i * ld;
+    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t ex = excl ? (int64_t)excl[i] - r0 : -1;     // the excluded column of this range, if it lies in it
+    int n2 = 1; while (n2 < K) n2 <<= 1;
+    bool done = false;
+    if (M >= 8 * KNN_SAMPLE && K * 8 <= KNN_TOPN_MAX) {
+        const int stride = M / KNN_SAMPLE;
+        for (int k = tid; k < KNN_SAMPLE; k += NT) keys[k] = (unsigned long long)knn_key(row[(int64_t)k * stride]);
+        __syncthreads();
+        knn_bitonic_desc(keys, KNN_SAMPLE, tid, NT);
+        int r = (int)((4.5 * K * KNN_SAMPLE) / M) + 1;
+        if (r < 8) r = 8;
+        const unsigned thr = (unsigned)keys[r < KNN_SAMPLE ? r : KNN_SAMPLE - 1];
+        __syncthreads();
+        if (tid == 0) s_count = 0;
+        __syncthreads();
+        for (int c = tid; c < M; c += NT) {
+            const unsigned u = knn_key(row[c]);
+            if (u > thr && c != ex) { const unsigned p = atomicAdd(&s_count, 1u); if (p < KNN_TOPN_MAX) keys[p] = ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - (r0 + c)); }
+        }
+        __syncthreads();
+        const unsigned cnt = s_count;
+        if (cnt >= (unsigned)K && cnt <= KNN_TOPN_MAX) {
+            int m2 = n2; while (m2 < (int)cnt) m2 <<= 1;
+            for (int k = cnt + tid; k < m2; k += NT) keys[k] = 0ull;
+            __syncthreads();
+            knn_bitonic_desc(keys, m2, tid, NT);
+            done = true;
+        }
+        __syncthreads();
+    }
+    if (!done) {
+        unsigned prefix = 0, prefix_mask = 0, remaining = K;
+        const int shifts[3] = {21, 10, 0};
+        const int widths[3] = {11, 11, 10};
+        for (int pass = 0; pass < 3; ++pass) {
+            const int sh = shifts[pass], nb = 1 << widths[pass];
+            for (int b = tid; b < nb; b += NT) hist[b] = 0;
+            __syncthreads();
+            for (int c = tid; c < M; c += NT) {
+                const unsigned u = knn_key(row[c]);
+                if ((u & prefix_mask) == prefix && c != ex) atomicAdd(&hist[(u >> sh) & (nb - 1)], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned rem = remaining; int b = nb - 1;
+                for (; b > 0; --b) { if (hist[b] >= rem) break; rem -= hist[b]; }
+                s_prefix = prefix | ((unsigned)b << sh); s_remaining = rem;
+            }
+            __syncthreads();
+            prefix = s_prefix; remaining = s_remaining;
+            prefix_mask |= (unsigned)(nb - 1) << sh;
+            __syncthreads();
+        }
+        // prefix = the key of the K-th largest eligible value (0 when fewer than K are eligible); `remaining` = how many copies of it belong to the top K
+        if (tid == 0) s_count = 0;
+        for (int k = tid; k < KNN_SAMPLE; k += NT) keys[k] = 0ull;
+        __syncthreads();
+        const unsigned thr = prefix;
+        for (int c = tid; c < M; c += NT) {
+            const unsigned u = knn_key(row[c]);
+            if (u > thr && c != ex) { const unsigned p = atomicAdd(&s_count, 1u); keys[p] = ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - (r0 + c)); }
+        }
+        __syncthreads();
+        // ties at the threshold: the `remaining` smallest ids, found by an ordered scan (ballot inside a wave, wave counts through LDS)
+        unsigned base = s_count, need = remaining;
+        for (int b0 = 0; b0 < M && need > 0; b0 += NT) {
+            const int c = b0 + tid;
+            const bool hit = c < M && c != ex && knn_key(row[c]) == thr;
+            const unsigned long long m = __ballot(hit);
+            if (lane == 0) s_wcnt[wave] = (unsigned)__popcll(m);
+            __syncthreads();
+            unsigned before = 0, total = 0;
+            for (int w = 0; w < NT / 64; ++w) { const unsigned n = s_wcnt[w]; if (w < wave) before += n; total += n; }
+            const unsigned pos = before + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+            if (hit && pos < need) keys[base + pos] = ((unsigned long long)thr << 32) | (unsigned)(0x7fffffff - (r0 + c));
+            const unsigned took = total < need ? total : need;
+            base += took; need -= took;
+            __syncthreads();
+        }
+        knn_bitonic_desc(keys, n2, tid, NT);
+    }
+    // keys[0 .. K): the range's candidates, sorted.  Merge with the running list: 2 n2 <= 4096 composites, sorted again
+    unsigned long long* mine = run + i * K;
+    if (!first) {
+        __syncthreads();
+        for (int k = tid; k < n2; k += NT) keys[n2 + k] = k < K ? mine[k] : 0ull;
+        for (int k = K + tid; k < n2; k += NT) keys[k] = 0ull;
+        __syncthreads();
+        knn_bitonic_desc(keys, 2 * n2, tid, NT);
+    }
+    for (int k = tid; k < K; k += NT) mine[k] = keys[k];
+}
+
+__global__ void k_knn_finish(const unsigned long long* __restrict__ run, int64_t n, int32_t* __restrict__ idx, float* __restrict__ sims) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const unsigned long long c = run[e];
+    idx[e] = c ? 0x7fffffff - (int32_t)(c & 0xffffffffu) : -1;
+    sims[e] = c ? knn_unkey((unsigned)(c >> 32)) : -INFINITY;
+}
+
+template <typename T> int kalloc(ntf_knn* h, T** p, int64_t n) {
+    *p = nullptr;
+    if (hipMalloc((void**)p, (size_t)std::max<int64_t>(n, 1) * sizeof(T)) != hipSuccess) { h->err = "hipMalloc failed"; return NTF_ENOMEM; }
+    return NTF_OK;
+}
+template <typename T> int kgrow(ntf_knn* h, T** p, int64_t* cap, int64_t n) {
+    if (n <= *cap) return NTF_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr; *cap = 0;
+    const int rc = kalloc(h, p, n);
+    if (rc == NTF_OK) *cap = n;
+    return rc;
+}
+
+size_t knn_sims_lds(int nqt, int dp) { return ((size_t)nqt * 32 * (dp + 1) + (size_t)nqt * 32 + (size_t)KNN_WAVES * 32 * KNN_SLD) * sizeof(float); }
+}  // namespace
+
+extern "C" void ntf_knn_destroy(ntf_knn* h) {
+    if (!h) return;
+    hipSetDevice(h->device);
+    if (h->st) hipStreamSynchronize(h->st);
+    for (void* p : {(void*)h->table, (void*)h->rinv, (void*)h->flag, (void*)h->q, (void*)h->q_rinv, (void*)h->q_excl, (void*)h->o_idx, (void*)h->o_sims, (void*)h->run, (void*)h->ws})
+        if (p) hipFree(p);
+    if (h->ev0) hipEventDestroy(h->ev0);
+    if (h->ev1) hipEventDestroy(h->ev1);
+    if (h->st) hipStreamDestroy(h->st);
+    delete h;
+}
+
+extern "C" int ntf_knn_create(int device, const float* table, int64_t n_rows, int32_t d, ntf_knn** out) {
+    if (!out) { g_knn_create_error = "knn: out is NULL"; return NTF_EINVAL; }
+    *out = nullptr;
+    if (!table || n_rows < 1 || n_rows > 0x7fffffffll || d < 1 || d > 256) { g_knn_create_error = "knn: need a table, 1 <= n_rows <= 2^31 - 1 and 1 <= d <= 256"; return NTF_EINVAL; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_knn_create_error = "no HIP device: the search has no CPU fallback"; return NTF_EHIP; }
+    if (device < 0 || device >= ndev) { g_knn_create_error = "no such HIP device (there is no CPU fallback)"; return NTF_EHIP; }
+    hipSetDevice(device);
+    ntf_knn* h = new ntf_knn();
+    h->device = device; h->n_rows = n_rows; h->d = d; h->dp = (d + KNN_KC - 1) / KNN_KC * KNN_KC;
+    const int64_t dp = h->dp;
+    if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->n_cu < 1) h->n_cu = 256;
+    if (hipStreamCreate(&h->st) != hipSuccess) { g_knn_create_error = "hipStreamCreate failed"; delete h; return NTF_EHIP; }
+    int rc = NTF_OK;
+    auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
+    A(kalloc(h, &h->table, n_rows * dp)); A(kalloc(h, &h->rinv, n_rows)); A(kalloc(h, &h->flag, 1));
+    if (rc != NTF_OK) { g_knn_create_error = h->err; ntf_knn_destroy(h); return rc; }
+    bool ok = true;
+    auto H = [&](hipError_t s) { ok = ok && s == hipSuccess; };
+    if (dp != d) H(hipMemset(h->table, 0, (size_t)n_rows * dp * 4));           // the pad columns are exact zeros: they add nothing to a chain
+    H(hipMemcpy2D(h->table, (size_t)dp * 4, table, (size_t)d * 4, (size_t)d * 4, (size_t)n_rows, hipMemcpyHostToDevice));
+    H(hipMemsetAsync(h->flag, 0, 4, h->st));
+    hipLaunchKernelGGL(k_knn_norms, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, h->st, h->table, n_rows, (int)d, (int)dp, h->rinv, h->flag);
+    H(hipGetLastError());
+    int flag = 0;
+    H(hipMemcpyAsync(&flag, h->flag, 4, hipMemcpyDeviceToHost, h->st));
+    H(hipStreamSynchronize(h->st));
+    if (!ok) { g_knn_create_error = "knn: device initialisation failed"; ntf_knn_destroy(h); return NTF_EHIP; }
+    if (flag) {
+        g_knn_create_error = (flag & 1) ? "knn: a table value is not finite" : "knn: the f32 squared norm of a table row overflows";
+        ntf_knn_destroy(h); return NTF_EINVAL;
+    }
+    *out = h;
+    return NTF_OK;
+}
+
+extern "C" int ntf_knn_query(ntf_knn* h, const float* queries, int64_t n, int32_t topn, const int64_t* exclude, int64_t workspace_bytes,
+                             int32_t* out_idx, float* out_sims, double* device_ms) {
+    if (!h) { g_knn_create_error = "knn query: the handle is NULL"; return NTF_EINVAL; }
+    if (!queries || !out_idx || !out_sims) KFAIL(h, NTF_EINVAL, "knn query: queries, out_idx and out_sims are required");
+    if (n < 1) KFAIL(h, NTF_EINVAL, "knn query: n < 1");
+    if (topn < 1 || topn > KNN_TOPN_MAX) KFAIL(h, NTF_EINVAL, "knn query: topn outside 1..2048");
+    if (workspace_bytes < 0) KFAIL(h, NTF_EINVAL, "knn query: workspace_bytes < 0");
+    const int64_t wsb = workspace_bytes ? workspace_bytes : NTF_KNN_WORKSPACE_BYTES;
+    const int64_t unit = (int64_t)KNN_QUNIT * KNN_RB * 4;
+    if (wsb < unit) KFAIL(h, NTF_EINVAL, "knn query: workspace_bytes below one unit of work (32 queries x 256 rows of f32 sims = 32 KiB)");
+    const int d = h->d; const int64_t dp = h->dp, N = h->n_rows;
+    for (int64_t e = 0; e < n * d; ++e) if (!std::isfinite(queries[e])) KFAIL(h, NTF_EINVAL, "knn query: a query value is not finite");
+    std::vector<int32_t> excl;
+    if (exclude) {
+        excl.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) { if (exclude[i] < -1 || exclude[i] >= N) KFAIL(h, NTF_EINVAL, "knn query: an exclude value outside [-1, n_rows)"); excl[(size_t)i] = (int32_t)exclude[i]; }
+    }
+    // the plan (header): a group of 32 g queries, a range of 256 r rows, group x range x 4 bytes <= the budget
+    const int64_t g = std::min<int64_t>(std::max<int64_t>(wsb / ((int64_t)8 << 20), 1), std::min<int64_t>(KNN_MAX_GROUP / KNN_QUNIT, (n + KNN_QUNIT - 1) / KNN_QUNIT));
+    const int64_t G = g * KNN_QUNIT;
+    // query tiles resident a workgroup of the sims kernel: 4 (dp <= 128: a 4-tile image of wider rows does not fit LDS beside the stages), 2 or 1, as many as a full group
+    // fills.  The workspace holds whole chunks of 32 nqt rows (gw = g rounded up to a multiple of nqt), so every query slot a workgroup stores to has its row there
+    const int nqt_max = (std::min(G, n) > 64 && dp <= 128) ? 4 : (std::min(G, n) > 32) ? 2 : 1;
+    const int64_t Gw = (g + nqt_max - 1) / nqt_max * nqt_max * KNN_QUNIT;
+    const int64_t R = std::min<int64_t>(std::min<int64_t>(wsb / (Gw * KNN_RB * 4), KNN_MAX_RANGE / KNN_RB), (N + KNN_RB - 1) / KNN_RB) * KNN_RB;
+    KCHK(h, hipSetDevice(h->device));
+    KCHK(h, hipStreamSynchronize(h->st));
+    {
+        int rc = NTF_OK;
+        auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
+        A(kgrow(h, &h->q, &h->q_cap, n * dp)); A(kgrow(h, &h->q_rinv, &h->qr_cap, n)); A(kgrow(h, &h->q_excl, &h->qe_cap, n));
+        A(kgrow(h, &h->o_idx, &h->oi_cap, n * topn)); A(kgrow(h, &h->o_sims, &h->os_cap, n * topn)); A(kgrow(h, &h->run, &h->run_cap, G * topn)); if (h->ws_cap != Gw * R) { if (h->ws) hipFree(h->ws); h->ws = nullptr; h->ws_cap = 0; A(kgrow(h, &h->ws, &h->ws_cap, Gw * R)); }      // never above this call's budget
+        if (rc != NTF_OK) return rc;
+    }
+    if (dp != d) KCHK(h, hipMemset(h->q, 0, (size_t)n * dp * 4));
+    KCHK(h, hipMemcpy2D(h->q, (size_t)dp * 4, queries, (size_t)d * 4, (size_t)d * 4, (size_t)n, hipMemcpyHostToDevice));
+    if (exclude) KCHK(h, hipMemcpy(h->q_excl, excl.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    KCHK(h, hipMemsetAsync(h->flag, 0, 4, h->st));
+    hipLaunchKernelGGL(k_knn_norms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->q, n, d, (int)dp, h->q_rinv, h->flag);
+    int flag = 0;
+    KCHK(h, hipMemcpyAsync(&flag, h->flag, 4, hipMemcpyDeviceToHost, h->st));
+    KCHK(h, hipStreamSynchronize(h->st));
+    if (flag) KFAIL(h, NTF_EINVAL, "knn query: the f32 squared norm of a query overflows");
+    if (device_ms) { if (!h->ev0) { KCHK(h, hipEventCreate(&h->ev0)); KCHK(h, hipEventCreate(&h->ev1)); } KCHK(h, hipEventRecord(h->ev0, h->st)); }
+    for (int64_t g0 = 0; g0 < n; g0 += G) {
+        const int ng = (int)std::min<int64_t>(G, n - g0);
+        const int nqt = std::min(nqt_max, ng > 64 ? 4 : ng > 32 ? 2 : 1);      // a shorter last group takes a shorter chunk (1, 2 and 4 divide nqt_max)
+        const size_t lds = knn_sims_lds(nqt, (int)dp);
+        const int per_cu = std::max<int>(1, (int)((160u << 10) / lds));
+        for (int64_t r0 = 0; r0 < N; r0 += R) {
+            const int rr = (int)std::min<int64_t>(R, N - r0);
+            KnnSimArgs a;
+            a.T = h->table; a.rinv_t = h->rinv; a.Q = h->q + g0 * dp; a.rinv_q = h->q_rinv + g0; a.S = h->ws; a.r0 = r0; a.ld = R; a.rr = rr; a.nq = ng; a.dp = (int)dp;
+            const dim3 grid((unsigned)std::min<int64_t>((rr + KNN_RB - 1) / KNN_RB, (int64_t)h->n_cu * per_cu), (unsigned)((ng + nqt * 32 - 1) / (nqt * 32)));
+            switch (nqt) {
+                case 1: set_max_lds(reinterpret_cast<const void*>(k_knn_sims<1>), (int)lds); hipLaunchKernelGGL(k_knn_sims<1>, grid, dim3(KNN_WAVES * 64), lds, h->st, a); break;
+                case 2: set_max_lds(reinterpret_cast<const void*>(k_knn_sims<2>), (int)lds); hipLaunchKernelGGL(k_knn_sims<2>, grid, dim3(KNN_WAVES * 64), lds, h->st, a); break;
+                default: set_max_lds(reinterpret_cast<const void*>(k_knn_sims<4>), (int)lds); hipLaunchKernelGGL(k_knn_sims<4>, grid, dim3(KNN_WAVES * 64), lds, h->st, a); break;
+            }
+            hipLaunchKernelGGL(k_knn_select, dim3((unsigned)ng), dim3(1024), 0, h->st, h->ws, R, rr, r0, (int)topn, exclude ? h->q_excl + g0 : nullptr, h->run, r0 == 0 ? 1 : 0);
+        }
+        const int64_t ne = (int64_t)ng * topn;
+        hipLaunchKernelGGL(k_knn_finish, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->st, h->run, ne, h->o_idx + g0 * topn, h->o_sims + g0 * topn);
+        const hipError_t s = hipGetLastError();
+        if (s != hipSuccess) KFAIL(h, NTF_EHIP, std::string("knn kernel launch: ") + hipGetErrorString(s));
+    }
+    if (device_ms) KCHK(h, hipEventRecord(h->ev1, h->st));
+    KCHK(h, hipStreamSynchronize(h->st));
+    if (device_ms) { float ms = 0.f; KCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
+    KCHK(h, hipMemcpy(out_idx, h->o_idx, (size_t)n * topn * 4, hipMemcpyDeviceToHost));
+    KCHK(h, hipMemcpy(out_sims, h->o_sims, (size_t)n * topn * 4, hipMemcpyDeviceToHost));
+    return NTF_OK;
+}

@@ -122,6 +122,10 @@ SYMBOLS = {
     "ntf_d2v_get": (C.c_int, [_P, C.c_int, _P]),
     "ntf_d2v_set": (C.c_int, [_P, C.c_int, _P]),
     "ntf_d2v_infer": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, C.c_double, C.c_double, _U64, _I32, _P, _P, _P]),
+    "ntf_knn_create": (C.c_int, [C.c_int, _P, _I64, _I32, C.POINTER(_P)]),
+    "ntf_knn_destroy": (None, [_P]),
+    "ntf_knn_last_error": (C.c_char_p, [_P]),
+    "ntf_knn_query": (C.c_int, [_P, _P, _I64, _I32, _P, _I64, _P, _P, _P]),
     "ntf_k_gemm_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _I64, _I64, _P, _I64, _I64, _P, _I64]),
     "ntf_k_fill_normal": (C.c_int, [_P, _U64, _U64, C.c_int, _I64, _P]),
     "ntf_k_fill_sign": (C.c_int, [_P, _U64, _U64, C.c_int, C.c_int, C.c_int, _P]),
@@ -773,3 +777,48 @@ class Doc2Vec:
         v = _f32(values)
         assert v.shape == ((self.n_docs if what == 0 else self.n_vocab), self.d)
         self._ck(lib().ntf_d2v_set(self._h, int(what), _ptr(v)))
+
+
+class Knn:
+    """Batched cosine nearest-neighbour search over a [rows, d] float32 table resident on one MI355X (include/opentf_amd.h ntf_knn_*): what
+    KeyedVectors.most_similar does one query a call on the host.  The table is uploaded once; `query` never forms [n, rows]."""
+
+    WORKSPACE_BYTES = 256 << 20      # NTF_KNN_WORKSPACE_BYTES
+    UNIT_BYTES = 32 * 256 * 4        # the smallest unit of work: 32 queries x 256 table rows of f32 sims
+
+    def __init__(self, table, device=0):
+        t = _f32(table)
+        if t.ndim != 2:
+            raise NtfError(f"table must be [rows, d], got {t.shape}")
+        self.n_rows, self.d = int(t.shape[0]), int(t.shape[1])
+        self._h = C.c_void_p()
+        rc = lib().ntf_knn_create(int(device), _ptr(t), self.n_rows, self.d, C.byref(self._h))
+        if rc != 0:
+            msg = lib().ntf_knn_last_error(None); self._h = None
+            raise NtfError(f"ntf_knn_create failed ({rc}): {msg.decode() if msg else ''}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().ntf_knn_destroy(self._h); self._h = None
+
+    def __del__(self):
+        try: self.close()
+        except Exception: pass
+
+    def query(self, queries, topn=10, exclude=None, workspace_bytes=0, want_ms=False):
+        """the topn most similar rows of every query [n, d], largest sim first, equal sims by ascending row id; exclude [n] (None; -1: none) = a row id never returned
+        for that query.  -> (idx [n, topn] int32, sims [n, topn] float32[, device ms]); slots past the eligible rows hold id -1 and sim -inf"""
+        if not getattr(self, "_h", None):
+            raise NtfError("the Knn handle is closed")
+        q = _f32(queries)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise NtfError(f"queries must be [n, {self.d}], got {q.shape}")
+        n = int(q.shape[0])
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.int64)
+        if ex is not None and ex.shape != (n,):
+            raise NtfError("exclude must hold one row id per query")
+        idx = np.empty((n, max(int(topn), 0)), dtype=np.int32); sims = np.empty((n, max(int(topn), 0)), dtype=np.float32); ms = C.c_double()
+        rc = lib().ntf_knn_query(self._h, _ptr(q), n, int(topn), _ptr(ex), int(workspace_bytes), _ptr(idx), _ptr(sims), C.byref(ms) if want_ms else None)
+        if rc != 0:
+            raise NtfError(f"libopentf_amd knn error {rc}: {lib().ntf_knn_last_error(self._h).decode()}")
+        return (idx, sims, ms.value) if want_ms else (idx, sims)

@@ -173,6 +173,39 @@ class KeyedVectors:
         top = np.argsort(-sims)[:topn]
         return [(self.index_to_key[i], float(sims[i])) for i in top]
 
+    def most_similar_batch(self, vectors, topn=10, exclude_keys=None, device=0):
+        """most_similar for a batch of query vectors [n, vector_size], on the device (libntf.Knn over self.vectors, made on first use and kept until close()):
+        per query a list of (key, sim), largest sim first, equal sims in index order.  exclude_keys (None, or one key or None per query) = a key never returned for
+        that query, as gensim drops the input keys of most_similar(positive=[key]).  A query with fewer than topn eligible keys gets a shorter list."""
+        v = np.ascontiguousarray(np.asarray(vectors, dtype=np.float32))
+        if v.ndim != 2 or v.shape[1] != self.vector_size:
+            raise ValueError(f"vectors must be [n, {self.vector_size}], got {v.shape}")
+        if not 1 <= int(topn) <= 2048:
+            raise ValueError(f"topn must be in 1..2048, got {topn}")
+        exclude = None
+        if exclude_keys is not None:
+            exclude_keys = list(exclude_keys)
+            if len(exclude_keys) != len(v):
+                raise ValueError(f"exclude_keys must hold one key (or None) per query: {len(exclude_keys)} != {len(v)}")
+            exclude = np.asarray([-1 if k is None else self.key_to_index[k] for k in exclude_keys], dtype=np.int64)
+        if len(v) == 0: return []
+        idx, sims = self.knn(device).query(v, topn=int(topn), exclude=exclude)
+        return [[(self.index_to_key[i], float(s)) for i, s in zip(ri.tolist(), rs.tolist()) if i >= 0] for ri, rs in zip(idx, sims)]
+
+    def knn(self, device=0):
+        """the device handle over self.vectors (libntf.Knn), made on first use - and again when self.vectors has been replaced or another device is asked for"""
+        from ... import libntf
+        if getattr(self, "_knn", None) is None or self._knn_of is not self.vectors or self._knn_device != int(device):
+            self.close()
+            self._knn = libntf.Knn(self.vectors, device=int(device)); self._knn_of = self.vectors; self._knn_device = int(device)
+        return self._knn
+
+    def close(self):
+        """frees the device handle most_similar_batch keeps"""
+        if getattr(self, "_knn", None) is not None:
+            self._knn.close()
+        self._knn = None; self._knn_of = None
+
 
 class Doc2VecTables:
     """what `self.model` is after learn(): .dv / .docvecs (doc tags '0'..'N-1'), .wv (words), .syn1neg and the hyper-parameters"""
@@ -345,10 +378,22 @@ class D2v(T2v):
         rows = np.arange(len(ptr) - 1) if rows is None else np.asarray(rows, dtype=np.int64)
         return self.infer_vecs([[key(int(w)) for w in words[ptr[i]:ptr[i + 1]]] for i in rows.tolist()])
 
+    def nearest_teams(self, docs, topn=10, init=None, ids=None):
+        """the batched counterpart of what infer_vec returns: infer_vecs(docs, init, ids), then the topn most similar known teams of every inferred vector
+        (the handle self.model.dv keeps for most_similar_batch: the table is on the device once), on the plugin's device - device 0 when it has none, as
+        infer_vecs.  -> (vecs [n, d] float32, idx [n, topn] int32 = rows of the doc-vector table, sims [n, topn] float32)"""
+        vecs = self.infer_vecs(docs, init=init, ids=ids)
+        if len(vecs) == 0: return vecs, np.zeros((0, int(topn)), np.int32), np.zeros((0, int(topn)), np.float32)
+        device = parse_devices(self.device)[0] if getattr(self, "device", None) is not None else 0
+        idx, sims = self.model.dv.knn(device).query(vecs, topn=int(topn))
+        return vecs, idx, sims
+
     def close(self):
-        """frees the device handle infer_vecs keeps"""
+        """frees the device handles infer_vecs and nearest_teams (self.model.dv's) keep"""
         if getattr(self, "_infer_net", None) is not None:
             self._infer_net.close(); self._infer_net = None
+        dv = getattr(getattr(self, "model", None), "dv", None)
+        if dv is not None: dv.close()
 
     @staticmethod
     def natsortvecs(d2v_model_wv):
