@@ -9,6 +9,7 @@
 // adds commute, so the result does not depend on how the counting is scheduled.
 #include "../../include/opentf_amd.h"
 #include "ntf_kernels.h"
+#include "ntf_host.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -169,18 +170,10 @@ struct AucState {
     unsigned __int128 total = 0;
     uint32_t S = 0, step0 = 0, stride = 1;
     bool lds_hist = false;
-    uint32_t *dv = nullptr, *dpiv = nullptr, *dflag = nullptr;
-    unsigned long long* dcnt = nullptr;
+    DevBuf dv, dpiv, dflag, dcnt;       // u32 keys, u32 pivots, one u32 flag, 2 G + 1 u64 counters
 };
 
-void auc_free(AucState* s) {
-    if (!s) return;
-    if (s->dv) hipFree(s->dv);
-    if (s->dpiv) hipFree(s->dpiv);
-    if (s->dflag) hipFree(s->dflag);
-    if (s->dcnt) hipFree(s->dcnt);
-    delete s;
-}
+void auc_free(AucState* s) { delete s; }
 
 int auc_check(uint64_t P, int64_t n, int64_t M, uint64_t* N_out) {
     const unsigned __int128 total = (unsigned __int128)n * M;
@@ -212,12 +205,8 @@ int auc_open(hipStream_t st, const uint32_t* pos_keys, size_t n_pos, int64_t n, 
     if (s->S) for (s->step0 = 1; s->step0 * 2 <= s->S; s->step0 <<= 1) {}
     const size_t nb = 2 * G + 1;
     s->lds_hist = nb <= (size_t)AUC_LDS_BUCKETS;
-    auto put = [](uint32_t** d, const void* host, size_t bytes) {
-        return hipMalloc((void**)d, bytes ? bytes : 16) == hipSuccess && (!bytes || hipMemcpy(*d, host, bytes, hipMemcpyHostToDevice) == hipSuccess);
-    };
-    if (!put(&s->dv, v.data(), G * 4) || !put(&s->dpiv, piv.data(), (size_t)s->S * 4) || hipMalloc((void**)&s->dcnt, nb * 8) != hipSuccess ||
-        hipMalloc((void**)&s->dflag, 16) != hipSuccess) { auc_free(s); return NTF_ENOMEM; }
-    if (hipMemsetAsync(s->dcnt, 0, nb * 8, st) != hipSuccess || hipMemsetAsync(s->dflag, 0, 4, st) != hipSuccess) { auc_free(s); return NTF_EHIP; }
+    if (!s->dv.put(v.data(), G * 4) || !s->dpiv.put(piv.data(), (size_t)s->S * 4) || !s->dcnt.alloc(nb * 8) || !s->dflag.alloc(16)) { auc_free(s); return NTF_ENOMEM; }
+    if (hipMemsetAsync(s->dcnt.p, 0, nb * 8, st) != hipSuccess || hipMemsetAsync(s->dflag.p, 0, 4, st) != hipSuccess) { auc_free(s); return NTF_EHIP; }
     *out = s;
     return NTF_OK;
 }
@@ -230,11 +219,11 @@ int auc_count(AucState* s, hipStream_t st, const float* x, int64_t L) {
     const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>(want, 1), AUC_MAX_BLOCKS);
     const uint32_t G = (uint32_t)s->v.size();
     if (s->lds_hist)
-        hipLaunchKernelGGL(k_auc_count<true>, dim3(blocks), dim3(AUC_THREADS), 0, st, (const uint32_t*)x, L, (const uint32_t*)s->dv, G,
-                           (const uint32_t*)s->dpiv, s->S, s->step0, s->stride, s->dcnt, s->dflag);
+        hipLaunchKernelGGL(k_auc_count<true>, dim3(blocks), dim3(AUC_THREADS), 0, st, (const uint32_t*)x, L, s->dv.as<const uint32_t>(), G,
+                           s->dpiv.as<const uint32_t>(), s->S, s->step0, s->stride, s->dcnt.as<unsigned long long>(), s->dflag.as<uint32_t>());
     else
-        hipLaunchKernelGGL(k_auc_count<false>, dim3(blocks), dim3(AUC_THREADS), 0, st, (const uint32_t*)x, L, (const uint32_t*)s->dv, G,
-                           (const uint32_t*)s->dpiv, s->S, s->step0, s->stride, s->dcnt, s->dflag);
+        hipLaunchKernelGGL(k_auc_count<false>, dim3(blocks), dim3(AUC_THREADS), 0, st, (const uint32_t*)x, L, s->dv.as<const uint32_t>(), G,
+                           s->dpiv.as<const uint32_t>(), s->S, s->step0, s->stride, s->dcnt.as<unsigned long long>(), s->dflag.as<uint32_t>());
     return hipGetLastError() == hipSuccess ? NTF_OK : NTF_EHIP;
 }
 
@@ -246,7 +235,7 @@ int auc_finish(AucState* s, hipStream_t st, uint64_t implicit_zeros, uint64_t ou
     std::vector<uint64_t> cnt(nb);
     uint32_t flag = 0;
     if (hipStreamSynchronize(st) != hipSuccess) return NTF_EHIP;
-    if (hipMemcpy(cnt.data(), s->dcnt, nb * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&flag, s->dflag, 4, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
+    if (hipMemcpy(cnt.data(), s->dcnt.p, nb * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&flag, s->dflag.p, 4, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
     if (flag) return NTF_EINVAL;                                                           // a NaN score
     if (implicit_zeros) {
         uint32_t nan = 0;
@@ -276,13 +265,6 @@ int auc_finish(AucState* s, hipStream_t st, uint64_t implicit_zeros, uint64_t ou
 using namespace ntf;
 
 namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess; }
-    bool put(const void* host, size_t bytes) { return alloc(bytes) && (!bytes || hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) == hipSuccess); }
-};
-
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 // the truth side of both entries: validates it and lists the positives as (instance, column)

@@ -13,9 +13,11 @@
 // Results are what scipy returns after sort_indices(): counts in uint8 arithmetic (wrap mod 256), entries whose wrapped count is 0
 // dropped (scipy's csr_matmat drops zero sums), column ids ascending inside a row.  Bit-exact by construction (integer work).
 #include "../../include/opentf_amd.h"
-#include <hip/hip_runtime.h>
+#include "ntf_host.h"
 #include <algorithm>
 #include <vector>
+
+using ntf::DevBuf;
 
 namespace {
 
@@ -196,20 +198,9 @@ __global__ __launch_bounds__(256) void k_cooc_compact(int n_experts, const uint3
     for (uint32_t i = lane; i < n; i += 64) { out_ix[dst + i] = tmp_ix[src + i]; out_val[dst + i] = tmp_val[src + i]; }
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) hipFree(p); }
-    bool alloc(size_t bytes, bool zero = false) {
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { p = nullptr; return false; }
-        return !zero || hipMemset(p, 0, bytes ? bytes : 16) == hipSuccess;
-    }
-    bool put(const void* host, size_t bytes) { return alloc(bytes) && (!bytes || hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) == hipSuccess); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
 bool scan_u32(const uint32_t* in, int64_t n, int64_t* out /*[n+1]*/) {
     const int64_t nb = std::max<int64_t>(1, (n + SCAN_BLOCK - 1) / SCAN_BLOCK);
-    Buf sums;
+    DevBuf sums;
     if (!sums.alloc((size_t)(nb + 1) * 8)) return false;
     hipLaunchKernelGGL(k_scan_block_sums, dim3((unsigned)nb), dim3(256), 0, 0, in, n, sums.as<int64_t>());
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, 0, sums.as<int64_t>(), nb);
@@ -222,7 +213,7 @@ bool scan_u32(const uint32_t* in, int64_t n, int64_t* out /*[n+1]*/) {
 struct ntf_csr_result {
     int device = 0;
     int64_t n_rows = 0, nnz = 0;
-    int64_t* indptr = nullptr; int32_t* indices = nullptr; uint8_t* data = nullptr;   // device
+    DevBuf indptr, indices, data;                                                        // device: int64 [n_rows + 1], int32 [nnz], uint8 [nnz]
     double ms = 0;                                                                       // device time of the build (HIP events)
 };
 
@@ -242,7 +233,7 @@ extern "C" int ntf_skill_cooccurrence(int device, int64_t n_teams, int32_t n_mem
         for (int64_t i = 0; i < n_skip; ++i) { if (skip_rows[i] < 0 || skip_rows[i] >= n_teams) return NTF_EINVAL; skip[(size_t)skip_rows[i]] = 1; }
     }
     if (hipSetDevice(device) != hipSuccess) return NTF_EHIP;
-    Buf mip, mix, sip, six, dskip, work, cursor, wstart, seg, tix, tval, rlen, biglist, bigcount, scratch;
+    DevBuf mip, mix, sip, six, dskip, work, cursor, wstart, seg, tix, tval, rlen, biglist, bigcount, scratch;
     if (!mip.put(m_indptr, (size_t)(n_teams + 1) * 8) || !mix.put(m_indices, (size_t)m_nnz * 4) || !sip.put(s_indptr, (size_t)(n_teams + 1) * 8) ||
         !six.put(s_indices, (size_t)s_nnz * 4) || (n_skip && !dskip.put(skip.data(), (size_t)n_teams)) || !work.alloc((size_t)n_members * 4, true) ||
         !cursor.alloc((size_t)n_members * 4, true) || !wstart.alloc((size_t)(n_members + 1) * 8) || !rlen.alloc((size_t)n_members * 4, true) ||
@@ -271,14 +262,12 @@ extern "C" int ntf_skill_cooccurrence(int device, int64_t n_teams, int32_t n_mem
     }
     ntf_csr_result* r = new ntf_csr_result();
     r->device = device; r->n_rows = n_members;
-    if (hipMalloc(&r->indptr, (size_t)(n_members + 1) * 8) != hipSuccess) { delete r; return NTF_ENOMEM; }
-    if (!scan_u32(rlen.as<uint32_t>(), n_members, r->indptr) ||
-        hipMemcpy(&r->nnz, r->indptr + n_members, 8, hipMemcpyDeviceToHost) != hipSuccess) { hipFree(r->indptr); delete r; return NTF_EHIP; }
-    if (hipMalloc(&r->indices, (size_t)std::max<int64_t>(r->nnz, 4) * 4) != hipSuccess || hipMalloc(&r->data, (size_t)std::max<int64_t>(r->nnz, 16)) != hipSuccess) {
-        hipFree(r->indptr); if (r->indices) hipFree(r->indices); delete r; return NTF_ENOMEM;
-    }
+    if (!r->indptr.alloc((size_t)(n_members + 1) * 8)) { delete r; return NTF_ENOMEM; }
+    if (!scan_u32(rlen.as<uint32_t>(), n_members, r->indptr.as<int64_t>()) ||
+        hipMemcpy(&r->nnz, r->indptr.as<int64_t>() + n_members, 8, hipMemcpyDeviceToHost) != hipSuccess) { delete r; return NTF_EHIP; }
+    if (!r->indices.alloc((size_t)std::max<int64_t>(r->nnz, 4) * 4) || !r->data.alloc((size_t)std::max<int64_t>(r->nnz, 16))) { delete r; return NTF_ENOMEM; }
     hipLaunchKernelGGL(k_cooc_compact, dim3((unsigned)((n_members + 3) / 4)), dim3(256), 0, 0, n_members, rlen.as<uint32_t>(), wstart.as<int64_t>(),
-                       r->indptr, tix.as<int32_t>(), tval.as<uint8_t>(), r->indices, r->data);
+                       r->indptr.as<int64_t>(), tix.as<int32_t>(), tval.as<uint8_t>(), r->indices.as<int32_t>(), r->data.as<uint8_t>());
     hipEventRecord(ev1, 0);
     const hipError_t s = hipDeviceSynchronize();
     float ms = 0; hipEventElapsedTime(&ms, ev0, ev1); r->ms = ms;
@@ -292,9 +281,9 @@ extern "C" int ntf_skill_cooccurrence(int device, int64_t n_teams, int32_t n_mem
 extern "C" int ntf_csr_result_fetch(ntf_csr_result* r, int64_t* indptr, int32_t* indices, uint8_t* data, double* device_ms) {
     if (!r || !indptr) return NTF_EINVAL;
     if (hipSetDevice(r->device) != hipSuccess) return NTF_EHIP;
-    if (hipMemcpy(indptr, r->indptr, (size_t)(r->n_rows + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
-    if (r->nnz && indices && hipMemcpy(indices, r->indices, (size_t)r->nnz * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
-    if (r->nnz && data && hipMemcpy(data, r->data, (size_t)r->nnz, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
+    if (hipMemcpy(indptr, r->indptr.p, (size_t)(r->n_rows + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
+    if (r->nnz && indices && hipMemcpy(indices, r->indices.p, (size_t)r->nnz * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
+    if (r->nnz && data && hipMemcpy(data, r->data.p, (size_t)r->nnz, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
     if (device_ms) *device_ms = r->ms;
     return NTF_OK;
 }
@@ -302,8 +291,5 @@ extern "C" int ntf_csr_result_fetch(ntf_csr_result* r, int64_t* indptr, int32_t*
 extern "C" void ntf_csr_result_free(ntf_csr_result* r) {
     if (!r) return;
     hipSetDevice(r->device);
-    if (r->indptr) hipFree(r->indptr);
-    if (r->indices) hipFree(r->indices);
-    if (r->data) hipFree(r->data);
     delete r;
 }

@@ -12,6 +12,7 @@
 // the documents are spread over waves except through the order of the atomic adds, and a one-wave launch (`serial`) reproduces the oracle's sequential pass.
 #include "../../include/opentf_amd.h"
 #include "ntf_device.h"
+#include "ntf_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -33,13 +34,10 @@ struct ntf_d2v {
     uint64_t seed = 0;
     // ntf_d2v_infer: the queries of the last call (CSR, ids) and their vectors [n, dp] (initial on the way in, inferred on the way out); grown on demand
     int64_t *q_ptr = nullptr, *q_ids = nullptr; int32_t* q_words = nullptr; float* q_vec = nullptr;
-    int64_t q_cap = 0, q_words_cap = 0;
+    int64_t q_ptr_cap = 0, q_ids_cap = 0, q_words_cap = 0, q_vec_cap = 0;
     std::string err;
 };
 static thread_local std::string g_d2v_create_error;
-
-#define DCHK(h, call) do { hipError_t _s = (call); if (_s != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(_s); return NTF_EHIP; } } while (0)
-#define DFAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
 
 extern "C" const char* ntf_d2v_last_error(const ntf_d2v* h) { return h ? h->err.c_str() : g_d2v_create_error.c_str(); }
 
@@ -409,12 +407,6 @@ __global__ __launch_bounds__(256, NV <= 2 ? 6 : 5) void k_d2v_infer(D2vInferArgs
     }
 }
 
-template <typename T> int dalloc(ntf_d2v* h, T** p, int64_t n) {
-    *p = nullptr;
-    if (n <= 0) return NTF_OK;
-    if (hipMalloc((void**)p, (size_t)n * sizeof(T)) != hipSuccess) { h->err = "hipMalloc failed"; return NTF_ENOMEM; }
-    return NTF_OK;
-}
 }  // namespace
 
 extern "C" void ntf_d2v_destroy(ntf_d2v* h) {
@@ -451,20 +443,22 @@ extern "C" int ntf_d2v_create(int device, int64_t n_docs, int64_t n_vocab, int32
     int rc = NTF_OK;
     auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
     if (hipStreamCreate(&h->st) != hipSuccess) { g_d2v_create_error = "hipStreamCreate failed"; delete h; return NTF_EHIP; }
-    A(dalloc(h, &h->doc_ptr, n_docs + 1)); A(dalloc(h, &h->words, std::max<int64_t>(nw, 1))); A(dalloc(h, &h->sample_int, n_vocab)); A(dalloc(h, &h->cum_table, n_vocab));
-    A(dalloc(h, &h->dv, n_docs * dp)); A(dalloc(h, &h->wv, n_vocab * dp)); A(dalloc(h, &h->syn1neg, n_vocab * dp)); A(dalloc(h, &h->order, n_docs)); A(dalloc(h, &h->progress, n_docs)); A(dalloc(h, &h->d_loss, 2));
+    A(dev_alloc(h, &h->doc_ptr, n_docs + 1)); A(dev_alloc(h, &h->words, std::max<int64_t>(nw, 1))); A(dev_alloc(h, &h->sample_int, n_vocab)); A(dev_alloc(h, &h->cum_table, n_vocab));
+    A(dev_alloc(h, &h->dv, n_docs * dp)); A(dev_alloc(h, &h->wv, n_vocab * dp)); A(dev_alloc(h, &h->syn1neg, n_vocab * dp)); A(dev_alloc(h, &h->order, n_docs)); A(dev_alloc(h, &h->progress, n_docs)); A(dev_alloc(h, &h->d_loss, 2));
     if (rc != NTF_OK) { g_d2v_create_error = h->err; ntf_d2v_destroy(h); return rc; }
-    hipMemcpy(h->doc_ptr, doc_ptr, (n_docs + 1) * 8, hipMemcpyHostToDevice);
-    if (nw) hipMemcpy(h->words, words, nw * 4, hipMemcpyHostToDevice);
-    hipMemcpy(h->sample_int, sample_int, n_vocab * 4, hipMemcpyHostToDevice);
-    hipMemcpy(h->cum_table, cum_table, n_vocab * 4, hipMemcpyHostToDevice);
+    bool ok = true;
+    auto H = [&](hipError_t s) { ok = ok && s == hipSuccess; };
+    H(hipMemcpy(h->doc_ptr, doc_ptr, (n_docs + 1) * 8, hipMemcpyHostToDevice));
+    if (nw) H(hipMemcpy(h->words, words, nw * 4, hipMemcpyHostToDevice));
+    H(hipMemcpy(h->sample_int, sample_int, n_vocab * 4, hipMemcpyHostToDevice));
+    H(hipMemcpy(h->cum_table, cum_table, n_vocab * 4, hipMemcpyHostToDevice));
     // any vector size (the reference's CI trains d9 tables, data.embedding.d is free): rows of d floats at a stride of dp, the pad columns zero.  A zero column of
     // every table stays zero through every update (each update is a multiple of another table's same column), and adds nothing to a dot product
-    if (dp != d) { hipMemset(h->dv, 0, (size_t)n_docs * dp * 4); hipMemset(h->wv, 0, (size_t)n_vocab * dp * 4); }
-    hipMemcpy2D(h->dv, (size_t)dp * 4, init_dv, (size_t)d * 4, (size_t)d * 4, (size_t)n_docs, hipMemcpyHostToDevice);
-    hipMemcpy2D(h->wv, (size_t)dp * 4, init_wv, (size_t)d * 4, (size_t)d * 4, (size_t)n_vocab, hipMemcpyHostToDevice);
-    hipMemsetAsync(h->syn1neg, 0, (size_t)n_vocab * dp * 4, h->st);
-    if (hipStreamSynchronize(h->st) != hipSuccess) { g_d2v_create_error = "device initialisation failed"; ntf_d2v_destroy(h); return NTF_EHIP; }
+    H(upload_padded(h->dv, dp, init_dv, d, n_docs));
+    H(upload_padded(h->wv, dp, init_wv, d, n_vocab));
+    H(hipMemsetAsync(h->syn1neg, 0, (size_t)n_vocab * dp * 4, h->st));
+    H(hipStreamSynchronize(h->st));
+    if (!ok) { g_d2v_create_error = "device initialisation failed"; ntf_d2v_destroy(h); return NTF_EHIP; }
     *out = h;
     return NTF_OK;
 }
@@ -473,19 +467,19 @@ extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32
                                    const int64_t* order, const double* progress, double* mean_loss, double* device_ms) {
     if (!h || window < 1 || window > 255 || negative < 0 || negative > 8 || (dm != 0 && dm != 1)) return NTF_EINVAL;
     if (!dm && 2 * window > 254) return NTF_EINVAL;
-    DCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     if (order) {
         std::vector<char> seen((size_t)h->n_docs, 0);
-        for (int64_t i = 0; i < h->n_docs; ++i) { if (order[i] < 0 || order[i] >= h->n_docs || seen[(size_t)order[i]]) DFAIL(h, NTF_EINVAL, "d2v: order is not a permutation of the documents"); seen[(size_t)order[i]] = 1; }
-        DCHK(h, hipMemcpyAsync(h->order, order, h->n_docs * 8, hipMemcpyHostToDevice, h->st));
-        DCHK(h, hipStreamSynchronize(h->st));
+        for (int64_t i = 0; i < h->n_docs; ++i) { if (order[i] < 0 || order[i] >= h->n_docs || seen[(size_t)order[i]]) FAIL(h, NTF_EINVAL, "d2v: order is not a permutation of the documents"); seen[(size_t)order[i]] = 1; }
+        HIPCHK(h, hipMemcpyAsync(h->order, order, h->n_docs * 8, hipMemcpyHostToDevice, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
     }
     if (progress) {
-        for (int64_t i = 0; i < h->n_docs; ++i) if (!(progress[i] >= 0.0 && progress[i] <= 1.0)) DFAIL(h, NTF_EINVAL, "d2v: progress outside [0, 1]");
-        DCHK(h, hipMemcpyAsync(h->progress, progress, h->n_docs * 8, hipMemcpyHostToDevice, h->st));
-        DCHK(h, hipStreamSynchronize(h->st));
+        for (int64_t i = 0; i < h->n_docs; ++i) if (!(progress[i] >= 0.0 && progress[i] <= 1.0)) FAIL(h, NTF_EINVAL, "d2v: progress outside [0, 1]");
+        HIPCHK(h, hipMemcpyAsync(h->progress, progress, h->n_docs * 8, hipMemcpyHostToDevice, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
     }
-    DCHK(h, hipMemsetAsync(h->d_loss, 0, 16, h->st));
+    HIPCHK(h, hipMemsetAsync(h->d_loss, 0, 16, h->st));
     D2vArgs a;
     a.n_docs = h->n_docs; a.n_vocab = h->n_vocab; a.d = h->dp; a.window = window; a.negative = negative; a.serial = serial ? 1 : 0;
     a.doc_ptr = h->doc_ptr; a.words = h->words; a.sample_int = h->sample_int; a.cum_table = h->cum_table; a.order = order ? h->order : nullptr; a.progress = progress ? h->progress : nullptr;
@@ -494,7 +488,7 @@ extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32
     // parallel: enough waves to fill the chip several times over, each striding through the documents
     const int64_t want = (h->n_docs + 3) / 4;
     const dim3 grid(serial ? 1u : (unsigned)std::min<int64_t>(want, 256 * 16)), block(serial ? 64 : 256);
-    if (device_ms) { if (!h->ev0) { DCHK(h, hipEventCreate(&h->ev0)); DCHK(h, hipEventCreate(&h->ev1)); } DCHK(h, hipEventRecord(h->ev0, h->st)); }
+    if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
     // PV-DM at the reference's window (src/mdl/emb/__config__.yaml: w = 5): word-vector additions deferred to one per kept position (k_d2v_epoch<.., 5>); NTF_D2V_DEFER=0: the plain kernel
     static const bool defer_ok = !(getenv("NTF_D2V_DEFER") && atoi(getenv("NTF_D2V_DEFER")) == 0);
     if (dm && window == 5 && defer_ok && h->dp >= 128) {     // (d = 64: the rows are 256 B and the plain kernel's shorter chain wins - 45.7 against 49.4 ms; d = 128 / 192 / 256: 55 / 78 / 98 against 66 / 102 / 133)
@@ -510,14 +504,14 @@ extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32
         case 3: hipLaunchKernelGGL(k_d2v_epoch<3>, grid, block, 0, h->st, a, dm); break;
         default: hipLaunchKernelGGL(k_d2v_epoch<4>, grid, block, 0, h->st, a, dm); break;
     }
-    if (device_ms) DCHK(h, hipEventRecord(h->ev1, h->st));
+    if (device_ms) HIPCHK(h, hipEventRecord(h->ev1, h->st));
     hipError_t s = hipGetLastError();
-    if (s != hipSuccess) DFAIL(h, NTF_EHIP, std::string("d2v kernel launch: ") + hipGetErrorString(s));
-    DCHK(h, hipStreamSynchronize(h->st));
-    if (device_ms) { float ms = 0.f; DCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
+    if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("d2v kernel launch: ") + hipGetErrorString(s));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    if (device_ms) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
     if (mean_loss) {
         double l[2] = {0, 0};
-        DCHK(h, hipMemcpy(l, h->d_loss, 16, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(l, h->d_loss, 16, hipMemcpyDeviceToHost));
         *mean_loss = l[1] > 0 ? l[0] / l[1] : 0.0;
     }
     return NTF_OK;
@@ -526,41 +520,31 @@ extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32
 extern "C" int ntf_d2v_infer(ntf_d2v* h, int64_t n, const int64_t* q_ptr, const int32_t* q_words, const int64_t* ids, int32_t dm, int32_t window, int32_t negative, int32_t epochs,
                              double alpha, double min_alpha, uint64_t seed, int32_t serial, const float* init, float* out, double* device_ms) {
     if (!h) { g_d2v_create_error = "d2v infer: the handle is NULL"; return NTF_EINVAL; }
-    if (!q_ptr || !q_words || !init || !out) DFAIL(h, NTF_EINVAL, "d2v infer: q_ptr, q_words, init and out are required");
-    if (n < 1) DFAIL(h, NTF_EINVAL, "d2v infer: n < 1");
-    if (window < 1 || window > 255 || (!dm && 2 * window > 254)) DFAIL(h, NTF_EINVAL, "d2v infer: window outside 1..255 (dm = 0: 1..127), as ntf_d2v_train_epoch");
-    if (negative < 0 || negative > 8) DFAIL(h, NTF_EINVAL, "d2v infer: negative outside 0..8");
-    if (dm != 0 && dm != 1) DFAIL(h, NTF_EINVAL, "d2v infer: dm is 0 or 1");
-    if (epochs < 1) DFAIL(h, NTF_EINVAL, "d2v infer: epochs < 1");
-    if (!std::isfinite(alpha) || !std::isfinite(min_alpha)) DFAIL(h, NTF_EINVAL, "d2v infer: alpha / min_alpha not finite");
-    if (q_ptr[0] != 0) DFAIL(h, NTF_EINVAL, "d2v infer: q_ptr[0] != 0");
-    for (int64_t i = 0; i < n; ++i) if (q_ptr[i + 1] < q_ptr[i]) DFAIL(h, NTF_EINVAL, "d2v infer: q_ptr not monotone");
+    if (!q_ptr || !q_words || !init || !out) FAIL(h, NTF_EINVAL, "d2v infer: q_ptr, q_words, init and out are required");
+    if (n < 1) FAIL(h, NTF_EINVAL, "d2v infer: n < 1");
+    if (window < 1 || window > 255 || (!dm && 2 * window > 254)) FAIL(h, NTF_EINVAL, "d2v infer: window outside 1..255 (dm = 0: 1..127), as ntf_d2v_train_epoch");
+    if (negative < 0 || negative > 8) FAIL(h, NTF_EINVAL, "d2v infer: negative outside 0..8");
+    if (dm != 0 && dm != 1) FAIL(h, NTF_EINVAL, "d2v infer: dm is 0 or 1");
+    if (epochs < 1) FAIL(h, NTF_EINVAL, "d2v infer: epochs < 1");
+    if (!std::isfinite(alpha) || !std::isfinite(min_alpha)) FAIL(h, NTF_EINVAL, "d2v infer: alpha / min_alpha not finite");
+    if (q_ptr[0] != 0) FAIL(h, NTF_EINVAL, "d2v infer: q_ptr[0] != 0");
+    for (int64_t i = 0; i < n; ++i) if (q_ptr[i + 1] < q_ptr[i]) FAIL(h, NTF_EINVAL, "d2v infer: q_ptr not monotone");
     const int64_t nw = q_ptr[n];
-    for (int64_t p = 0; p < nw; ++p) if (q_words[p] < 0 || q_words[p] >= h->n_vocab) DFAIL(h, NTF_EINVAL, "d2v infer: word index out of the vocabulary");
-    DCHK(h, hipSetDevice(h->device));
-    DCHK(h, hipStreamSynchronize(h->st));
+    for (int64_t p = 0; p < nw; ++p) if (q_words[p] < 0 || q_words[p] >= h->n_vocab) FAIL(h, NTF_EINVAL, "d2v infer: word index out of the vocabulary");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     const int64_t dp = h->dp; const int d = h->d;
-    if (n > h->q_cap) {
-        for (void* p : {(void*)h->q_ptr, (void*)h->q_ids, (void*)h->q_vec}) if (p) hipFree(p);
-        h->q_ptr = nullptr; h->q_ids = nullptr; h->q_vec = nullptr; h->q_cap = 0;
+    {
         int rc = NTF_OK;
         auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
-        A(dalloc(h, &h->q_ptr, n + 1)); A(dalloc(h, &h->q_ids, n)); A(dalloc(h, &h->q_vec, n * dp));
+        A(dev_grow(h, &h->q_ptr, &h->q_ptr_cap, n + 1)); A(dev_grow(h, &h->q_ids, &h->q_ids_cap, n)); A(dev_grow(h, &h->q_vec, &h->q_vec_cap, n * dp));
+        A(dev_grow(h, &h->q_words, &h->q_words_cap, std::max<int64_t>(nw, 1)));
         if (rc != NTF_OK) return rc;
-        h->q_cap = n;
     }
-    if (std::max<int64_t>(nw, 1) > h->q_words_cap) {
-        if (h->q_words) hipFree(h->q_words);
-        h->q_words = nullptr; h->q_words_cap = 0;
-        const int rc = dalloc(h, &h->q_words, std::max<int64_t>(nw, 1));
-        if (rc != NTF_OK) return rc;
-        h->q_words_cap = std::max<int64_t>(nw, 1);
-    }
-    DCHK(h, hipMemcpy(h->q_ptr, q_ptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
-    if (nw) DCHK(h, hipMemcpy(h->q_words, q_words, (size_t)nw * 4, hipMemcpyHostToDevice));
-    if (ids) DCHK(h, hipMemcpy(h->q_ids, ids, (size_t)n * 8, hipMemcpyHostToDevice));
-    if (dp != d) DCHK(h, hipMemset(h->q_vec, 0, (size_t)n * dp * 4));       // the pad columns zero, as the tables'
-    DCHK(h, hipMemcpy2D(h->q_vec, (size_t)dp * 4, init, (size_t)d * 4, (size_t)d * 4, (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->q_ptr, q_ptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+    if (nw) HIPCHK(h, hipMemcpy(h->q_words, q_words, (size_t)nw * 4, hipMemcpyHostToDevice));
+    if (ids) HIPCHK(h, hipMemcpy(h->q_ids, ids, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, upload_padded(h->q_vec, dp, init, d, n));       // the pad columns zero, as the tables'
     D2vInferArgs a;
     a.n = n; a.n_vocab = h->n_vocab; a.d = h->dp; a.window = window; a.negative = negative; a.serial = serial ? 1 : 0; a.dm = dm; a.epochs = epochs;
     a.q_ptr = h->q_ptr; a.q_words = h->q_words; a.ids = ids ? h->q_ids : nullptr; a.sample_int = h->sample_int; a.cum_table = h->cum_table;
@@ -568,38 +552,38 @@ extern "C" int ntf_d2v_infer(ntf_d2v* h, int64_t n, const int64_t* q_ptr, const 
     a.alpha = alpha; a.delta = (alpha - min_alpha) / (double)std::max(epochs - 1, 1); a.seed = seed;
     const int64_t want = (n + 3) / 4;
     const dim3 grid(serial ? 1u : (unsigned)std::min<int64_t>(want, 256 * 16)), block(serial ? 64 : 256);
-    if (device_ms) { if (!h->ev0) { DCHK(h, hipEventCreate(&h->ev0)); DCHK(h, hipEventCreate(&h->ev1)); } DCHK(h, hipEventRecord(h->ev0, h->st)); }
+    if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
     switch (h->dp / 64) {
         case 1: hipLaunchKernelGGL(k_d2v_infer<1>, grid, block, 0, h->st, a); break;
         case 2: hipLaunchKernelGGL(k_d2v_infer<2>, grid, block, 0, h->st, a); break;
         case 3: hipLaunchKernelGGL(k_d2v_infer<3>, grid, block, 0, h->st, a); break;
         default: hipLaunchKernelGGL(k_d2v_infer<4>, grid, block, 0, h->st, a); break;
     }
-    if (device_ms) DCHK(h, hipEventRecord(h->ev1, h->st));
+    if (device_ms) HIPCHK(h, hipEventRecord(h->ev1, h->st));
     hipError_t s = hipGetLastError();
-    if (s != hipSuccess) DFAIL(h, NTF_EHIP, std::string("d2v infer kernel launch: ") + hipGetErrorString(s));
-    DCHK(h, hipStreamSynchronize(h->st));
-    if (device_ms) { float ms = 0.f; DCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
-    DCHK(h, hipMemcpy2D(out, (size_t)d * 4, h->q_vec, (size_t)dp * 4, (size_t)d * 4, (size_t)n, hipMemcpyDeviceToHost));
+    if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("d2v infer kernel launch: ") + hipGetErrorString(s));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    if (device_ms) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
+    HIPCHK(h, hipMemcpy2D(out, (size_t)d * 4, h->q_vec, (size_t)dp * 4, (size_t)d * 4, (size_t)n, hipMemcpyDeviceToHost));
     return NTF_OK;
 }
 
 extern "C" int ntf_d2v_get(ntf_d2v* h, int what, float* host) {   // what: 0 = doc vectors [n_docs, d], 1 = word vectors [n_vocab, d], 2 = syn1neg [n_vocab, d]
     if (!h || !host || what < 0 || what > 2) return NTF_EINVAL;
-    DCHK(h, hipSetDevice(h->device));
-    DCHK(h, hipStreamSynchronize(h->st));
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     const float* src = what == 0 ? h->dv : what == 1 ? h->wv : h->syn1neg;
     const int64_t rows = what == 0 ? h->n_docs : h->n_vocab;
-    DCHK(h, hipMemcpy2D(host, (size_t)h->d * 4, src, (size_t)h->dp * 4, (size_t)h->d * 4, (size_t)rows, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy2D(host, (size_t)h->d * 4, src, (size_t)h->dp * 4, (size_t)h->d * 4, (size_t)rows, hipMemcpyDeviceToHost));
     return NTF_OK;
 }
 
 extern "C" int ntf_d2v_set(ntf_d2v* h, int what, const float* host) {   // resume from a saved table (same `what` as ntf_d2v_get)
     if (!h || !host || what < 0 || what > 2) return NTF_EINVAL;
-    DCHK(h, hipSetDevice(h->device));
-    DCHK(h, hipStreamSynchronize(h->st));
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     float* dst = what == 0 ? h->dv : what == 1 ? h->wv : h->syn1neg;
     const int64_t rows = what == 0 ? h->n_docs : h->n_vocab;
-    DCHK(h, hipMemcpy2D(dst, (size_t)h->dp * 4, host, (size_t)h->d * 4, (size_t)h->d * 4, (size_t)rows, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy2D(dst, (size_t)h->dp * 4, host, (size_t)h->d * 4, (size_t)h->d * 4, (size_t)rows, hipMemcpyHostToDevice));
     return NTF_OK;
 }

@@ -4,6 +4,8 @@
 #include "ntf_kernels.h"
 #include "ntf_fused.h"
 #include "ntf_head.h"
+#include "ntf_host.h"
+#include "ntf_select.h"
 
 #include <algorithm>
 #include <cmath>
@@ -150,7 +152,7 @@ struct ntf_engine {
     int (*cb_fn)(int32_t, void*) = nullptr; void* cb_user = nullptr;   // ntf_step_staged_deferred_cb -> the step's StepCtx
     bool pend_valid = false; FusedDw pend; NormalSpec pend_eps_b; float pend_klw_b = 0.f; int pend_chunks = 0;
     // unigram_b staging (sparse per-batch alias table)
-    std::vector<int32_t> ub_entries; void* ub_host[2] = {nullptr, nullptr}; void* ub_dev[2] = {nullptr, nullptr}; hipEvent_t ub_ev[2] = {nullptr, nullptr};
+    std::vector<int32_t> ub_entries; void* ub_host[2] = {nullptr, nullptr}; char* ub_dev[2] = {nullptr, nullptr}; hipEvent_t ub_ev[2] = {nullptr, nullptr};
     bool ub_used[2] = {false, false}; size_t ub_cap = 0; int ub_slot = 0; int ub_nsup[2] = {0, 0}; double ub_total[2] = {0, 0};
     uint16_t* pl_mu = nullptr; uint16_t* pl_wp = nullptr;   // fp16 split planes of the output layer's mu / Wp (fp16x3 arithmetic)
     hipStream_t st2 = nullptr;        // side stream: Adam of finished expert chunks runs beside the dW kernel of the next chunk
@@ -164,15 +166,6 @@ struct ntf_engine {
     int ep_open = 0; StepCtx ep_ctx;        // the ntf_step_staged_ep phase that ran last (0: none pending)
 };
 
-#define HIPCHK(e, call)                                                                                   \
-    do {                                                                                                  \
-        hipError_t _s = (call);                                                                           \
-        if (_s != hipSuccess) {                                                                           \
-            (e)->err = std::string(#call) + ": " + hipGetErrorString(_s);                                 \
-            return NTF_EHIP;                                                                              \
-        }                                                                                                 \
-    } while (0)
-#define FAIL(e, code, msg) do { (e)->err = (msg); return (code); } while (0)
 static int join_side(ntf_engine* e);
 
 struct Scope {
@@ -216,14 +209,7 @@ static void make_key(const ntf_engine* e, uint64_t step, int layer, int tensor, 
 }
 enum { T_EPS_W = 0, T_EPS_B = 1, T_S_IN = 2, T_S_OUT = 3, T_NEG = 4 };
 
-template <typename T> static int dmalloc(ntf_engine* e, T** p, int64_t n) {
-    *p = nullptr;
-    if (n <= 0) return NTF_OK;
-    hipError_t s = hipMalloc((void**)p, (size_t)n * sizeof(T));
-    if (s != hipSuccess) { e->err = std::string("hipMalloc: ") + hipGetErrorString(s); return NTF_ENOMEM; }
-    return NTF_OK;
-}
-#define DM(e, p, n) do { int _r = dmalloc(e, p, n); if (_r) return _r; } while (0)
+#define DM(e, p, n) do { int _r = dev_alloc(e, p, n); if (_r) return _r; } while (0)
 template <typename T> static void dfree(T*& p) { if (p) { hipFree(p); p = nullptr; } }
 
 extern "C" int ntf_abi_version(void) { return NTF_ABI_VERSION; }
@@ -310,25 +296,25 @@ extern "C" int ntf_engine_create(const ntf_config* cfg, ntf_engine** out) {
     const int B = cfg->max_batch, M = cfg->dims[e->L];
     int rc = NTF_OK;
     auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
-    A(dmalloc(e, &e->P, off)); A(dmalloc(e, &e->G, off)); A(dmalloc(e, &e->M1, off)); A(dmalloc(e, &e->V2, off));
-    A(dmalloc(e, &e->d_rows, B)); for (int k = 0; k < 2; ++k) A(dmalloc(e, &e->d_neg_set[k], (int64_t)B * std::max(1, cfg->ns)));
+    A(dev_alloc(e, &e->P, off)); A(dev_alloc(e, &e->G, off)); A(dev_alloc(e, &e->M1, off)); A(dev_alloc(e, &e->V2, off));
+    A(dev_alloc(e, &e->d_rows, B)); for (int k = 0; k < 2; ++k) A(dev_alloc(e, &e->d_neg_set[k], (int64_t)B * std::max(1, cfg->ns)));
     e->act.assign(e->L, nullptr);
-    for (int l = (cfg->input_mode == NTF_INPUT_MULTIHOT ? 1 : 0); l < e->L; ++l) A(dmalloc(e, &e->act[l], (int64_t)B * cfg->dims[l]));  // multi-hot X is never dense
-    A(dmalloc(e, &e->Zout, (int64_t)B * M)); A(dmalloc(e, &e->dZout, (int64_t)((M + 255) / 256 * 256) * fused_ldb(B)));
-    if (e->maxhid) { A(dmalloc(e, &e->Zh, (int64_t)B * e->maxhid)); A(dmalloc(e, &e->dAct[0], (int64_t)B * e->maxhid)); A(dmalloc(e, &e->dAct[1], (int64_t)B * e->maxhid)); }
+    for (int l = (cfg->input_mode == NTF_INPUT_MULTIHOT ? 1 : 0); l < e->L; ++l) A(dev_alloc(e, &e->act[l], (int64_t)B * cfg->dims[l]));  // multi-hot X is never dense
+    A(dev_alloc(e, &e->Zout, (int64_t)B * M)); A(dev_alloc(e, &e->dZout, (int64_t)((M + 255) / 256 * 256) * fused_ldb(B)));
+    if (e->maxhid) { A(dev_alloc(e, &e->Zh, (int64_t)B * e->maxhid)); A(dev_alloc(e, &e->dAct[0], (int64_t)B * e->maxhid)); A(dev_alloc(e, &e->dAct[1], (int64_t)B * e->maxhid)); }
     e->Wp.assign(e->L, nullptr); e->bp.assign(e->L, nullptr);
-    if (cfg->bayesian) for (int l = 0; l < e->L; ++l) { A(dmalloc(e, &e->Wp[l], e->layers[l].nw())); A(dmalloc(e, &e->bp[l], e->layers[l].out)); }
-    A(dmalloc(e, &e->partial, (int64_t)B * std::max(loss_dense_nchunk(M), fused_loss_slots(M)))); A(dmalloc(e, &e->row_fix, B));
-    if (cfg->bayesian && cfg->input_mode == NTF_INPUT_MULTIHOT) A(dmalloc(e, &e->l0_touched, (int64_t)(cfg->dims[0] + 255) / 256 * 256));
-    A(dmalloc(e, &e->d_loss, 4)); A(dmalloc(e, &e->d_kl, 4)); A(dmalloc(e, &e->d_chain, 2)); A(dmalloc(e, &e->d_acc, 2)); A(dmalloc(e, &e->d_acc_steps, 2));
-    A(dmalloc(e, &e->ent_mc, B)); A(dmalloc(e, &e->ent_mean, B)); A(dmalloc(e, &e->gemm_slab, kGemmSlabFloats));
+    if (cfg->bayesian) for (int l = 0; l < e->L; ++l) { A(dev_alloc(e, &e->Wp[l], e->layers[l].nw())); A(dev_alloc(e, &e->bp[l], e->layers[l].out)); }
+    A(dev_alloc(e, &e->partial, (int64_t)B * std::max(loss_dense_nchunk(M), fused_loss_slots(M)))); A(dev_alloc(e, &e->row_fix, B));
+    if (cfg->bayesian && cfg->input_mode == NTF_INPUT_MULTIHOT) A(dev_alloc(e, &e->l0_touched, (int64_t)(cfg->dims[0] + 255) / 256 * 256));
+    A(dev_alloc(e, &e->d_loss, 4)); A(dev_alloc(e, &e->d_kl, 4)); A(dev_alloc(e, &e->d_chain, 2)); A(dev_alloc(e, &e->d_acc, 2)); A(dev_alloc(e, &e->d_acc_steps, 2));
+    A(dev_alloc(e, &e->ent_mc, B)); A(dev_alloc(e, &e->ent_mean, B)); A(dev_alloc(e, &e->gemm_slab, kGemmSlabFloats));
     if (rc == NTF_OK && fused_ok(e)) {
-        A(dmalloc(e, &e->dh_slab, fused_dh_slab_floats(B, e->layers[e->L - 1].in, M)));
-        for (int k = 0; k < 2; ++k) A(dmalloc(e, &e->fws_set[k], (int64_t)fused_workspace_bytes(B, e->layers[e->L - 1].in, M)));
+        A(dev_alloc(e, &e->dh_slab, fused_dh_slab_floats(B, e->layers[e->L - 1].in, M)));
+        for (int k = 0; k < 2; ++k) A(dev_alloc(e, &e->fws_set[k], (int64_t)fused_workspace_bytes(B, e->layers[e->L - 1].in, M)));
         e->fws = e->fws_set[0];
         if (cfg->mfma != NTF_MFMA_F32 && e->layers[e->L - 1].in == 128) {
-            A(dmalloc(e, &e->pl_mu, fused_planes_elems(M, 128)));
-            if (cfg->bayesian) A(dmalloc(e, &e->pl_wp, fused_planes_elems(M, 128)));
+            A(dev_alloc(e, &e->pl_mu, fused_planes_elems(M, 128)));
+            if (cfg->bayesian) A(dev_alloc(e, &e->pl_wp, fused_planes_elems(M, 128)));
             if (rc == NTF_OK) { hipMemsetAsync(e->pl_mu, 0, (size_t)fused_planes_elems(M, 128) * 2, e->st); if (e->pl_wp) hipMemsetAsync(e->pl_wp, 0, (size_t)fused_planes_elems(M, 128) * 2, e->st); }
         }
     }
@@ -740,7 +726,7 @@ static int sample_negatives(ntf_engine* e, const StepCtx& c) {
         launch_ns_alias(e->st, c.rows_dev, c.B, M, e->cfg.ns, e->m_indptr, e->m_indices, e->al_prob, e->al_alias, e->al_weight, e->al_total, e->al_weighted,
                         k0, k1, (uint32_t)c.step, c.row0, e->d_neg_set[c.step & 1]);
     } else if (e->cfg.nsd == NTF_NSD_UNIGRAM_B) {
-        const char* d = static_cast<const char*>(e->ub_dev[c.ub]);
+        const char* d = e->ub_dev[c.ub];
         const size_t n = (size_t)e->ub_nsup[c.ub];
         launch_ns_alias_sparse(e->st, c.rows_dev, c.B, M, e->cfg.ns, e->m_indptr, e->m_indices, reinterpret_cast<const int32_t*>(d),
                                reinterpret_cast<const float*>(d + n * 8), reinterpret_cast<const int32_t*>(d + n * 4),
@@ -780,7 +766,7 @@ static int set_batch_unigram(ntf_engine* e, const int64_t* global_rows_host, int
         e->hp.ub = -1;
         for (int k = 0; k < 2; ++k) { if (e->ub_host[k]) hipHostFree(e->ub_host[k]); if (e->ub_dev[k]) hipFree(e->ub_dev[k]); e->ub_host[k] = nullptr; e->ub_dev[k] = nullptr; }
         e->ub_cap = need * 2;
-        for (int k = 0; k < 2; ++k) { HIPCHK(e, hipHostMalloc(&e->ub_host[k], e->ub_cap, hipHostMallocDefault)); HIPCHK(e, hipMalloc(&e->ub_dev[k], e->ub_cap)); }
+        for (int k = 0; k < 2; ++k) { HIPCHK(e, hipHostMalloc(&e->ub_host[k], e->ub_cap, hipHostMallocDefault)); DM(e, &e->ub_dev[k], (int64_t)e->ub_cap); }
         if (!e->ub_ev[0]) { HIPCHK(e, hipEventCreateWithFlags(&e->ub_ev[0], hipEventDisableTiming)); HIPCHK(e, hipEventCreateWithFlags(&e->ub_ev[1], hipEventDisableTiming)); }
         e->ub_used[0] = e->ub_used[1] = false;
     }
@@ -1997,11 +1983,11 @@ extern "C" int ntf_forward_topk(ntf_engine* e, const int64_t* rows, int32_t B, i
                                 int32_t* indices_host, float* pred_unc, float* model_unc) {
     if (!e || !values_host || !indices_host) return NTF_EINVAL;
     const int M = e->cfg.dims[e->L];
-    if (K < 1 || K > M || K > 2048) FAIL(e, NTF_EINVAL, "topk: K must be in [1, min(M, 2048)]");
+    if (K < 1 || K > M || K > SEL_MAX) FAIL(e, NTF_EINVAL, "topk: K must be in [1, min(M, 2048)]");
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int r = infer_probs(e, rows, B, nmc, nullptr, pred_unc || model_unc); if (r) return r;
     if (e->tk_cap < (int64_t)e->cfg.max_batch * K) { dfree(e->tk_vals); dfree(e->tk_idx); e->tk_cap = (int64_t)e->cfg.max_batch * K; DM(e, &e->tk_vals, e->tk_cap); DM(e, &e->tk_idx, e->tk_cap); }
-    { Scope t(e, F_INFER); launch_topk_rows(e->st, e->Pbuf, B, M, K, e->tk_vals, e->tk_idx, nullptr); }
+    { Scope t(e, F_INFER); launch_topk_rows(e->st, e->Pbuf, B, M, K, e->tk_vals, e->tk_idx); }
     HIPCHK(e, hipMemcpyAsync(values_host, e->tk_vals, (size_t)B * K * 4, hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipMemcpyAsync(indices_host, e->tk_idx, (size_t)B * K * 4, hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
@@ -2029,7 +2015,7 @@ extern "C" int ntf_score_rows(ntf_engine* e, const int64_t* rows, int64_t n, int
     if (!e) return NTF_EINVAL;
     if (e->ep) FAIL(e, NTF_ESTATE, "score_rows: an expert shard scores nothing on its own (whole-model engines only)");
     const int M = e->cfg.dims[e->L];
-    const int kcap = std::min(M, 2048);
+    const int kcap = std::min(M, SEL_MAX);
     const bool want_auc = out_counts != nullptr, want_out = out_vals || out_idx;
     if (!rows || n < 1 || B < 1 || B > e->cfg.max_batch || nmc < 1) FAIL(e, NTF_EINVAL, "score_rows: bad rows / n / B / nmc (B must be in [1, max_batch])");
     if (K < 0 || K > kcap) FAIL(e, NTF_EINVAL, "score_rows: K must be 0 (dense) or in [1, min(M, 2048)]");
@@ -2087,7 +2073,7 @@ extern "C" int ntf_score_rows(ntf_engine* e, const int64_t* rows, int64_t n, int
         const int b = (int)std::min<int64_t>(B, n - o);
         if ((r = infer_probs(e, rows + o, b, nmc, nullptr, false))) return r;
         Scope t(e, F_INFER);
-        if (R) launch_topk_rows(e->st, e->Pbuf, b, M, R, sb.vals + o * R, sb.idx + o * R, nullptr);
+        if (R) launch_topk_rows(e->st, e->Pbuf, b, M, R, sb.vals + o * R, sb.idx + o * R);
         if (want_auc && K == 0) launch_score_pos_keys_dense(e->st, e->Pbuf, b, M, sb.rows + o, e->m_indptr, e->m_indices, sb.slot + o, sb.keys, sb.nan);
     }
     const uint64_t step1 = e->step;
@@ -2138,7 +2124,7 @@ extern "C" int ntf_gather_meanpool(ntf_engine* e, const int64_t* rows, int64_t n
         for (int64_t i = 0; i < n; ++i) if (rows[i] < 0 || rows[i] >= e->s_rows) FAIL(e, NTF_EINVAL, "gather: row id out of range");
         DM(e, &drows, n); HIPCHK(e, hipMemcpy(drows, rows, n * 8, hipMemcpyHostToDevice));
     }
-    int rc = dmalloc(e, &dout, n * e->table_d);
+    int rc = dev_alloc(e, &dout, n * e->table_d);
     if (rc) { dfree(drows); return rc; }
     { Scope t(e, F_GATHER); launch_gather_meanpool(e->st, e->s_indptr, e->s_indices, e->table, drows, n, e->table_d, 1, dout); }
     hipError_t s = hipStreamSynchronize(e->st);

@@ -1,0 +1,60 @@
+// The host scaffold of every entry of the library, once: the check macros and allocators of a handle with an `err` string (ntf_engine, ntf_n2v, ntf_d2v,
+// ntf_knn), the RAII device buffer of the handle-less entries (ntf_metrics, ntf_auc, ntf_cooc) and the upload of a host table into padded device rows.
+#pragma once
+#include "../../include/opentf_amd.h"
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <string>
+
+#define HIPCHK(h, call)                                                                                   \
+    do {                                                                                                  \
+        hipError_t _s = (call);                                                                           \
+        if (_s != hipSuccess) {                                                                           \
+            (h)->err = std::string(#call) + ": " + hipGetErrorString(_s);                                 \
+            return NTF_EHIP;                                                                              \
+        }                                                                                                 \
+    } while (0)
+#define FAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
+
+namespace ntf {
+
+// n elements of T; n <= 0 gives a null pointer and NTF_OK
+template <class H, typename T> int dev_alloc(H* h, T** p, int64_t n) {
+    *p = nullptr;
+    if (n <= 0) return NTF_OK;
+    const hipError_t s = hipMalloc((void**)p, (size_t)n * sizeof(T));
+    if (s != hipSuccess) { *p = nullptr; h->err = std::string("hipMalloc: ") + hipGetErrorString(s); return NTF_ENOMEM; }
+    return NTF_OK;
+}
+// a buffer that only grows: at least n elements afterwards, the contents not kept
+template <class H, typename T> int dev_grow(H* h, T** p, int64_t* cap, int64_t n) {
+    if (n <= *cap) return NTF_OK;
+    if (*p) hipFree(*p);
+    *cap = 0;
+    const int rc = dev_alloc(h, p, n);
+    if (rc == NTF_OK) *cap = n;
+    return rc;
+}
+
+// a device buffer that lives as long as its owner; an empty request still allocates (16 bytes), so `p` is never null after a success
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) hipFree(p); }
+    bool alloc(size_t bytes, bool zero = false) {
+        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { p = nullptr; return false; }
+        return !zero || hipMemset(p, 0, bytes ? bytes : 16) == hipSuccess;
+    }
+    bool put(const void* host, size_t bytes) { return alloc(bytes) && (!bytes || hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) == hipSuccess); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// host table [rows, d] -> device rows of stride dp >= d floats; the pad columns are exact zeros (they add nothing to a dot product or a norm chain)
+inline hipError_t upload_padded(float* dst, int64_t dp, const float* src, int64_t d, int64_t rows) {
+    if (dp != d) { const hipError_t s = hipMemset(dst, 0, (size_t)rows * dp * 4); if (s != hipSuccess) return s; }
+    return hipMemcpy2D(dst, (size_t)dp * 4, src, (size_t)d * 4, (size_t)d * 4, (size_t)rows, hipMemcpyHostToDevice);
+}
+
+}  // namespace ntf

@@ -131,8 +131,7 @@ void launch_fill(hipStream_t st, float* p, int64_t n, float v);
 void launch_sigmoid_acc(hipStream_t st, const float* Act, int64_t n_rows, int M, float scale, int accumulate, float* out,
                         float* ent_rows /*nullable: per-row entropy of THIS pass*/);
 void launch_row_entropy(hipStream_t st, const float* P, int n_rows, int M, float* ent);
-void launch_topk_rows(hipStream_t st, const float* P, int n_rows, int M, int K, float* vals, int32_t* idx, void* workspace);
-size_t topk_workspace_bytes(int n_rows, int M, int K);
+void launch_topk_rows(hipStream_t st, const float* P, int n_rows, int M, int K, float* vals, int32_t* idx);   // K <= SEL_MAX (ntf_select.h)
 
 // ---- scoring a prediction set where it is produced (ntf_score_rows, ntf_engine.hip): the eval-stage kernels on device-resident data
 // ranking metrics (ntf_metrics.hip, k_rank_metrics) of n ranked lists topk [n, K] against the CSR truth rows rows[i]; every pointer is device memory; n_cut <= 8

@@ -4,6 +4,7 @@
 #include "ntf_kernels.h"
 #include <cstdlib>
 #include "ntf_device.h"
+#include "ntf_select.h"
 #include <algorithm>
 #include <cstdint>
 
@@ -977,121 +978,19 @@ void launch_row_entropy(hipStream_t st, const float* P, int n_rows, int M, float
 }
 
 // =====================================================================================
-// Row-wise top-K of the probabilities (src/pkgmgr.py:125-134 topk): per row a 3-pass radix select on the
-// f32 bit pattern (probabilities are positive, so the unsigned order is the value order) finds the K-th
-// value, then the row is compacted and the K survivors are sorted (descending value, ascending index for
-// ties) by a bitonic sort in LDS.  One workgroup per row.
+// Row-wise top-K of the probabilities (src/pkgmgr.py:125-134 topk): one workgroup per row runs the selection of ntf_select.h on the
+// f32 bit pattern (probabilities are non-negative) and stores the K survivors, descending value, ascending index for ties.
 // =====================================================================================
-constexpr int TK_MAX = 2048;
-constexpr int TK_SAMPLE = 4096;
-size_t topk_workspace_bytes(int, int, int) { return 0; }
-
-// descending bitonic sort of n2 (power of two) 64-bit keys in LDS by the whole workgroup
-__device__ __forceinline__ void bitonic_desc(unsigned long long* keys, int n2, int tid, int nthreads) {
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < n2 / 2; t += nthreads) {
-                const int lo = (t / stride) * stride * 2 + (t % stride), hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long a = keys[lo], b = keys[hi];
-                if ((a < b) == desc) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
-}
-
-// Probabilities of one row cluster in a few exponent bins, so an MSB-first radix histogram serialises on LDS atomics (measured: 19 ms
-// per 1000 rows of 233 629).  Instead: (1) a strided sample of TK_SAMPLE values is sorted in LDS and its r-th largest taken as a
-// threshold, r chosen so that ~4.5 K values of the row are expected above it; (2) one pass collects the values above the threshold
-// (a few hundred appends); (3) if at least K and at most TK_MAX were collected, the top K of the row are among them — every value >= the
-// K-th largest is above the threshold — and a bitonic sort on (value desc, column asc) finishes.  Otherwise (ties, tiny rows, unlucky
-// sample) the exact radix selection below runs.  The result is the same deterministic ranking either way.
 __global__ __launch_bounds__(1024) void k_topk_rows(const float* __restrict__ P, int M, int K, float* __restrict__ vals, int32_t* __restrict__ idx) {
-    __shared__ unsigned long long keys[TK_SAMPLE];      // sample sort, then the candidates (TK_MAX <= TK_SAMPLE)
-    __shared__ unsigned hist[2048];
-    __shared__ unsigned s_prefix, s_remaining, s_count;
+    __shared__ SelShared sh;
     const int64_t i = blockIdx.x;
-    const float* row = P + i * M;
-    const int tid = threadIdx.x, NT = blockDim.x;
-    int n2 = 1; while (n2 < K) n2 <<= 1;
-    bool done = false;
-    if (M >= 8 * TK_SAMPLE && K * 8 <= TK_MAX) {
-        const int stride = M / TK_SAMPLE;
-        for (int k = tid; k < TK_SAMPLE; k += NT) keys[k] = (unsigned long long)__float_as_uint(row[(int64_t)k * stride]);   // probabilities: non-negative, bit order = value order
-        __syncthreads();
-        bitonic_desc(keys, TK_SAMPLE, tid, NT);
-        // expected number of row values above the r-th largest sample value: r * M / TK_SAMPLE; aim at 4.5 K (>= K with overwhelming probability)
-        int r = (int)((4.5 * K * TK_SAMPLE) / M) + 1;
-        if (r < 8) r = 8;
-        const unsigned thr = (unsigned)keys[r < TK_SAMPLE ? r : TK_SAMPLE - 1];
-        __syncthreads();
-        if (tid == 0) s_count = 0;
-        __syncthreads();
-        for (int c = tid; c < M; c += NT) {
-            const unsigned u = __float_as_uint(row[c]);
-            if (u > thr) { const unsigned p = atomicAdd(&s_count, 1u); if (p < TK_MAX) keys[p] = ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - c); }
-        }
-        __syncthreads();
-        const unsigned cnt = s_count;
-        if (cnt >= (unsigned)K && cnt <= TK_MAX) {
-            int m2 = n2; while (m2 < (int)cnt) m2 <<= 1;
-            for (int k = cnt + tid; k < m2; k += NT) keys[k] = 0ull;
-            __syncthreads();
-            bitonic_desc(keys, m2, tid, NT);
-            done = true;
-        }
-        __syncthreads();
-    }
-    if (!done) {
-        unsigned prefix = 0, prefix_mask = 0, remaining = K;
-        // bits [31:21], [20:10], [9:0]
-        const int shifts[3] = {21, 10, 0};
-        const int widths[3] = {11, 11, 10};
-        for (int pass = 0; pass < 3; ++pass) {
-            const int sh = shifts[pass], nb = 1 << widths[pass];
-            for (int b = tid; b < nb; b += NT) hist[b] = 0;
-            __syncthreads();
-            for (int c = tid; c < M; c += NT) {
-                const unsigned u = __float_as_uint(row[c]);
-                if ((u & prefix_mask) == prefix) atomicAdd(&hist[(u >> sh) & (nb - 1)], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                unsigned rem = remaining; int b = nb - 1;
-                for (; b > 0; --b) { if (hist[b] >= rem) break; rem -= hist[b]; }
-                s_prefix = prefix | ((unsigned)b << sh); s_remaining = rem;
-            }
-            __syncthreads();
-            prefix = s_prefix; remaining = s_remaining;
-            prefix_mask |= (unsigned)(nb - 1) << sh;
-            __syncthreads();
-        }
-        // prefix = bit pattern of the K-th largest value; `remaining` = how many copies of it belong to the top K
-        if (tid == 0) s_count = 0;
-        for (int k = tid; k < TK_MAX; k += NT) keys[k] = 0ull;
-        __syncthreads();
-        const unsigned thr = prefix;
-        for (int c = tid; c < M; c += NT) {
-            const unsigned u = __float_as_uint(row[c]);
-            if (u > thr) { const unsigned p = atomicAdd(&s_count, 1u); keys[p] = ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - c); }
-        }
-        __syncthreads();
-        // ties at the threshold: smallest column ids first (deterministic)
-        if (tid == 0) {
-            unsigned need = remaining, p = s_count;
-            for (int c = 0; c < M && need > 0; ++c)
-                if (__float_as_uint(row[c]) == thr) { keys[p++] = ((unsigned long long)thr << 32) | (unsigned)(0x7fffffff - c); --need; }
-            s_count = p;
-        }
-        __syncthreads();
-        bitonic_desc(keys, n2, tid, NT);
-    }
-    for (int k = tid; k < K; k += NT) {
-        vals[i * K + k] = __uint_as_float((unsigned)(keys[k] >> 32));
-        idx[i * K + k] = 0x7fffffff - (int)(keys[k] & 0xffffffffu);
+    select_topk_row<ProbKey, false>(sh, P + i * M, M, K, 0, -1);
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+        vals[i * K + k] = ProbKey::value((unsigned)(sh.keys[k] >> 32));
+        idx[i * K + k] = 0x7fffffff - (int)(sh.keys[k] & 0xffffffffu);
     }
 }
-void launch_topk_rows(hipStream_t st, const float* P, int n_rows, int M, int K, float* vals, int32_t* idx, void*) {
+void launch_topk_rows(hipStream_t st, const float* P, int n_rows, int M, int K, float* vals, int32_t* idx) {
     hipLaunchKernelGGL(k_topk_rows, dim3(n_rows), dim3(1024), 0, st, P, M, K, vals, idx);
 }
 

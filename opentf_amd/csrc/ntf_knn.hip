@@ -9,6 +9,8 @@
 #include "../../include/opentf_amd.h"
 #include "ntf_device.h"
 #include "ntf_fused_common.h"
+#include "ntf_host.h"
+#include "ntf_select.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -31,9 +33,6 @@ struct ntf_knn {
 };
 static thread_local std::string g_knn_create_error;
 
-#define KCHK(h, call) do { hipError_t _s = (call); if (_s != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(_s); return NTF_EHIP; } } while (0)
-#define KFAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
-
 extern "C" const char* ntf_knn_last_error(const ntf_knn* h) { return h ? h->err.c_str() : g_knn_create_error.c_str(); }
 
 namespace {
@@ -44,8 +43,6 @@ constexpr int KNN_RB = KNN_WAVES * 32;   // table rows a workgroup takes at a ti
 constexpr int KNN_QUNIT = 32;            // the query unit of the workspace plan
 constexpr int KNN_MAX_GROUP = 1024;      // queries a group holds at most
 constexpr int64_t KNN_MAX_RANGE = 262144;   // rows a range holds at most: a selection workgroup walks one (query, range) row of sims
-constexpr int KNN_TOPN_MAX = 2048;
-constexpr int KNN_SAMPLE = 4096;
 
 // ---- reciprocal norms: n2 = one k-ordered fmaf chain from 0, rinv = 1 / sqrt(n2) (IEEE sqrt, IEEE divide), 0 when n2 < FLT_MIN.  flag |= 1: a non-finite value, |= 2: n2 overflows.
 // One thread a row keeps the chain sequential; the rows come through LDS in 32-float chunks so that the global reads are whole 128-B lines (8 lanes a row, 16 bytes each)
@@ -161,115 +158,17 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void k_knn_sims(KnnSimArgs a) {
     }
 }
 
-// ---- selection.  f32 bits -> unsigned key in value order (negative values: all bits flipped; others: the sign bit set); every real value's key is >= 1
-__device__ __forceinline__ unsigned knn_key(float v) { const unsigned u = __float_as_uint(v); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float knn_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-__device__ __forceinline__ void knn_bitonic_desc(unsigned long long* keys, int n2, int tid, int nthreads) {
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < n2 / 2; t += nthreads) {
-                const int lo = (t / stride) * stride * 2 + (t % stride), hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long x = keys[lo], y = keys[hi];
-                if ((x < y) == desc) { keys[lo] = y; keys[hi] = x; }
-            }
-            __syncthreads();
-        }
-}
-
 // One workgroup per query of the group: the K largest of its sims row S[q, 0 .. M) by the composite (key << 32) | (0x7fffffff - id), id = r0 + column, the
-// excluded id left out - k_topk_rows' two routes (a sorted sample's threshold, one collecting pass, a bitonic sort; else an exact 3-pass radix selection) on signed
-// values - then merged with the query's running list (first = 0) by the same composite: a total order, so the merge is exact and the order of the ranges free.
-// A composite of 0 is an empty slot.
+// excluded id left out (the selection of ntf_select.h on signed values), then merged with the query's running list (first = 0) by the same composite: a total
+// order, so the merge is exact and the order of the ranges free.  A composite of 0 is an empty slot.
 __global__ __launch_bounds__(1024) void k_knn_select(const float* __restrict__ S, int64_t ld, int M, int64_t r0, int K, const int32_t* __restrict__ excl,
                                                      unsigned long long* __restrict__ run, int first) {
-    __shared__ unsigned long long keys[KNN_SAMPLE];
-    __shared__ unsigned hist[2048];
-    __shared__ unsigned s_prefix, s_remaining, s_count, s_wcnt[16];
+    __shared__ SelShared sh;
+    unsigned long long* keys = sh.keys;
     const int64_t i = blockIdx.x;
-    const float* row = S + i * ld;
-    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, NT = blockDim.x;
     const int64_t ex = excl ? (int64_t)excl[i] - r0 : -1;     // the excluded column of this range, if it lies in it
-    int n2 = 1; while (n2 < K) n2 <<= 1;
-    bool done = false;
-    if (M >= 8 * KNN_SAMPLE && K * 8 <= KNN_TOPN_MAX) {
-        const int stride = M / KNN_SAMPLE;
-        for (int k = tid; k < KNN_SAMPLE; k += NT) keys[k] = (unsigned long long)knn_key(row[(int64_t)k * stride]);
-        __syncthreads();
-        knn_bitonic_desc(keys, KNN_SAMPLE, tid, NT);
-        int r = (int)((4.5 * K * KNN_SAMPLE) / M) + 1;
-        if (r < 8) r = 8;
-        const unsigned thr = (unsigned)keys[r < KNN_SAMPLE ? r : KNN_SAMPLE - 1];
-        __syncthreads();
-        if (tid == 0) s_count = 0;
-        __syncthreads();
-        for (int c = tid; c < M; c += NT) {
-            const unsigned u = knn_key(row[c]);
-            if (u > thr && c != ex) { const unsigned p = atomicAdd(&s_count, 1u); if (p < KNN_TOPN_MAX) keys[p] = ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - (r0 + c)); }
-        }
-        __syncthreads();
-        const unsigned cnt = s_count;
-        if (cnt >= (unsigned)K && cnt <= KNN_TOPN_MAX) {
-            int m2 = n2; while (m2 < (int)cnt) m2 <<= 1;
-            for (int k = cnt + tid; k < m2; k += NT) keys[k] = 0ull;
-            __syncthreads();
-            knn_bitonic_desc(keys, m2, tid, NT);
-            done = true;
-        }
-        __syncthreads();
-    }
-    if (!done) {
-        unsigned prefix = 0, prefix_mask = 0, remaining = K;
-        const int shifts[3] = {21, 10, 0};
-        const int widths[3] = {11, 11, 10};
-        for (int pass = 0; pass < 3; ++pass) {
-            const int sh = shifts[pass], nb = 1 << widths[pass];
-            for (int b = tid; b < nb; b += NT) hist[b] = 0;
-            __syncthreads();
-            for (int c = tid; c < M; c += NT) {
-                const unsigned u = knn_key(row[c]);
-                if ((u & prefix_mask) == prefix && c != ex) atomicAdd(&hist[(u >> sh) & (nb - 1)], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                unsigned rem = remaining; int b = nb - 1;
-                for (; b > 0; --b) { if (hist[b] >= rem) break; rem -= hist[b]; }
-                s_prefix = prefix | ((unsigned)b << sh); s_remaining = rem;
-            }
-            __syncthreads();
-            prefix = s_prefix; remaining = s_remaining;
-            prefix_mask |= (unsigned)(nb - 1) << sh;
-            __syncthreads();
-        }
-        // prefix = the key of the K-th largest eligible value (0 when fewer than K are eligible); `remaining` = how many copies of it belong to the top K
-        if (tid == 0) s_count = 0;
-        for (int k = tid; k < KNN_SAMPLE; k += NT) keys[k] = 0ull;
-        __syncthreads();
-        const unsigned thr = prefix;
-        for (int c = tid; c < M; c += NT) {
-            const unsigned u = knn_key(row[c]);
-            if (u > thr && c != ex) { const unsigned p = atomicAdd(&s_count, 1u); keys[p] = ((unsigned long long)u << 32) | (unsigned)(0x7fffffff - (r0 + c)); }
-        }
-        __syncthreads();
-        // ties at the threshold: the `remaining` smallest ids, found by an ordered scan (ballot inside a wave, wave counts through LDS)
-        unsigned base = s_count, need = remaining;
-        for (int b0 = 0; b0 < M && need > 0; b0 += NT) {
-            const int c = b0 + tid;
-            const bool hit = c < M && c != ex && knn_key(row[c]) == thr;
-            const unsigned long long m = __ballot(hit);
-            if (lane == 0) s_wcnt[wave] = (unsigned)__popcll(m);
-            __syncthreads();
-            unsigned before = 0, total = 0;
-            for (int w = 0; w < NT / 64; ++w) { const unsigned n = s_wcnt[w]; if (w < wave) before += n; total += n; }
-            const unsigned pos = before + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-            if (hit && pos < need) keys[base + pos] = ((unsigned long long)thr << 32) | (unsigned)(0x7fffffff - (r0 + c));
-            const unsigned took = total < need ? total : need;
-            base += took; need -= took;
-            __syncthreads();
-        }
-        knn_bitonic_desc(keys, n2, tid, NT);
-    }
+    const int n2 = select_topk_row<SignedKey, true>(sh, S + i * ld, M, K, r0, ex);
     // keys[0 .. K): the range's candidates, sorted.  Merge with the running list: 2 n2 <= 4096 composites, sorted again
     unsigned long long* mine = run + i * K;
     if (!first) {
@@ -277,7 +176,7 @@ __global__ __launch_bounds__(1024) void k_knn_select(const float* __restrict__ S
         for (int k = tid; k < n2; k += NT) keys[n2 + k] = k < K ? mine[k] : 0ull;
         for (int k = K + tid; k < n2; k += NT) keys[k] = 0ull;
         __syncthreads();
-        knn_bitonic_desc(keys, 2 * n2, tid, NT);
+        bitonic_desc(keys, 2 * n2, tid, NT);
     }
     for (int k = tid; k < K; k += NT) mine[k] = keys[k];
 }
@@ -287,21 +186,7 @@ __global__ void k_knn_finish(const unsigned long long* __restrict__ run, int64_t
     if (e >= n) return;
     const unsigned long long c = run[e];
     idx[e] = c ? 0x7fffffff - (int32_t)(c & 0xffffffffu) : -1;
-    sims[e] = c ? knn_unkey((unsigned)(c >> 32)) : -INFINITY;
-}
-
-template <typename T> int kalloc(ntf_knn* h, T** p, int64_t n) {
-    *p = nullptr;
-    if (hipMalloc((void**)p, (size_t)std::max<int64_t>(n, 1) * sizeof(T)) != hipSuccess) { h->err = "hipMalloc failed"; return NTF_ENOMEM; }
-    return NTF_OK;
-}
-template <typename T> int kgrow(ntf_knn* h, T** p, int64_t* cap, int64_t n) {
-    if (n <= *cap) return NTF_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const int rc = kalloc(h, p, n);
-    if (rc == NTF_OK) *cap = n;
-    return rc;
+    sims[e] = c ? SignedKey::value((unsigned)(c >> 32)) : -INFINITY;
 }
 
 size_t knn_sims_lds(int nqt, int dp) { return ((size_t)nqt * 32 * (dp + 1) + (size_t)nqt * 32 + (size_t)KNN_WAVES * 32 * KNN_SLD) * sizeof(float); }
@@ -334,12 +219,11 @@ extern "C" int ntf_knn_create(int device, const float* table, int64_t n_rows, in
     if (hipStreamCreate(&h->st) != hipSuccess) { g_knn_create_error = "hipStreamCreate failed"; delete h; return NTF_EHIP; }
     int rc = NTF_OK;
     auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
-    A(kalloc(h, &h->table, n_rows * dp)); A(kalloc(h, &h->rinv, n_rows)); A(kalloc(h, &h->flag, 1));
+    A(dev_alloc(h, &h->table, n_rows * dp)); A(dev_alloc(h, &h->rinv, n_rows)); A(dev_alloc(h, &h->flag, 1));
     if (rc != NTF_OK) { g_knn_create_error = h->err; ntf_knn_destroy(h); return rc; }
     bool ok = true;
     auto H = [&](hipError_t s) { ok = ok && s == hipSuccess; };
-    if (dp != d) H(hipMemset(h->table, 0, (size_t)n_rows * dp * 4));           // the pad columns are exact zeros: they add nothing to a chain
-    H(hipMemcpy2D(h->table, (size_t)dp * 4, table, (size_t)d * 4, (size_t)d * 4, (size_t)n_rows, hipMemcpyHostToDevice));
+    H(upload_padded(h->table, dp, table, d, n_rows));
     H(hipMemsetAsync(h->flag, 0, 4, h->st));
     hipLaunchKernelGGL(k_knn_norms, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, h->st, h->table, n_rows, (int)d, (int)dp, h->rinv, h->flag);
     H(hipGetLastError());
@@ -358,19 +242,19 @@ extern "C" int ntf_knn_create(int device, const float* table, int64_t n_rows, in
 extern "C" int ntf_knn_query(ntf_knn* h, const float* queries, int64_t n, int32_t topn, const int64_t* exclude, int64_t workspace_bytes,
                              int32_t* out_idx, float* out_sims, double* device_ms) {
     if (!h) { g_knn_create_error = "knn query: the handle is NULL"; return NTF_EINVAL; }
-    if (!queries || !out_idx || !out_sims) KFAIL(h, NTF_EINVAL, "knn query: queries, out_idx and out_sims are required");
-    if (n < 1) KFAIL(h, NTF_EINVAL, "knn query: n < 1");
-    if (topn < 1 || topn > KNN_TOPN_MAX) KFAIL(h, NTF_EINVAL, "knn query: topn outside 1..2048");
-    if (workspace_bytes < 0) KFAIL(h, NTF_EINVAL, "knn query: workspace_bytes < 0");
+    if (!queries || !out_idx || !out_sims) FAIL(h, NTF_EINVAL, "knn query: queries, out_idx and out_sims are required");
+    if (n < 1) FAIL(h, NTF_EINVAL, "knn query: n < 1");
+    if (topn < 1 || topn > SEL_MAX) FAIL(h, NTF_EINVAL, "knn query: topn outside 1..2048");
+    if (workspace_bytes < 0) FAIL(h, NTF_EINVAL, "knn query: workspace_bytes < 0");
     const int64_t wsb = workspace_bytes ? workspace_bytes : NTF_KNN_WORKSPACE_BYTES;
     const int64_t unit = (int64_t)KNN_QUNIT * KNN_RB * 4;
-    if (wsb < unit) KFAIL(h, NTF_EINVAL, "knn query: workspace_bytes below one unit of work (32 queries x 256 rows of f32 sims = 32 KiB)");
+    if (wsb < unit) FAIL(h, NTF_EINVAL, "knn query: workspace_bytes below one unit of work (32 queries x 256 rows of f32 sims = 32 KiB)");
     const int d = h->d; const int64_t dp = h->dp, N = h->n_rows;
-    for (int64_t e = 0; e < n * d; ++e) if (!std::isfinite(queries[e])) KFAIL(h, NTF_EINVAL, "knn query: a query value is not finite");
+    for (int64_t e = 0; e < n * d; ++e) if (!std::isfinite(queries[e])) FAIL(h, NTF_EINVAL, "knn query: a query value is not finite");
     std::vector<int32_t> excl;
     if (exclude) {
         excl.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) { if (exclude[i] < -1 || exclude[i] >= N) KFAIL(h, NTF_EINVAL, "knn query: an exclude value outside [-1, n_rows)"); excl[(size_t)i] = (int32_t)exclude[i]; }
+        for (int64_t i = 0; i < n; ++i) { if (exclude[i] < -1 || exclude[i] >= N) FAIL(h, NTF_EINVAL, "knn query: an exclude value outside [-1, n_rows)"); excl[(size_t)i] = (int32_t)exclude[i]; }
     }
     // the plan (header): a group of 32 g queries, a range of 256 r rows, group x range x 4 bytes <= the budget
     const int64_t g = std::min<int64_t>(std::max<int64_t>(wsb / ((int64_t)8 << 20), 1), std::min<int64_t>(KNN_MAX_GROUP / KNN_QUNIT, (n + KNN_QUNIT - 1) / KNN_QUNIT));
@@ -380,25 +264,24 @@ extern "C" int ntf_knn_query(ntf_knn* h, const float* queries, int64_t n, int32_
     const int nqt_max = (std::min(G, n) > 64 && dp <= 128) ? 4 : (std::min(G, n) > 32) ? 2 : 1;
     const int64_t Gw = (g + nqt_max - 1) / nqt_max * nqt_max * KNN_QUNIT;
     const int64_t R = std::min<int64_t>(std::min<int64_t>(wsb / (Gw * KNN_RB * 4), KNN_MAX_RANGE / KNN_RB), (N + KNN_RB - 1) / KNN_RB) * KNN_RB;
-    KCHK(h, hipSetDevice(h->device));
-    KCHK(h, hipStreamSynchronize(h->st));
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     {
         int rc = NTF_OK;
         auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
-        A(kgrow(h, &h->q, &h->q_cap, n * dp)); A(kgrow(h, &h->q_rinv, &h->qr_cap, n)); A(kgrow(h, &h->q_excl, &h->qe_cap, n));
-        A(kgrow(h, &h->o_idx, &h->oi_cap, n * topn)); A(kgrow(h, &h->o_sims, &h->os_cap, n * topn)); A(kgrow(h, &h->run, &h->run_cap, G * topn)); if (h->ws_cap != Gw * R) { if (h->ws) hipFree(h->ws); h->ws = nullptr; h->ws_cap = 0; A(kgrow(h, &h->ws, &h->ws_cap, Gw * R)); }      // never above this call's budget
+        A(dev_grow(h, &h->q, &h->q_cap, n * dp)); A(dev_grow(h, &h->q_rinv, &h->qr_cap, n)); A(dev_grow(h, &h->q_excl, &h->qe_cap, n));
+        A(dev_grow(h, &h->o_idx, &h->oi_cap, n * topn)); A(dev_grow(h, &h->o_sims, &h->os_cap, n * topn)); A(dev_grow(h, &h->run, &h->run_cap, G * topn)); if (h->ws_cap != Gw * R) { if (h->ws) hipFree(h->ws); h->ws = nullptr; h->ws_cap = 0; A(dev_grow(h, &h->ws, &h->ws_cap, Gw * R)); }      // never above this call's budget
         if (rc != NTF_OK) return rc;
     }
-    if (dp != d) KCHK(h, hipMemset(h->q, 0, (size_t)n * dp * 4));
-    KCHK(h, hipMemcpy2D(h->q, (size_t)dp * 4, queries, (size_t)d * 4, (size_t)d * 4, (size_t)n, hipMemcpyHostToDevice));
-    if (exclude) KCHK(h, hipMemcpy(h->q_excl, excl.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    KCHK(h, hipMemsetAsync(h->flag, 0, 4, h->st));
+    HIPCHK(h, upload_padded(h->q, dp, queries, d, n));
+    if (exclude) HIPCHK(h, hipMemcpy(h->q_excl, excl.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemsetAsync(h->flag, 0, 4, h->st));
     hipLaunchKernelGGL(k_knn_norms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->q, n, d, (int)dp, h->q_rinv, h->flag);
     int flag = 0;
-    KCHK(h, hipMemcpyAsync(&flag, h->flag, 4, hipMemcpyDeviceToHost, h->st));
-    KCHK(h, hipStreamSynchronize(h->st));
-    if (flag) KFAIL(h, NTF_EINVAL, "knn query: the f32 squared norm of a query overflows");
-    if (device_ms) { if (!h->ev0) { KCHK(h, hipEventCreate(&h->ev0)); KCHK(h, hipEventCreate(&h->ev1)); } KCHK(h, hipEventRecord(h->ev0, h->st)); }
+    HIPCHK(h, hipMemcpyAsync(&flag, h->flag, 4, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    if (flag) FAIL(h, NTF_EINVAL, "knn query: the f32 squared norm of a query overflows");
+    if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
     for (int64_t g0 = 0; g0 < n; g0 += G) {
         const int ng = (int)std::min<int64_t>(G, n - g0);
         const int nqt = std::min(nqt_max, ng > 64 ? 4 : ng > 32 ? 2 : 1);      // a shorter last group takes a shorter chunk (1, 2 and 4 divide nqt_max)
@@ -419,12 +302,12 @@ extern "C" int ntf_knn_query(ntf_knn* h, const float* queries, int64_t n, int32_
         const int64_t ne = (int64_t)ng * topn;
         hipLaunchKernelGGL(k_knn_finish, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->st, h->run, ne, h->o_idx + g0 * topn, h->o_sims + g0 * topn);
         const hipError_t s = hipGetLastError();
-        if (s != hipSuccess) KFAIL(h, NTF_EHIP, std::string("knn kernel launch: ") + hipGetErrorString(s));
+        if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("knn kernel launch: ") + hipGetErrorString(s));
     }
-    if (device_ms) KCHK(h, hipEventRecord(h->ev1, h->st));
-    KCHK(h, hipStreamSynchronize(h->st));
-    if (device_ms) { float ms = 0.f; KCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
-    KCHK(h, hipMemcpy(out_idx, h->o_idx, (size_t)n * topn * 4, hipMemcpyDeviceToHost));
-    KCHK(h, hipMemcpy(out_sims, h->o_sims, (size_t)n * topn * 4, hipMemcpyDeviceToHost));
+    if (device_ms) HIPCHK(h, hipEventRecord(h->ev1, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    if (device_ms) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
+    HIPCHK(h, hipMemcpy(out_idx, h->o_idx, (size_t)n * topn * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(out_sims, h->o_sims, (size_t)n * topn * 4, hipMemcpyDeviceToHost));
     return NTF_OK;
 }

@@ -3,6 +3,7 @@
 // skill coverage of the top-k experts.  One wave per test instance; integer/index work, latency-bound, nothing here is MFMA-shaped.
 #include "../../include/opentf_amd.h"
 #include "ntf_device.h"
+#include "ntf_host.h"
 #include <string>
 #include <vector>
 
@@ -106,14 +107,6 @@ void launch_rank_metrics(hipStream_t st, const int32_t* topk, int64_t n, int K, 
 using namespace ntf;
 
 namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    bool put(const void* host, size_t bytes) {
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return false;
-        return !bytes || hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    }
-};
 bool make_cut(const int32_t* cutoffs, int n, Cutoffs& c) {
     if (!cutoffs || n < 1 || n > MAX_CUT) return false;
     c.n = n;
@@ -131,9 +124,7 @@ extern "C" int ntf_rank_metrics(int device, const int32_t* topk_idx, int64_t n, 
     DevBuf dk, dip, dix, dr, dout;
     const int64_t nnz = truth_indptr[n_truth_rows];
     if (!dk.put(topk_idx, (size_t)n * K * 4) || !dip.put(truth_indptr, (size_t)(n_truth_rows + 1) * 8) || !dix.put(truth_indices, (size_t)nnz * 4) ||
-        (rows && !dr.put(rows, (size_t)n * 8)) || !dout.put(nullptr, 0)) return NTF_ENOMEM;
-    hipFree(dout.p); dout.p = nullptr;
-    if (hipMalloc(&dout.p, (size_t)n * 5 * n_cut * 4) != hipSuccess) return NTF_ENOMEM;
+        (rows && !dr.put(rows, (size_t)n * 8)) || !dout.alloc((size_t)n * 5 * n_cut * 4)) return NTF_ENOMEM;
     hipLaunchKernelGGL(k_rank_metrics, dim3((unsigned)n), dim3(64), 0, 0, (const int32_t*)dk.p, K, (const int64_t*)dip.p, (const int32_t*)dix.p,
                        rows ? (const int64_t*)dr.p : nullptr, c, (float*)dout.p);
     if (hipMemcpy(out, dout.p, (size_t)n * 5 * n_cut * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;
@@ -152,8 +143,8 @@ extern "C" int ntf_skill_coverage(int device, const int32_t* topk_idx, int64_t n
     if (hipSetDevice(device) != hipSuccess) return NTF_EHIP;
     DevBuf dk, sip, six, dr, cip, cix, dout;
     if (!dk.put(topk_idx, (size_t)n * K * 4) || !sip.put(skill_indptr, (size_t)(n_skill_rows + 1) * 8) || !six.put(skill_indices, (size_t)skill_indptr[n_skill_rows] * 4) ||
-        (rows && !dr.put(rows, (size_t)n * 8)) || !cip.put(cov_indptr, (size_t)(n_experts + 1) * 8) || !cix.put(cov_indices, (size_t)cov_indptr[n_experts] * 4)) return NTF_ENOMEM;
-    if (hipMalloc(&dout.p, (size_t)n * n_cut * 4) != hipSuccess) return NTF_ENOMEM;
+        (rows && !dr.put(rows, (size_t)n * 8)) || !cip.put(cov_indptr, (size_t)(n_experts + 1) * 8) || !cix.put(cov_indices, (size_t)cov_indptr[n_experts] * 4) ||
+        !dout.alloc((size_t)n * n_cut * 4)) return NTF_ENOMEM;
     hipLaunchKernelGGL(k_skill_coverage, dim3((unsigned)n), dim3(64), 0, 0, (const int32_t*)dk.p, K, (const int64_t*)sip.p, (const int32_t*)six.p,
                        rows ? (const int64_t*)dr.p : nullptr, (const int64_t*)cip.p, (const int32_t*)cix.p, c, (float*)dout.p);
     if (hipMemcpy(out, dout.p, (size_t)n * n_cut * 4, hipMemcpyDeviceToHost) != hipSuccess) return NTF_EHIP;

@@ -9,6 +9,7 @@
 // reduction and one coalesced f32 atomic row add (the forms that run at full rate on gfx950: 256 contiguous bytes per wave-instruction).
 #include "../../include/opentf_amd.h"
 #include "ntf_device.h"
+#include "ntf_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,9 +31,6 @@ struct ntf_n2v {
     std::string err;
 };
 static thread_local std::string g_n2v_create_error;
-
-#define NCHK(h, call) do { hipError_t _s = (call); if (_s != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(_s); return NTF_EHIP; } } while (0)
-#define NFAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
 
 extern "C" const char* ntf_n2v_last_error(const ntf_n2v* h) { return h ? h->err.c_str() : g_n2v_create_error.c_str(); }
 
@@ -136,13 +134,6 @@ __global__ __launch_bounds__(256) void k_n2v_edge_bce(const float* __restrict__ 
     if (lane == 0) atomicAdd(out, (double)(fmaxf(-dot, 0.f) + log1pf(expf(-fabsf(dot)))));
 }
 
-template <typename T> static int nalloc(ntf_n2v* h, T** p, int64_t n) {
-    *p = nullptr;
-    if (n <= 0) return NTF_OK;
-    if (hipMalloc((void**)p, (size_t)n * sizeof(T)) != hipSuccess) { h->err = "hipMalloc failed"; return NTF_ENOMEM; }
-    return NTF_OK;
-}
-
 extern "C" void ntf_n2v_destroy(ntf_n2v* h) {
     if (!h) return;
     hipSetDevice(h->device);
@@ -172,15 +163,17 @@ extern "C" int ntf_n2v_create(int device, int64_t num_nodes, int32_t d, const in
     auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
     if (hipStreamCreate(&h->st) != hipSuccess) { g_n2v_create_error = "hipStreamCreate failed"; delete h; return NTF_EHIP; }
     const int64_t np = num_nodes * d;
-    A(nalloc(h, &h->rowptr, num_nodes + 1)); A(nalloc(h, &h->col, std::max<int64_t>(nnz, 1)));
-    A(nalloc(h, &h->W, np)); A(nalloc(h, &h->G, np)); A(nalloc(h, &h->M1, np)); A(nalloc(h, &h->V2, np)); A(nalloc(h, &h->d_loss, 2));
+    A(dev_alloc(h, &h->rowptr, num_nodes + 1)); A(dev_alloc(h, &h->col, std::max<int64_t>(nnz, 1)));
+    A(dev_alloc(h, &h->W, np)); A(dev_alloc(h, &h->G, np)); A(dev_alloc(h, &h->M1, np)); A(dev_alloc(h, &h->V2, np)); A(dev_alloc(h, &h->d_loss, 2));
     if (rc != NTF_OK) { g_n2v_create_error = h->err; ntf_n2v_destroy(h); return rc; }
-    hipMemcpy(h->rowptr, rowptr, (num_nodes + 1) * 8, hipMemcpyHostToDevice);
-    if (nnz) hipMemcpy(h->col, col, nnz * 4, hipMemcpyHostToDevice);
-    if (du != d) hipMemset(h->W, 0, np * 4);
-    hipMemcpy2D(h->W, (size_t)d * 4, init_weight, (size_t)du * 4, (size_t)du * 4, (size_t)num_nodes, hipMemcpyHostToDevice);
-    hipMemsetAsync(h->G, 0, np * 4, h->st); hipMemsetAsync(h->M1, 0, np * 4, h->st); hipMemsetAsync(h->V2, 0, np * 4, h->st);
-    if (hipStreamSynchronize(h->st) != hipSuccess) { g_n2v_create_error = "device initialisation failed"; ntf_n2v_destroy(h); return NTF_EHIP; }
+    bool ok = true;
+    auto H = [&](hipError_t s) { ok = ok && s == hipSuccess; };
+    H(hipMemcpy(h->rowptr, rowptr, (num_nodes + 1) * 8, hipMemcpyHostToDevice));
+    if (nnz) H(hipMemcpy(h->col, col, nnz * 4, hipMemcpyHostToDevice));
+    H(upload_padded(h->W, d, init_weight, du, num_nodes));
+    H(hipMemsetAsync(h->G, 0, np * 4, h->st)); H(hipMemsetAsync(h->M1, 0, np * 4, h->st)); H(hipMemsetAsync(h->V2, 0, np * 4, h->st));
+    H(hipStreamSynchronize(h->st));
+    if (!ok) { g_n2v_create_error = "device initialisation failed"; ntf_n2v_destroy(h); return NTF_EHIP; }
     *out = h;
     return NTF_OK;
 }
@@ -191,27 +184,26 @@ static void n2v_key(const ntf_n2v* h, uint64_t step, int tensor, uint32_t& k0, u
     k0 = (uint32_t)x; k1 = (uint32_t)(x >> 32);
 }
 static int stage_batch(ntf_n2v* h, const int64_t* batch, int64_t B) {
-    for (int64_t i = 0; i < B; ++i) if (batch[i] < 0 || batch[i] >= h->n) NFAIL(h, NTF_EINVAL, "n2v: start node out of range");
-    if (h->batch_cap < B) { if (h->d_batch) hipFree(h->d_batch); int r = nalloc(h, &h->d_batch, B); if (r) return r; h->batch_cap = B; }
-    NCHK(h, hipMemcpyAsync(h->d_batch, batch, B * 8, hipMemcpyHostToDevice, h->st));
-    NCHK(h, hipStreamSynchronize(h->st));
+    for (int64_t i = 0; i < B; ++i) if (batch[i] < 0 || batch[i] >= h->n) FAIL(h, NTF_EINVAL, "n2v: start node out of range");
+    if (int r = dev_grow(h, &h->d_batch, &h->batch_cap, B)) return r;
+    HIPCHK(h, hipMemcpyAsync(h->d_batch, batch, B * 8, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     return NTF_OK;
 }
 static int need_rows(ntf_n2v* h, int64_t elems) {
     h->win_p = h->win_n = nullptr; h->n_win_p = h->n_win_n = 0; h->win_ctx = 0;   // every writer of d_rows comes through here
-    if (h->rows_cap < elems) { if (h->d_rows) hipFree(h->d_rows); int r = nalloc(h, &h->d_rows, elems); if (r) return r; h->rows_cap = elems; }
-    return NTF_OK;
+    return dev_grow(h, &h->d_rows, &h->rows_cap, elems);
 }
 
 extern "C" int ntf_n2v_walks(ntf_n2v* h, const int64_t* start, int64_t n, int32_t walk_length, uint64_t step, int64_t* out_host) {
     if (!h || !start || n < 1 || walk_length < 1 || !out_host) return NTF_EINVAL;
-    NCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     int r = stage_batch(h, start, n); if (r) return r;
     if ((r = need_rows(h, n * walk_length))) return r;
     uint32_t k0, k1; n2v_key(h, step, 0, k0, k1);
     hipLaunchKernelGGL(k_n2v_walks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->rowptr, h->col, h->d_batch, n, n, walk_length, k0, k1, (uint32_t)step, h->d_rows);
-    NCHK(h, hipMemcpyAsync(out_host, h->d_rows, n * walk_length * 8, hipMemcpyDeviceToHost, h->st));
-    NCHK(h, hipStreamSynchronize(h->st));
+    HIPCHK(h, hipMemcpyAsync(out_host, h->d_rows, n * walk_length * 8, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     return NTF_OK;
 }
 
@@ -230,26 +222,26 @@ static void launch_pairs(ntf_n2v* h, const int64_t* rows, int64_t n_rows, int ct
 extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, int32_t walk_length, int32_t context, int32_t walks_per_node, int32_t num_neg,
                                    float lr, const int64_t* inj_pos, int64_t n_pos, const int64_t* inj_neg, int64_t n_neg, int32_t apply, float* loss_out) {
     if (!h || walk_length < 2 || context < 2 || context > walk_length) return NTF_EINVAL;
-    NCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     // every argument check (and stage_batch, which checks the start nodes) comes before the step index is taken and before anything on the device is touched:
     // a refused call changes nothing, so the draws of the calls after it are the ones they would have been without it
     int r;
     const bool injected = inj_pos || inj_neg;
     if (injected) {   // parity tests: the window rows themselves are given
-        if ((n_pos > 0 && !inj_pos) || (n_neg > 0 && !inj_neg) || n_pos < 0 || n_neg < 0) NFAIL(h, NTF_EINVAL, "n2v: injected rows missing or a negative row count");
-        for (int64_t i = 0; i < n_pos * context; ++i) if (inj_pos[i] < 0 || inj_pos[i] >= h->n) NFAIL(h, NTF_EINVAL, "n2v: injected node out of range");
-        for (int64_t i = 0; i < n_neg * context; ++i) if (inj_neg[i] < 0 || inj_neg[i] >= h->n) NFAIL(h, NTF_EINVAL, "n2v: injected node out of range");
+        if ((n_pos > 0 && !inj_pos) || (n_neg > 0 && !inj_neg) || n_pos < 0 || n_neg < 0) FAIL(h, NTF_EINVAL, "n2v: injected rows missing or a negative row count");
+        for (int64_t i = 0; i < n_pos * context; ++i) if (inj_pos[i] < 0 || inj_pos[i] >= h->n) FAIL(h, NTF_EINVAL, "n2v: injected node out of range");
+        for (int64_t i = 0; i < n_neg * context; ++i) if (inj_neg[i] < 0 || inj_neg[i] >= h->n) FAIL(h, NTF_EINVAL, "n2v: injected node out of range");
         if ((r = need_rows(h, (n_pos + n_neg) * context))) return r;
     } else {
-        if (!batch || B < 1 || walks_per_node < 1 || num_neg < 0) NFAIL(h, NTF_EINVAL, "n2v: need a batch of B >= 1 start nodes, walks_per_node >= 1 and num_neg >= 0");
+        if (!batch || B < 1 || walks_per_node < 1 || num_neg < 0) FAIL(h, NTF_EINVAL, "n2v: need a batch of B >= 1 start nodes, walks_per_node >= 1 and num_neg >= 0");
         if ((r = stage_batch(h, batch, B))) return r;
     }
-    NCHK(h, hipMemsetAsync(h->d_loss, 0, 8, h->st));
+    HIPCHK(h, hipMemsetAsync(h->d_loss, 0, 8, h->st));
     const uint64_t step = h->step++;
     if (injected) {
-        if (n_pos) NCHK(h, hipMemcpyAsync(h->d_rows, inj_pos, n_pos * context * 8, hipMemcpyHostToDevice, h->st));
-        if (n_neg) NCHK(h, hipMemcpyAsync(h->d_rows + n_pos * context, inj_neg, n_neg * context * 8, hipMemcpyHostToDevice, h->st));
-        NCHK(h, hipStreamSynchronize(h->st));
+        if (n_pos) HIPCHK(h, hipMemcpyAsync(h->d_rows, inj_pos, n_pos * context * 8, hipMemcpyHostToDevice, h->st));
+        if (n_neg) HIPCHK(h, hipMemcpyAsync(h->d_rows + n_pos * context, inj_neg, n_neg * context * 8, hipMemcpyHostToDevice, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
         launch_pairs(h, h->d_rows, n_pos, context, 1);
         launch_pairs(h, h->d_rows + n_pos * context, n_neg, context, 0);
         h->win_p = h->d_rows; h->win_n = h->d_rows + n_pos * context; h->n_win_p = n_pos; h->n_win_n = n_neg;
@@ -284,47 +276,47 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
     }
     if (loss_out) {
         double l = 0;
-        NCHK(h, hipMemcpyAsync(&l, h->d_loss, 8, hipMemcpyDeviceToHost, h->st));
-        NCHK(h, hipStreamSynchronize(h->st));
+        HIPCHK(h, hipMemcpyAsync(&l, h->d_loss, 8, hipMemcpyDeviceToHost, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
         *loss_out = (float)l;
     }
     hipError_t s = hipGetLastError();
-    if (s != hipSuccess) NFAIL(h, NTF_EHIP, std::string("n2v kernel launch: ") + hipGetErrorString(s));
+    if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("n2v kernel launch: ") + hipGetErrorString(s));
     return NTF_OK;
 }
 
 extern "C" int ntf_n2v_get(ntf_n2v* h, int what, float* host) {   // what: 0 = embedding.weight, 1 = its gradient (as the last batch with apply = 0 left it)
     if (!h || !host || what < 0 || what > 1) return NTF_EINVAL;
-    NCHK(h, hipSetDevice(h->device));
-    NCHK(h, hipStreamSynchronize(h->st));
-    NCHK(h, hipMemcpy2D(host, (size_t)h->d_user * 4, what ? h->G : h->W, (size_t)h->d * 4, (size_t)h->d_user * 4, (size_t)h->n, hipMemcpyDeviceToHost));
-    if (what) NCHK(h, hipMemsetAsync(h->G, 0, (size_t)h->n * h->d * 4, h->st));   // reading the gradient consumes it
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    HIPCHK(h, hipMemcpy2D(host, (size_t)h->d_user * 4, what ? h->G : h->W, (size_t)h->d * 4, (size_t)h->d_user * 4, (size_t)h->n, hipMemcpyDeviceToHost));
+    if (what) HIPCHK(h, hipMemsetAsync(h->G, 0, (size_t)h->n * h->d * 4, h->st));   // reading the gradient consumes it
     return NTF_OK;
 }
 
 extern "C" int ntf_n2v_last_windows(ntf_n2v* h, int64_t* n_pos, int64_t* n_neg, int32_t* context, int64_t* pos_rows, int64_t* neg_rows) {
     if (!h || !n_pos || !n_neg || !context) return NTF_EINVAL;
-    if (!h->win_ctx) NFAIL(h, NTF_ESTATE, "n2v: no batch since the scratch was last reused (ntf_n2v_walks and ntf_n2v_edge_bce write over the window rows)");
+    if (!h->win_ctx) FAIL(h, NTF_ESTATE, "n2v: no batch since the scratch was last reused (ntf_n2v_walks and ntf_n2v_edge_bce write over the window rows)");
     *n_pos = h->n_win_p; *n_neg = h->n_win_n; *context = h->win_ctx;
-    NCHK(h, hipSetDevice(h->device));
-    if (pos_rows && h->n_win_p) NCHK(h, hipMemcpyAsync(pos_rows, h->win_p, h->n_win_p * h->win_ctx * 8, hipMemcpyDeviceToHost, h->st));
-    if (neg_rows && h->n_win_n) NCHK(h, hipMemcpyAsync(neg_rows, h->win_n, h->n_win_n * h->win_ctx * 8, hipMemcpyDeviceToHost, h->st));
-    NCHK(h, hipStreamSynchronize(h->st));
+    HIPCHK(h, hipSetDevice(h->device));
+    if (pos_rows && h->n_win_p) HIPCHK(h, hipMemcpyAsync(pos_rows, h->win_p, h->n_win_p * h->win_ctx * 8, hipMemcpyDeviceToHost, h->st));
+    if (neg_rows && h->n_win_n) HIPCHK(h, hipMemcpyAsync(neg_rows, h->win_n, h->n_win_n * h->win_ctx * 8, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     return NTF_OK;
 }
 
 extern "C" int ntf_n2v_edge_bce(ntf_n2v* h, const int64_t* src, const int64_t* dst, int64_t n, float* mean_bce) {
     if (!h || !src || !dst || n < 1 || !mean_bce) return NTF_EINVAL;
-    NCHK(h, hipSetDevice(h->device));
-    for (int64_t i = 0; i < n; ++i) if (src[i] < 0 || src[i] >= h->n || dst[i] < 0 || dst[i] >= h->n) NFAIL(h, NTF_EINVAL, "n2v: edge endpoint out of range");
+    HIPCHK(h, hipSetDevice(h->device));
+    for (int64_t i = 0; i < n; ++i) if (src[i] < 0 || src[i] >= h->n || dst[i] < 0 || dst[i] >= h->n) FAIL(h, NTF_EINVAL, "n2v: edge endpoint out of range");
     int r = need_rows(h, 2 * n); if (r) return r;
-    NCHK(h, hipMemcpyAsync(h->d_rows, src, n * 8, hipMemcpyHostToDevice, h->st));
-    NCHK(h, hipMemcpyAsync(h->d_rows + n, dst, n * 8, hipMemcpyHostToDevice, h->st));
-    NCHK(h, hipMemsetAsync(h->d_loss + 1, 0, 8, h->st));
+    HIPCHK(h, hipMemcpyAsync(h->d_rows, src, n * 8, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipMemcpyAsync(h->d_rows + n, dst, n * 8, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipMemsetAsync(h->d_loss + 1, 0, 8, h->st));
     hipLaunchKernelGGL(k_n2v_edge_bce, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->st, h->W, h->d_rows, h->d_rows + n, n, h->d, h->d_loss + 1);
     double l = 0;
-    NCHK(h, hipMemcpyAsync(&l, h->d_loss + 1, 8, hipMemcpyDeviceToHost, h->st));
-    NCHK(h, hipStreamSynchronize(h->st));
+    HIPCHK(h, hipMemcpyAsync(&l, h->d_loss + 1, 8, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
     *mean_bce = (float)(l / (double)n);
     return NTF_OK;
 }

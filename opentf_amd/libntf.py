@@ -195,10 +195,43 @@ class ScoreResult:
         self.metrics, self.counts, self.auc, self.vals, self.idx = metrics, counts, auc, vals, idx
 
 
-class Engine:
+class _Handle:
+    """One native handle: the pointer, close / __del__, the return-code check and the raise of a failed create.  A subclass names its three symbols and the word
+    its error messages carry after "libopentf_amd"."""
+
+    _CREATE = _DESTROY = _LAST_ERROR = None
+    _TAG = ""
+
+    def _create(self, *args):
+        self._h = C.c_void_p()
+        rc = getattr(lib(), self._CREATE)(*args, C.byref(self._h))
+        if rc != 0:
+            msg = getattr(lib(), self._LAST_ERROR)(None)
+            self._h = None
+            raise NtfError(f"{self._CREATE} failed ({rc}): {msg.decode() if msg else ''}")
+
+    def _ck(self, rc):
+        if rc != 0:
+            raise NtfError(f"libopentf_amd{self._TAG} error {rc}: {getattr(lib(), self._LAST_ERROR)(self._h).decode()}")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._DESTROY)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Engine(_Handle):
     """One Fnn/Bnn model resident on one MI355X.  dims = [D, *h, M].
     expert_shard = (lo, hi), ep_world = G: this engine owns the experts [lo, hi) of the output layer only (one of G such engines, one per GPU;
     hidden layers replicated; see ntf_config.expert_lo in include/opentf_amd.h and opentf_amd/ep.py).  `dims[-1]` then is hi - lo, `experts_global` is M."""
+
+    _CREATE, _DESTROY, _LAST_ERROR = "ntf_engine_create", "ntf_engine_destroy", "ntf_last_error"
 
     def __init__(self, dims, bayesian=False, input_mode=INPUT_DENSE, max_batch=1000, ns=5, nsd="uniform", tpw=10.0, tnw=1.0,
                  lr=1e-3, seed=0, device=0, stream=None, fused=True, fuse_adam=False, mfma=None, expert_shard=None, ep_world=1):
@@ -228,29 +261,8 @@ class Engine:
         if expert_shard is not None or self.ep_world > 1:
             cfg.expert_lo, cfg.experts_global, cfg.ep_world = self.expert_lo, self.experts_global, self.ep_world
         self.stream_handle = stream   # the caller's hipStream_t (int) the engine runs on, None: a stream of its own
-        self._h = C.c_void_p()
-        rc = lib().ntf_engine_create(C.byref(cfg), C.byref(self._h))
-        if rc != 0:
-            msg = lib().ntf_last_error(None)
-            self._h = None
-            raise NtfError(f"ntf_engine_create failed ({rc}): {msg.decode() if msg else ''}")
+        self._create(C.byref(cfg))
         self._keep = []
-
-    # ---- plumbing
-    def _ck(self, rc):
-        if rc != 0:
-            raise NtfError(f"libopentf_amd error {rc}: {lib().ntf_last_error(self._h).decode()}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().ntf_engine_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- data
     @staticmethod
@@ -630,8 +642,10 @@ class Engine:
         return {names[i].decode(): (ms[i], calls[i]) for i in range(min(n, cap))}
 
 
-class Node2Vec:
+class Node2Vec(_Handle):
     """torch_geometric.nn.Node2Vec (p = q = 1) resident on one MI355X: embedding.weight [num_nodes, d] + dense Adam (include/opentf_amd.h)."""
+
+    _CREATE, _DESTROY, _LAST_ERROR, _TAG = "ntf_n2v_create", "ntf_n2v_destroy", "ntf_n2v_last_error", " n2v"
 
     def __init__(self, rowptr, col, init_weight, seed=0, device=0):
         self.rowptr = np.ascontiguousarray(rowptr, dtype=np.int64); self.col = np.ascontiguousarray(col, dtype=np.int32)
@@ -639,23 +653,7 @@ class Node2Vec:
         self.num_nodes, self.d = w.shape
         if len(self.rowptr) != self.num_nodes + 1:
             raise NtfError("rowptr must have num_nodes + 1 entries")
-        self._h = C.c_void_p()
-        rc = lib().ntf_n2v_create(int(device), self.num_nodes, self.d, _ptr(self.rowptr), _ptr(self.col), _ptr(w), int(seed) & (2**64 - 1), C.byref(self._h))
-        if rc != 0:
-            msg = lib().ntf_n2v_last_error(None); self._h = None
-            raise NtfError(f"ntf_n2v_create failed ({rc}): {msg.decode() if msg else ''}")
-
-    def _ck(self, rc):
-        if rc != 0:
-            raise NtfError(f"libopentf_amd n2v error {rc}: {lib().ntf_n2v_last_error(self._h).decode()}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().ntf_n2v_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
+        self._create(int(device), self.num_nodes, self.d, _ptr(self.rowptr), _ptr(self.col), _ptr(w), int(seed) & (2**64 - 1))
 
     def walks(self, start, walk_length, step=0):
         s = np.ascontiguousarray(start, dtype=np.int64)
@@ -697,10 +695,11 @@ class Node2Vec:
         self._ck(lib().ntf_n2v_edge_bce(self._h, _ptr(s), _ptr(t), len(s), C.byref(out))); return out.value
 
 
-class Doc2Vec:
+class Doc2Vec(_Handle):
     """gensim.models.Doc2Vec's tables (doc vectors, word vectors, syn1neg) resident on one MI355X and its negative-sampling trainer (include/opentf_amd.h ntf_d2v_*).
     The documents come as CSR over vocabulary indices together with what build_vocab prepares (sample_int, cum_table) and the initial vectors."""
 
+    _CREATE, _DESTROY, _LAST_ERROR, _TAG = "ntf_d2v_create", "ntf_d2v_destroy", "ntf_d2v_last_error", " d2v"
     DV, WV, SYN1NEG = 0, 1, 2
 
     def __init__(self, doc_ptr, words, sample_int, cum_table, init_wv, init_dv, seed=0, device=0):
@@ -711,24 +710,7 @@ class Doc2Vec:
         self.n_vocab = wv.shape[0]
         if len(self.doc_ptr) != self.n_docs + 1 or len(si) != self.n_vocab or len(ct) != self.n_vocab or wv.shape[1] != self.d:
             raise NtfError("doc_ptr / sample_int / cum_table / initial vectors do not fit together")
-        self._h = C.c_void_p()
-        rc = lib().ntf_d2v_create(int(device), self.n_docs, self.n_vocab, self.d, _ptr(self.doc_ptr), _ptr(self.words), _ptr(si), _ptr(ct), _ptr(wv), _ptr(dv),
-                                  int(seed) & (2**64 - 1), C.byref(self._h))
-        if rc != 0:
-            msg = lib().ntf_d2v_last_error(None); self._h = None
-            raise NtfError(f"ntf_d2v_create failed ({rc}): {msg.decode() if msg else ''}")
-
-    def _ck(self, rc):
-        if rc != 0:
-            raise NtfError(f"libopentf_amd d2v error {rc}: {lib().ntf_d2v_last_error(self._h).decode()}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().ntf_d2v_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
+        self._create(int(device), self.n_docs, self.n_vocab, self.d, _ptr(self.doc_ptr), _ptr(self.words), _ptr(si), _ptr(ct), _ptr(wv), _ptr(dv), int(seed) & (2**64 - 1))
 
     def train_epoch(self, dm, window, alpha_start, alpha_end, epoch, negative=5, serial=False, order=None, progress=None, want_loss=False, want_ms=False):
         """one pass over the documents (gensim train(epochs=1)); returns (mean loss | None, device ms | None)"""
@@ -779,11 +761,12 @@ class Doc2Vec:
         self._ck(lib().ntf_d2v_set(self._h, int(what), _ptr(v)))
 
 
-class Knn:
+class Knn(_Handle):
     """Batched cosine nearest-neighbour search over a [rows, d] float32 table resident on one MI355X (include/opentf_amd.h ntf_knn_*): what
     KeyedVectors.most_similar does one query a call on the host.  The table is uploaded once; `query` never forms [n, rows]."""
 
-    WORKSPACE_BYTES = 256 << 20      # NTF_KNN_WORKSPACE_BYTES
+    _CREATE, _DESTROY, _LAST_ERROR, _TAG = "ntf_knn_create", "ntf_knn_destroy", "ntf_knn_last_error", " knn"
+    WORKSPACE_BYTES = 256 << 20     # NTF_KNN_WORKSPACE_BYTES
     UNIT_BYTES = 32 * 256 * 4        # the smallest unit of work: 32 queries x 256 table rows of f32 sims
 
     def __init__(self, table, device=0):
@@ -791,19 +774,7 @@ class Knn:
         if t.ndim != 2:
             raise NtfError(f"table must be [rows, d], got {t.shape}")
         self.n_rows, self.d = int(t.shape[0]), int(t.shape[1])
-        self._h = C.c_void_p()
-        rc = lib().ntf_knn_create(int(device), _ptr(t), self.n_rows, self.d, C.byref(self._h))
-        if rc != 0:
-            msg = lib().ntf_knn_last_error(None); self._h = None
-            raise NtfError(f"ntf_knn_create failed ({rc}): {msg.decode() if msg else ''}")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().ntf_knn_destroy(self._h); self._h = None
-
-    def __del__(self):
-        try: self.close()
-        except Exception: pass
+        self._create(int(device), _ptr(t), self.n_rows, self.d)
 
     def query(self, queries, topn=10, exclude=None, workspace_bytes=0, want_ms=False):
         """the topn most similar rows of every query [n, d], largest sim first, equal sims by ascending row id; exclude [n] (None; -1: none) = a row id never returned
@@ -818,7 +789,5 @@ class Knn:
         if ex is not None and ex.shape != (n,):
             raise NtfError("exclude must hold one row id per query")
         idx = np.empty((n, max(int(topn), 0)), dtype=np.int32); sims = np.empty((n, max(int(topn), 0)), dtype=np.float32); ms = C.c_double()
-        rc = lib().ntf_knn_query(self._h, _ptr(q), n, int(topn), _ptr(ex), int(workspace_bytes), _ptr(idx), _ptr(sims), C.byref(ms) if want_ms else None)
-        if rc != 0:
-            raise NtfError(f"libopentf_amd knn error {rc}: {lib().ntf_knn_last_error(self._h).decode()}")
+        self._ck(lib().ntf_knn_query(self._h, _ptr(q), n, int(topn), _ptr(ex), int(workspace_bytes), _ptr(idx), _ptr(sims), C.byref(ms) if want_ms else None))
         return (idx, sims, ms.value) if want_ms else (idx, sims)

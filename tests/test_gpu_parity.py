@@ -434,26 +434,41 @@ def test_forward_probs_uncertainty_h128(bayesian, mfma):
         assert np.array_equal(idx, order)
 
 
-@pytest.mark.parametrize("M,K,ties", [(40000, 50, False), (70001, 100, False), (40000, 20, True), (33000, 256, False),
-                                      (40000, 257, False), (40000, 2048, False), (2048, 2048, False), (70001, 1, False)])
+_TOPK_CASES = [(40000, 50, None), (70001, 100, None), (40000, 20, 100), (33000, 256, None), (40000, 257, None), (40000, 2048, None), (2048, 2048, None),
+               (70001, 1, None), (40000, 20, 3000), (40000, 50, 1000), (2500, 40, 2040)]
+
+
+@pytest.mark.parametrize("M,K,ties", _TOPK_CASES, ids=[f"{M}-{K}-{ {None: False, 100: True}.get(g0, g0)}" for M, K, g0 in _TOPK_CASES])
 def test_topk_sampled_threshold_path_is_exact(M, K, ties):
-    """Rows long enough for the sampled-threshold selection (ntf_kernels.hip k_topk_rows): the result must be the exact, deterministic
+    """Rows long enough for the sampled-threshold selection (ntf_select.h, run by k_topk_rows): the result must be the exact, deterministic
     ranking (value descending, expert id ascending among equals) — also when a tie group straddles the K-th place.  K above 256 leaves
     the sampled path for the exact radix selection on a long row (257: the first such K; 2048: the sort's capacity); K = M ranks the
-    whole row; K = 1 sorts nothing."""
+    whole row; K = 1 sorts nothing.
+    `ties` is the first column g0 of a group of 300 experts with one probability, the row's largest (None: no such group), so the top K
+    are g0 .. g0 + K - 1, all taken by the ordered scan of the ties at the threshold, 1024 columns a round: g0 = 100 finds them in its
+    first round; 3000 finds nothing in two whole rounds, then all 20 (the sampled route has fallen through to the radix route, as for
+    1000); 1000 takes 24 from round 0 and 26 from round 1; (2500, 40, 2040), a short row that goes to the radix route directly, takes 8
+    at the end of round 1 and 32 from round 2."""
     torch.manual_seed(M)
     fsd = O.fnn_init(16, [32], M)
-    if ties:   # many experts share one weight row and bias -> identical probabilities
-        fsd["layers.1.weight"][100:400] = fsd["layers.1.weight"][100]; fsd["layers.1.bias"][100:400] = 3.0
+    g0 = ties
+    if g0 is not None:   # many experts share one weight row and bias -> identical probabilities
+        fsd["layers.1.weight"][g0:g0 + 300] = fsd["layers.1.weight"][g0]; fsd["layers.1.bias"][g0:g0 + 300] = 3.0
     X = torch.randn(12, 16)
     f = _engine([16, 32, M], max_batch=12)
     f.load_state_dict(fsd); f.set_dense_input(X.numpy())
     p = f.forward(np.arange(12))
+    if g0 is not None:
+        grp = p[:, g0:g0 + 300].view(np.uint32)
+        assert (grp == grp[:, :1]).all()                    # in every row the 300 members are bit-equal
+        assert (p <= p[:, g0:g0 + 1]).all()                 # and no value is above the group's
     vals, idx = f.forward_topk(np.arange(12), K)
     for i in range(12):
         order = np.lexsort((np.arange(M), -p[i].astype(np.float64)))[:K]     # value desc, id asc
         assert np.array_equal(idx[i], order), i
         assert np.array_equal(vals[i], p[i][order])
+        if g0 is not None:
+            assert np.array_equal(idx[i], np.arange(g0, g0 + K)), i
 
 
 @pytest.mark.parametrize("M", [40000, 300])
