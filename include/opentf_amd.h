@@ -356,6 +356,36 @@ int  ntf_n2v_last_windows(ntf_n2v* h, int64_t* n_pos, int64_t* n_neg, int32_t* c
 int  ntf_n2v_get(ntf_n2v* h, int what /* 0 embedding.weight, 1 gradient */, float* host /* [num_nodes, d] */);
 int  ntf_n2v_edge_bce(ntf_n2v* h, const int64_t* src, const int64_t* dst, int64_t n, float* mean_bce);
 
+/* ---- metapath2vec skill-embedding producer on the device                                   src/mdl/emb/gnn.py (`m2v` branch of the Gnn plugin, trained by _train_rw)
+ * torch_geometric.nn.MetaPath2Vec 2.6.1 as published (restated in tests/m2v_reference.py): after the walks it IS node2vec - the same windows, loss, dense Adam and
+ * held-out-edge loss over one table with global row ids - so ntf_m2v_create returns an ntf_n2v handle that carries a metapath, and every ntf_n2v_* entry works on it.
+ * Types and rows: n_types node types in TABLE ORDER (PyG sorts the type names), type t owns rows [start[t], start[t] + type_count[t]), start = the running sum,
+ * total = sum(type_count); the table is [total + 1, d] (`Embedding(count + 1, d)`), row `total` is the DUMMY row - an ordinary trained row.
+ * Metapath: n_hops hops (1 .. NTF_M2V_MAX_HOPS), hop i goes from type hop_src[i] to type hop_dst[i] over its own CSR: hop_rowptr[i] [type_count[hop_src[i]] + 1]
+ * int64, hop_col[i] int32 LOCAL ids of type hop_dst[i] (NULL allowed where the hop has no edge).  hop_dst[i] must be hop_src[i + 1].
+ * Positive walks (ntf_n2v_walks, ntf_n2v_train_batch): start ids are LOCAL ids of type hop_src[0] in [0, type_count[hop_src[0]]); position 0 is stored as
+ * start[hop_src[0]] + local, position s >= 1 as start[hop_dst[(s - 1) % n_hops]] + local, the dummy as `total`.  Step s (1-based) uses hop (s - 1) % n_hops: from a
+ * real node of degree deg > 0 the neighbour at index (u * deg) >> 32 of its CSR row; from a node of degree 0, or from the dummy, the dummy (absorbing).  u is word
+ * (s - 1) & 3 of Philox4x32-10(counter (r lo, r hi, (s - 1) >> 2, step), key n2v_key(seed, step, 0)), r = the walk's row - node2vec's layout; a dead end or a dummy
+ * consumes its draw slot like any step, so position s of walk r always reads the same word.  Row r starts at batch[r % B].
+ * Negative walks: start as above, position s >= 1 is start[hop_dst[(s - 1) % n_hops]] + ((u * type_count[that type]) >> 32), never the dummy; u from counter
+ * (r lo, r hi, 0x4E454700 + ((s - 1) >> 2), step), key n2v_key(seed, step, 1).
+ * walk_length keeps this ABI's meaning, NODES per walk: PyG's MetaPath2Vec counts steps, so a caller passes its walk_length + 1.
+ * ntf_n2v_edge_bce, ntf_n2v_get, ntf_n2v_last_windows and injected windows speak GLOBAL row ids and [total + 1, d]; injected windows may name the dummy row.
+ * Refused with NTF_EINVAL, before anything is allocated / before the step index is taken, changing nothing: n_types outside 1 .. NTF_M2V_MAX_TYPES, n_hops outside
+ * 1 .. NTF_M2V_MAX_HOPS, a type id outside [0, n_types), a negative count, hop_dst[i] != hop_src[i + 1], a rowptr that does not start at 0 or is not monotone, a column
+ * outside its destination type, d outside 1 .. 256; at ntf_n2v_train_batch / ntf_n2v_walks: walk_length - 1 > n_hops on a metapath that is not a cycle
+ * (hop_dst[n_hops - 1] != hop_src[0]), a start id outside the start type.  The optimiser is the dense Adam of the n2v section.
+ * The pairs of a metapath handle run through k_m2v_pairs, which sums the terms that land on the dummy row per workgroup before they reach the gradient (same terms, another
+ * order of the f32 sums on that one row); the environment variable NTF_M2V_PAIRS=0, read by ntf_m2v_create, keeps node2vec's k_n2v_pairs for A/B runs. */
+#define NTF_M2V_MAX_TYPES 8
+#define NTF_M2V_MAX_HOPS  8
+int  ntf_m2v_create(int device, int32_t n_types, const int64_t* type_count /* [n_types], table order */,
+                    int32_t n_hops, const int32_t* hop_src, const int32_t* hop_dst /* [n_hops] type ids */,
+                    const int64_t* const* hop_rowptr /* [n_hops] -> [type_count[hop_src[i]] + 1] */,
+                    const int32_t* const* hop_col    /* [n_hops] -> LOCAL ids of type hop_dst[i] */,
+                    int32_t d, const float* init_weight /* [total + 1, d] */, uint64_t seed, ntf_n2v** out);
+
 /* ---- doc2vec team-vector producer on the device                          src/mdl/emb/d2v.py:69-84 (gensim.models.Doc2Vec: build_vocab + train)
  * gensim 4.3.3's PV-DM (dm = 1, mean of doc vector + shrunk-window word vectors) and PV-DBOW with dbow_words = 1 (dm = 0), negative sampling from the
  * count^0.75 table, frequent-word subsampling, 1000-bin sigmoid table, |f| >= 6 skipped - as the reference's call leaves gensim's defaults (oracle/d2v_oracle.py

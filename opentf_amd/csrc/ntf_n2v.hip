@@ -7,16 +7,27 @@
 //   update  : torch.optim.Adam on the dense embedding matrix (every row moves every step through its moments)
 // One wave per window row: the start row lives in registers (d / 64 values per lane), every rest row costs one coalesced row read, a wave
 // reduction and one coalesced f32 atomic row add (the forms that run at full rate on gfx950: 256 contiguous bytes per wave-instruction).
+// metapath2vec (torch_geometric.nn.MetaPath2Vec, the `m2v` method of the same plugin) is node2vec after the walks: ntf_m2v_create makes an ntf_n2v handle that carries a
+// metapath over per-hop CSRs, k_m2v_walks / k_m2v_negs draw its typed walks and negatives, k_m2v_pairs is k_n2v_pairs with the dummy row's terms summed per workgroup.
 #include "../../include/opentf_amd.h"
 #include "ntf_device.h"
 #include "ntf_host.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
 using namespace ntf;
+
+// metapath of an m2v handle, handed to k_m2v_walks / k_m2v_negs by value: hop i leads from a node of type src to one of type dst over its own CSR (LOCAL ids);
+// src_start / dst_start / dst_count are the table's first row and row count of those types, total = the dummy row
+struct m2v_path {
+    int n_hops = 0; int64_t total = 0;
+    const int64_t* rowptr[NTF_M2V_MAX_HOPS] = {}; const int32_t* col[NTF_M2V_MAX_HOPS] = {};
+    int64_t src_start[NTF_M2V_MAX_HOPS] = {}, dst_start[NTF_M2V_MAX_HOPS] = {}, dst_count[NTF_M2V_MAX_HOPS] = {};
+};
 
 struct ntf_n2v {
     int device = 0; hipStream_t st = nullptr;
@@ -28,6 +39,9 @@ struct ntf_n2v {
     const int64_t *win_p = nullptr, *win_n = nullptr; int64_t n_win_p = 0, n_win_n = 0; int win_ctx = 0;   // the last batch's window rows inside d_rows (ntf_n2v_last_windows)
     double* d_loss = nullptr;
     int64_t adam_t = 0; uint64_t seed = 0, step = 0;
+    bool m2v = false, cycle = false; m2v_path mp; int64_t start_count = 0;   // ntf_m2v_create: the metapath; rowptr / col above stay NULL, n = total + 1
+    bool dummy_pairs = false;                                                // pairs through k_m2v_pairs: a metapath handle's default (NTF_M2V_PAIRS=0, read by ntf_m2v_create, turns it off)
+    std::vector<void*> hop_bufs;                                           // the per-hop CSRs the metapath points into
     std::string err;
 };
 static thread_local std::string g_n2v_create_error;
@@ -62,6 +76,40 @@ __global__ void k_n2v_negs(const int64_t* __restrict__ batch, int64_t B, int64_t
         if (((s - 1) & 3) == 0) rnd = philox4x32(make_uint4((uint32_t)r, (uint32_t)(r >> 32), 0x4E454700u + (uint32_t)((s - 1) >> 2), step), make_uint2(k0, k1));
         const uint32_t u = ((s - 1) & 3) == 0 ? rnd.x : ((s - 1) & 3) == 1 ? rnd.y : ((s - 1) & 3) == 2 ? rnd.z : rnd.w;
         rw[r * wl + s] = (int64_t)(((uint64_t)u * (uint64_t)num_nodes) >> 32);
+    }
+}
+// metapath2vec walks (MetaPath2Vec.pos_sample): step s goes over hop (s - 1) % n_hops; `cur` is the LOCAL id inside the type the walk stands on, -1 = the dummy.
+// A node without neighbours in that hop leads to the dummy and the dummy stays; both still take their draw slot, so the Philox layout is k_n2v_walks'.
+__global__ void k_m2v_walks(const m2v_path mp, const int64_t* __restrict__ batch, int64_t B, int64_t n_walks, int wl, uint32_t k0, uint32_t k1, uint32_t step,
+                            int64_t* __restrict__ rw) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_walks) return;
+    int64_t cur = batch[r % B];
+    rw[r * wl] = mp.src_start[0] + cur;
+    uint4 rnd = make_uint4(0, 0, 0, 0);
+    for (int s = 1; s < wl; ++s) {
+        if (((s - 1) & 3) == 0) rnd = philox4x32(make_uint4((uint32_t)r, (uint32_t)(r >> 32), (uint32_t)((s - 1) >> 2), step), make_uint2(k0, k1));
+        const uint32_t u = ((s - 1) & 3) == 0 ? rnd.x : ((s - 1) & 3) == 1 ? rnd.y : ((s - 1) & 3) == 2 ? rnd.z : rnd.w;
+        const int hp = (s - 1) % mp.n_hops;
+        if (cur >= 0) {
+            const int64_t a = mp.rowptr[hp][cur], deg = mp.rowptr[hp][cur + 1] - a;
+            cur = deg > 0 ? (int64_t)mp.col[hp][a + (int64_t)(((uint64_t)u * (uint64_t)deg) >> 32)] : -1;
+        }
+        rw[r * wl + s] = cur >= 0 ? mp.dst_start[hp] + cur : mp.total;
+    }
+}
+// metapath2vec negatives (MetaPath2Vec.neg_sample): the start node, then at position s a uniformly random node of the type hop (s - 1) % n_hops leads to; never the dummy
+__global__ void k_m2v_negs(const m2v_path mp, const int64_t* __restrict__ batch, int64_t B, int64_t n_rows, int wl, uint32_t k0, uint32_t k1, uint32_t step,
+                           int64_t* __restrict__ rw) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    rw[r * wl] = mp.src_start[0] + batch[r % B];
+    uint4 rnd = make_uint4(0, 0, 0, 0);
+    for (int s = 1; s < wl; ++s) {
+        if (((s - 1) & 3) == 0) rnd = philox4x32(make_uint4((uint32_t)r, (uint32_t)(r >> 32), 0x4E454700u + (uint32_t)((s - 1) >> 2), step), make_uint2(k0, k1));
+        const uint32_t u = ((s - 1) & 3) == 0 ? rnd.x : ((s - 1) & 3) == 1 ? rnd.y : ((s - 1) & 3) == 2 ? rnd.z : rnd.w;
+        const int hp = (s - 1) % mp.n_hops;
+        rw[r * wl + s] = mp.dst_start[hp] + (int64_t)(((uint64_t)u * (uint64_t)mp.dst_count[hp]) >> 32);
     }
 }
 // windows of `ctx` consecutive nodes: out row j * n_walks + r = rw[r, j : j + ctx]   (torch.cat of the slices along dim 0)
@@ -104,6 +152,59 @@ __global__ __launch_bounds__(256) void k_n2v_pairs(const float* __restrict__ W, 
     if (lane == 0 && r < n_rows) atomicAdd(loss, (double)lsum * (double)inv_pairs);
 }
 
+// k_n2v_pairs for a metapath handle: the same terms, but those that land on the DUMMY row (a rest row or a start row that is the dummy - every walk that met a
+// dead end names it from there on) do not go to G one atomic row add each: a wave keeps their sum in registers, the workgroup's four waves meet in LDS, and
+// G[dummy] takes one row add per workgroup that had such a term.  Every other row goes the way k_n2v_pairs sends it.
+template <int NV>
+__global__ __launch_bounds__(256) void k_m2v_pairs(const float* __restrict__ W, const int64_t* __restrict__ rows, int64_t n_rows, int ctx, int d,
+                                                   float inv_pairs, int positive, int64_t dummy, float* __restrict__ G, double* __restrict__ loss) {
+    __shared__ float sh[4][NV * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+    float lsum = 0.f, gd[NV];
+    int any = 0;          // wave-uniform: a window row is one wave's
+#pragma unroll
+    for (int k = 0; k < NV; ++k) gd[k] = 0.f;
+    if (r < n_rows) {
+        const int64_t s = rows[r * ctx];
+        float hs[NV], gs[NV];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) { hs[k] = W[s * d + lane + 64 * k]; gs[k] = 0.f; }
+        for (int c = 1; c < ctx; ++c) {
+            const int64_t v = rows[r * ctx + c];
+            float hv[NV], dot = 0.f;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) { hv[k] = W[v * d + lane + 64 * k]; dot += hs[k] * hv[k]; }
+            dot = wave_reduce_sum(dot);
+            const float sg = 1.f / (1.f + expf(-dot));
+            float coef;   // d loss / d dot
+            if (positive) { lsum -= logf(sg + 1e-15f); coef = -sg * (1.f - sg) / (sg + 1e-15f) * inv_pairs; }
+            else { lsum -= logf(1.f - sg + 1e-15f); coef = sg * (1.f - sg) / (1.f - sg + 1e-15f) * inv_pairs; }
+            if (v == dummy) {
+                any = 1;
+#pragma unroll
+                for (int k = 0; k < NV; ++k) { gd[k] += coef * hs[k]; gs[k] += coef * hv[k]; }
+            } else {
+#pragma unroll
+                for (int k = 0; k < NV; ++k) { atomicAdd(G + v * d + lane + 64 * k, coef * hs[k]); gs[k] += coef * hv[k]; }
+            }
+        }
+        if (s == dummy) {
+            any = 1;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) gd[k] += gs[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) atomicAdd(G + s * d + lane + 64 * k, gs[k]);
+        }
+    }
+    if (lane == 0 && r < n_rows) atomicAdd(loss, (double)lsum * (double)inv_pairs);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) sh[wave][lane + 64 * k] = gd[k];
+    if (__syncthreads_or(any))          // every thread of the workgroup arrives here (no early return above)
+        for (int q = threadIdx.x; q < NV * 64; q += 256) atomicAdd(G + dummy * d + q, (sh[0][q] + sh[1][q]) + (sh[2][q] + sh[3][q]));
+}
+
 // dense Adam that also clears the gradient for the next batch (one pass over the four buffers)
 __global__ void k_n2v_adam(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n, float lr_over_bc1,
                            float b1, float b2, float eps, float bc2_sqrt) {
@@ -140,6 +241,7 @@ extern "C" void ntf_n2v_destroy(ntf_n2v* h) {
     if (h->st) hipStreamSynchronize(h->st);
     for (void* p : {(void*)h->rowptr, (void*)h->col, (void*)h->W, (void*)h->G, (void*)h->M1, (void*)h->V2, (void*)h->d_batch, (void*)h->d_rows, (void*)h->d_loss})
         if (p) hipFree(p);
+    for (void* p : h->hop_bufs) if (p) hipFree(p);
     if (h->st) hipStreamDestroy(h->st);
     delete h;
 }
@@ -178,18 +280,81 @@ extern "C" int ntf_n2v_create(int device, int64_t num_nodes, int32_t d, const in
     return NTF_OK;
 }
 
+// metapath2vec: an ntf_n2v handle over [total + 1, d] that carries a metapath (include/opentf_amd.h); everything is checked on the host before anything is allocated
+extern "C" int ntf_m2v_create(int device, int32_t n_types, const int64_t* type_count, int32_t n_hops, const int32_t* hop_src, const int32_t* hop_dst,
+                              const int64_t* const* hop_rowptr, const int32_t* const* hop_col, int32_t d, const float* init_weight, uint64_t seed, ntf_n2v** out) {
+    if (!out) { g_n2v_create_error = "out is NULL"; return NTF_EINVAL; }
+    *out = nullptr;
+    auto bad = [&](const char* m) { g_n2v_create_error = m; return (int)NTF_EINVAL; };
+    if (n_types < 1 || n_types > NTF_M2V_MAX_TYPES || n_hops < 1 || n_hops > NTF_M2V_MAX_HOPS) return bad("m2v: need 1 .. 8 node types and 1 .. 8 hops");
+    if (d < 1 || d > 256 || !type_count || !hop_src || !hop_dst || !hop_rowptr || !hop_col || !init_weight) return bad("m2v: need 1 <= d <= 256, type counts, hops with their CSRs and initial weights");
+    int64_t start[NTF_M2V_MAX_TYPES + 1] = {0};
+    for (int t = 0; t < n_types; ++t) {
+        if (type_count[t] < 1 || type_count[t] > 0x7FFFFFFF) return bad("m2v: a node type needs between 1 and 2^31 - 1 nodes");
+        start[t + 1] = start[t] + type_count[t];
+    }
+    const int64_t total = start[n_types];
+    int64_t nnz[NTF_M2V_MAX_HOPS];
+    for (int i = 0; i < n_hops; ++i) {
+        if (hop_src[i] < 0 || hop_src[i] >= n_types || hop_dst[i] < 0 || hop_dst[i] >= n_types) return bad("m2v: a hop names a node type outside [0, n_types)");
+        if (i + 1 < n_hops && hop_dst[i] != hop_src[i + 1]) return bad("m2v: the metapath does not chain (a hop's destination type is not the next hop's source type)");
+        const int64_t ns = type_count[hop_src[i]], nd = type_count[hop_dst[i]]; const int64_t* rp = hop_rowptr[i];
+        if (!rp || rp[0] != 0) return bad("m2v: a hop's rowptr is missing or does not start at 0");
+        for (int64_t k = 0; k < ns; ++k) if (rp[k + 1] < rp[k]) return bad("m2v: rowptr not monotone");
+        nnz[i] = rp[ns];
+        if (nnz[i] > 0 && !hop_col[i]) return bad("m2v: a hop with edges has no column array");
+        for (int64_t p = 0; p < nnz[i]; ++p) if (hop_col[i][p] < 0 || hop_col[i][p] >= nd) return bad("m2v: neighbour id outside its destination type");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_n2v_create_error = "no such HIP device (there is no CPU fallback)"; return NTF_EHIP; }
+    hipSetDevice(device);
+    ntf_n2v* h = new ntf_n2v();
+    h->device = device; h->n = total + 1; h->d_user = d; h->d = (d + 63) / 64 * 64; h->seed = seed;   // rows padded as in ntf_n2v_create
+    h->m2v = true; h->cycle = hop_dst[n_hops - 1] == hop_src[0]; h->start_count = type_count[hop_src[0]];
+    h->mp.n_hops = n_hops; h->mp.total = total;
+    h->dummy_pairs = true;                                                  // 3.32 against 4.73 ms per batch at dblp shapes (profiles/m2v_bench.md); 0 keeps the plain k_n2v_pairs
+    if (const char* e = getenv("NTF_M2V_PAIRS")) h->dummy_pairs = atoi(e) != 0;
+    int rc = NTF_OK;
+    auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
+    if (hipStreamCreate(&h->st) != hipSuccess) { g_n2v_create_error = "hipStreamCreate failed"; delete h; return NTF_EHIP; }
+    const int64_t np = h->n * h->d;
+    bool ok = true;
+    auto H = [&](hipError_t s) { ok = ok && s == hipSuccess; };
+    for (int i = 0; i < n_hops && rc == NTF_OK; ++i) {
+        const int64_t ns = type_count[hop_src[i]];
+        int64_t* rp = nullptr; int32_t* cl = nullptr;
+        A(dev_alloc(h, &rp, ns + 1)); h->hop_bufs.push_back(rp);
+        A(dev_alloc(h, &cl, std::max<int64_t>(nnz[i], 1))); h->hop_bufs.push_back(cl);
+        if (rc != NTF_OK) break;
+        H(hipMemcpy(rp, hop_rowptr[i], (ns + 1) * 8, hipMemcpyHostToDevice));
+        if (nnz[i]) H(hipMemcpy(cl, hop_col[i], nnz[i] * 4, hipMemcpyHostToDevice));
+        h->mp.rowptr[i] = rp; h->mp.col[i] = cl;
+        h->mp.src_start[i] = start[hop_src[i]]; h->mp.dst_start[i] = start[hop_dst[i]]; h->mp.dst_count[i] = type_count[hop_dst[i]];
+    }
+    A(dev_alloc(h, &h->W, np)); A(dev_alloc(h, &h->G, np)); A(dev_alloc(h, &h->M1, np)); A(dev_alloc(h, &h->V2, np)); A(dev_alloc(h, &h->d_loss, 2));
+    if (rc != NTF_OK) { g_n2v_create_error = h->err; ntf_n2v_destroy(h); return rc; }
+    H(upload_padded(h->W, h->d, init_weight, d, h->n));
+    H(hipMemsetAsync(h->G, 0, np * 4, h->st)); H(hipMemsetAsync(h->M1, 0, np * 4, h->st)); H(hipMemsetAsync(h->V2, 0, np * 4, h->st));
+    H(hipStreamSynchronize(h->st));
+    if (!ok) { g_n2v_create_error = "device initialisation failed"; ntf_n2v_destroy(h); return NTF_EHIP; }
+    *out = h;
+    return NTF_OK;
+}
+
 static void n2v_key(const ntf_n2v* h, uint64_t step, int tensor, uint32_t& k0, uint32_t& k1) {
     uint64_t x = h->seed ^ (step * 0x9E3779B97F4A7C15ull + (uint64_t)tensor * 0xBF58476D1CE4E5B9ull);
     x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
     k0 = (uint32_t)x; k1 = (uint32_t)(x >> 32);
 }
 static int stage_batch(ntf_n2v* h, const int64_t* batch, int64_t B) {
-    for (int64_t i = 0; i < B; ++i) if (batch[i] < 0 || batch[i] >= h->n) FAIL(h, NTF_EINVAL, "n2v: start node out of range");
+    const int64_t lim = h->m2v ? h->start_count : h->n;        // a metapath handle takes LOCAL ids of its start type
+    for (int64_t i = 0; i < B; ++i) if (batch[i] < 0 || batch[i] >= lim) FAIL(h, NTF_EINVAL, "n2v: start node out of range");
     if (int r = dev_grow(h, &h->d_batch, &h->batch_cap, B)) return r;
     HIPCHK(h, hipMemcpyAsync(h->d_batch, batch, B * 8, hipMemcpyHostToDevice, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));
     return NTF_OK;
 }
+static bool m2v_too_long(const ntf_n2v* h, int walk_length) { return h->m2v && !h->cycle && walk_length - 1 > h->mp.n_hops; }
 static int need_rows(ntf_n2v* h, int64_t elems) {
     h->win_p = h->win_n = nullptr; h->n_win_p = h->n_win_n = 0; h->win_ctx = 0;   // every writer of d_rows comes through here
     return dev_grow(h, &h->d_rows, &h->rows_cap, elems);
@@ -198,10 +363,12 @@ static int need_rows(ntf_n2v* h, int64_t elems) {
 extern "C" int ntf_n2v_walks(ntf_n2v* h, const int64_t* start, int64_t n, int32_t walk_length, uint64_t step, int64_t* out_host) {
     if (!h || !start || n < 1 || walk_length < 1 || !out_host) return NTF_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
+    if (m2v_too_long(h, walk_length)) FAIL(h, NTF_EINVAL, "m2v: a walk longer than the metapath needs a metapath that ends on its start type");
     int r = stage_batch(h, start, n); if (r) return r;
     if ((r = need_rows(h, n * walk_length))) return r;
     uint32_t k0, k1; n2v_key(h, step, 0, k0, k1);
-    hipLaunchKernelGGL(k_n2v_walks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->rowptr, h->col, h->d_batch, n, n, walk_length, k0, k1, (uint32_t)step, h->d_rows);
+    if (h->m2v) hipLaunchKernelGGL(k_m2v_walks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->mp, h->d_batch, n, n, walk_length, k0, k1, (uint32_t)step, h->d_rows);
+    else hipLaunchKernelGGL(k_n2v_walks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->rowptr, h->col, h->d_batch, n, n, walk_length, k0, k1, (uint32_t)step, h->d_rows);
     HIPCHK(h, hipMemcpyAsync(out_host, h->d_rows, n * walk_length * 8, hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));
     return NTF_OK;
@@ -211,6 +378,16 @@ static void launch_pairs(ntf_n2v* h, const int64_t* rows, int64_t n_rows, int ct
     if (n_rows <= 0 || ctx < 2) return;
     const float inv = 1.f / (float)(n_rows * (ctx - 1));
     const dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
+    if (h->dummy_pairs) {
+        const int64_t dummy = h->mp.total;
+        switch (h->d / 64) {
+            case 1: hipLaunchKernelGGL(k_m2v_pairs<1>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss); break;
+            case 2: hipLaunchKernelGGL(k_m2v_pairs<2>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss); break;
+            case 3: hipLaunchKernelGGL(k_m2v_pairs<3>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss); break;
+            default: hipLaunchKernelGGL(k_m2v_pairs<4>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss); break;
+        }
+        return;
+    }
     switch (h->d / 64) {
         case 1: hipLaunchKernelGGL(k_n2v_pairs<1>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, h->G, h->d_loss); break;
         case 2: hipLaunchKernelGGL(k_n2v_pairs<2>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, h->G, h->d_loss); break;
@@ -234,6 +411,7 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
         if ((r = need_rows(h, (n_pos + n_neg) * context))) return r;
     } else {
         if (!batch || B < 1 || walks_per_node < 1 || num_neg < 0) FAIL(h, NTF_EINVAL, "n2v: need a batch of B >= 1 start nodes, walks_per_node >= 1 and num_neg >= 0");
+        if (m2v_too_long(h, walk_length)) FAIL(h, NTF_EINVAL, "m2v: a walk longer than the metapath needs a metapath that ends on its start type");
         if ((r = stage_batch(h, batch, B))) return r;
     }
     HIPCHK(h, hipMemsetAsync(h->d_loss, 0, 8, h->st));
@@ -254,12 +432,14 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
         int64_t* win_p = rw_n + ng * walk_length; int64_t* win_n = win_p + pw * nw * context;
         uint32_t k0, k1;
         n2v_key(h, step, 0, k0, k1);
-        hipLaunchKernelGGL(k_n2v_walks, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, h->st, h->rowptr, h->col, h->d_batch, (int64_t)B, pw, walk_length, k0, k1, (uint32_t)step, rw_p);
+        if (h->m2v) hipLaunchKernelGGL(k_m2v_walks, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, h->st, h->mp, h->d_batch, (int64_t)B, pw, walk_length, k0, k1, (uint32_t)step, rw_p);
+        else hipLaunchKernelGGL(k_n2v_walks, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, h->st, h->rowptr, h->col, h->d_batch, (int64_t)B, pw, walk_length, k0, k1, (uint32_t)step, rw_p);
         hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((pw * nw * context + 255) / 256)), dim3(256), 0, h->st, rw_p, pw, walk_length, context, win_p);
         launch_pairs(h, win_p, pw * nw, context, 1);
         if (ng) {
             n2v_key(h, step, 1, k0, k1);
-            hipLaunchKernelGGL(k_n2v_negs, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, h->st, h->d_batch, (int64_t)B, ng, walk_length, h->n, k0, k1, (uint32_t)step, rw_n);
+            if (h->m2v) hipLaunchKernelGGL(k_m2v_negs, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, h->st, h->mp, h->d_batch, (int64_t)B, ng, walk_length, k0, k1, (uint32_t)step, rw_n);
+            else hipLaunchKernelGGL(k_n2v_negs, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, h->st, h->d_batch, (int64_t)B, ng, walk_length, h->n, k0, k1, (uint32_t)step, rw_n);
             hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((ng * nw * context + 255) / 256)), dim3(256), 0, h->st, rw_n, ng, walk_length, context, win_n);
             launch_pairs(h, win_n, ng * nw, context, 0);
         }

@@ -115,6 +115,7 @@ SYMBOLS = {
     "ntf_n2v_get": (C.c_int, [_P, C.c_int, _P]),
     "ntf_n2v_last_windows": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ntf_n2v_edge_bce": (C.c_int, [_P, _P, _P, _I64, _P]),
+    "ntf_m2v_create": (C.c_int, [C.c_int, _I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _U64, C.POINTER(_P)]),
     "ntf_d2v_create": (C.c_int, [C.c_int, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _U64, C.POINTER(_P)]),
     "ntf_d2v_destroy": (None, [_P]),
     "ntf_d2v_last_error": (C.c_char_p, [_P]),
@@ -693,6 +694,33 @@ class Node2Vec(_Handle):
     def edge_bce(self, src, dst):
         s = np.ascontiguousarray(src, dtype=np.int64); t = np.ascontiguousarray(dst, dtype=np.int64); out = C.c_float()
         self._ck(lib().ntf_n2v_edge_bce(self._h, _ptr(s), _ptr(t), len(s), C.byref(out))); return out.value
+
+
+class MetaPath2Vec(Node2Vec):
+    """torch_geometric.nn.MetaPath2Vec resident on one MI355X (include/opentf_amd.h, ntf_m2v_create): a Node2Vec handle over [total + 1, d] that carries a metapath.
+    type_counts: node counts in table order (sorted type names); hops: [(src_type, dst_type, rowptr, col)] with LOCAL ids, hop i's dst = hop i + 1's src.
+    `walks` / `train_batch` take LOCAL ids of hops[0]'s source type and `walk_length` counts NODES (PyG's walk_length + 1); everything else speaks global rows,
+    `dummy` (= total) included."""
+
+    _CREATE = "ntf_m2v_create"
+
+    def __init__(self, type_counts, hops, init_weight, seed=0, device=0):
+        tc = np.ascontiguousarray(type_counts, dtype=np.int64).reshape(-1)
+        w = _f32(init_weight)
+        self.num_nodes, self.d = w.shape
+        self.type_start = np.concatenate([[0], np.cumsum(tc)]).astype(np.int64)
+        self.dummy = int(self.type_start[-1])
+        if self.num_nodes != self.dummy + 1:
+            raise NtfError("init_weight must have sum(type_counts) + 1 rows (the last one is the dummy row)")
+        hs = np.ascontiguousarray([h[0] for h in hops], dtype=np.int32); hd = np.ascontiguousarray([h[1] for h in hops], dtype=np.int32)
+        self._rowptr = [np.ascontiguousarray(h[2], dtype=np.int64) for h in hops]; self._col = [np.ascontiguousarray(h[3], dtype=np.int32) for h in hops]
+        for s, rp in zip(hs, self._rowptr):
+            if not (0 <= s < len(tc)) or len(rp) != tc[s] + 1:
+                raise NtfError("a hop's rowptr must have (node count of its source type) + 1 entries")
+        self.start_count = int(tc[hs[0]]) if len(hs) else 0
+        rps = (C.c_void_p * max(len(hops), 1))(*[a.ctypes.data for a in self._rowptr])
+        cls = (C.c_void_p * max(len(hops), 1))(*[a.ctypes.data if a.size else None for a in self._col])
+        self._create(int(device), len(tc), _ptr(tc), len(hops), _ptr(hs), _ptr(hd), rps, cls, self.d, _ptr(w), int(seed) & (2**64 - 1))
 
 
 class Doc2Vec(_Handle):

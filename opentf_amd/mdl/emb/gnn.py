@@ -20,6 +20,10 @@ What the caller (src/main.py:100-153) does and what it gets here:
 
 Node ids of the homogeneous graph: [skills | members | teams].  (PyG's HeteroData orders the three blocks by Python set iteration, i.e.
 arbitrarily per process; consumers select by type, gnn.py:505-509, so the order is not part of the contract.)
+
+The metapath2vec method (`...Gnn_m2v`) goes through the same loop: `torch_geometric.nn.MetaPath2Vec` over the metapath of the `m2v` section (`_metapath`), per-hop
+CSRs of the same stm structure (`m2v_graph`), the table [members | skills | teams | dummy row] (PyG sorts the type names; `Embedding(count + 1, d)`), the loader over
+the metapath's start type, walks of `wl` STEPS (= wl + 1 nodes on the device).  INTEGRATION.md §2b lists what is not pinned against the reference tree.
 """
 from __future__ import annotations
 
@@ -75,6 +79,61 @@ def member_team_edges(member, teams, off):
 
 NODE_ORDER = "skill|member|team"     # row blocks of the table this plugin trains (stm_graph)
 
+# ---- metapath2vec (`m2v`): torch_geometric.nn.MetaPath2Vec's table - the node types sorted by name, then the dummy row
+M2V_TYPES = ("member", "skill", "team")
+M2V_ORDER = "|".join(M2V_TYPES) + "|dummy"
+_M2V_RELATIONS = ("to", "rev_to")
+
+
+def _metapath(cfg):
+    """(list of (src, rel, dst), label or None) of the m2v section's `metapath_name` (the ONE place that key is read): either `[[triples...], "label"]`, as
+    `graph.structure` is written, or a bare list of triples.  Checked here, before any device call: relations `to` / `rev_to`, node types skill / member / team
+    (anything else, `loc` included, is not built here), every hop one of the four skill-team / member-team directions, a chain (a hop's destination is the next
+    hop's source), and all three types present (the skill block feeds get_dense_vecs, v_loss needs member and team rows)."""
+    raw = cfg_get(cfg_get(cfg, "m2v"), "metapath_name")
+    if raw is None or isinstance(raw, str) or len(raw) == 0:
+        raise ValueError("m2v: metapath_name must be a list of [src, rel, dst] triples, or [[triples...], 'label']")
+    raw, label = list(raw), None
+    if len(raw) == 2 and isinstance(raw[1], str) and not isinstance(raw[0], str) and len(raw[0]) and not isinstance(raw[0][0], str):
+        raw, label = list(raw[0]), raw[1]
+    path = []
+    for hop in raw:
+        if isinstance(hop, str) or len(hop) != 3 or not all(isinstance(x, str) for x in hop):
+            raise ValueError(f"m2v: a metapath entry must be a [src, rel, dst] triple of names, got {hop!r}")
+        s, r, d = (str(x) for x in hop)
+        if r not in _M2V_RELATIONS: raise NotImplementedError(f"m2v: relation {r!r} (only {_M2V_RELATIONS} are built here)")
+        for t in (s, d):
+            if t not in M2V_TYPES: raise NotImplementedError(f"m2v: node type {t!r} (only {M2V_TYPES} are built here)")
+        if "team" not in (s, d) or s == d: raise NotImplementedError(f"m2v: no {s} -> {d} edges in the skill-team-member graph")
+        path.append((s, r, d))
+    for a, b in zip(path[:-1], path[1:]):
+        if a[2] != b[0]: raise ValueError(f"m2v: the metapath does not chain: {a} is followed by {b}")
+    missing = [t for t in M2V_TYPES if t not in {x for s, _, d in path for x in (s, d)}]
+    if missing: raise ValueError(f"m2v: the metapath must visit skill, member and team; missing {missing}")
+    return path, label
+
+
+def m2v_graph(skill, member, drop_teams, metapath):
+    """(type counts in table order, offsets {type: first row} + 'dummy', hops [(src id, dst id, rowptr int64, col int32 LOCAL ids)]) of a metapath over the stm
+    structure.  The CSR of a hop is chosen by its (src, dst) types alone: skill -> team is skill.T, team -> skill is skill, member -> team / team -> member are
+    member.T / member without the rows of `drop_teams` (exactly the member-team edges stm_graph drops)."""
+    skill = scipy.sparse.csr_matrix(skill); member = scipy.sparse.csr_matrix(member)
+    keep = np.ones(member.shape[0], dtype=bool); keep[np.asarray(list(drop_teams), dtype=np.int64)] = False
+    member = scipy.sparse.diags(keep.astype(member.dtype)) @ member
+    member.eliminate_zeros()
+    count = {"member": member.shape[1], "skill": skill.shape[1], "team": skill.shape[0]}
+    mats = {("skill", "team"): lambda: skill.T, ("team", "skill"): lambda: skill, ("member", "team"): lambda: member.T, ("team", "member"): lambda: member}
+    off, at = {}, 0
+    for t in M2V_TYPES: off[t] = at; at += count[t]
+    off["dummy"] = at
+    csr, hops = {}, []
+    for s, _, d in metapath:
+        if (s, d) not in csr:
+            rp, cl = _csr(mats[(s, d)]())
+            csr[(s, d)] = (rp, cl.astype(np.int32))
+        hops.append((M2V_TYPES.index(s), M2V_TYPES.index(d), *csr[(s, d)]))
+    return [count[t] for t in M2V_TYPES], off, hops
+
 
 def _barrier():
     import torch.distributed as dist
@@ -120,10 +179,14 @@ def _rank0_says(flag):
 class Gnn(T2v):
     def __init__(self, output, device, seed, cfg, model):
         super().__init__(output, device, seed, cfg, model)
-        if self.name != "n2v":
-            raise NotImplementedError(f"opentf_amd trains the node2vec table on the device; '{self.name}' stays the reference's mdl.emb.gnn.Gnn")
+        if self.name not in ("n2v", "m2v"):
+            raise NotImplementedError(f"opentf_amd trains the random-walk tables (n2v, m2v) on the device; '{self.name}' stays the reference's mdl.emb.gnn.Gnn")
+        self.metapath, self.metapath_label = _metapath(cfg) if self.name == "m2v" else (None, None)      # refused here, before any device call
+        if self.metapath and int(cfg_get(self._mcfg(), "wl") or 0) > len(self.metapath) and self.metapath[-1][2] != self.metapath[0][0]:
+            raise ValueError("m2v: wl steps outrun the metapath, which does not end on its start type")
         self.writer = summary_writer()
         self.offsets = None
+        self.blocks = None      # {node type: (first row, end row)} of the loaded table
 
     def _mcfg(self):
         return cfg_get(self.cfg, self.name)
@@ -134,7 +197,8 @@ class Gnn(T2v):
         name = (f"/{self.name}.b{cfg_get(m, 'b')}.e{cfg_get(m, 'e')}.ns{cfg_get(m, 'ns')}.lr{cfg_get(m, 'lr')}.es{cfg_get(m, 'es')}.spe{cfg_get(m, 'spe')}"
                 f".d{cfg_get(m, 'd')}.{cfg_get(g, 'dup_edge')}.{structure[1]}")
         name += ".pre" if cfg_get(g, "pre") else ""
-        return name + f".w{cfg_get(m, 'w')}.wl{cfg_get(m, 'wl')}.wn{cfg_get(m, 'wn')}"
+        name += f".w{cfg_get(m, 'w')}.wl{cfg_get(m, 'wl')}.wn{cfg_get(m, 'wn')}"
+        return name + (f".{self.metapath_label}" if self.name == "m2v" and self.metapath_label else "")
 
     def learn(self, teamsvecs, splits=None, time_indexes=None):
         import torch
@@ -156,9 +220,17 @@ class Gnn(T2v):
                                            # after training the whole first fold, and the others' wait inside gloo's connect would be cut by the store's own (short) timeout
         for foldidx in splits["folds"].keys():
             drop = np.concatenate([np.asarray(splits["test"]), np.asarray(splits["folds"][foldidx]["valid"])])
-            rowptr, col, off, n = stm_graph(skill, member, drop)
+            seed = int(self.seed or 0) + 7919 * int(foldidx)
+            if self.name == "m2v":
+                counts, off, hops = m2v_graph(skill, member, drop, self.metapath)
+                n, n_start = off["dummy"] + 1, counts[hops[0][0]]
+            else:
+                rowptr, col, off, n = stm_graph(skill, member, drop)
+                n_start = n
             self.offsets = off
-            init = torch.nn.Embedding(n, d).weight.detach().numpy()       # the draw Node2Vec's constructor makes (gnn.py:153-160)
+            init = torch.nn.Embedding(n, d).weight.detach().numpy()       # the draw Node2Vec's / MetaPath2Vec's constructor makes (gnn.py:153-160): Embedding(count + 1, d) for m2v
+            if self.name == "m2v": make_net = lambda: libntf.MetaPath2Vec(counts, hops, init, seed=seed, device=parse_devices(self.device)[0])
+            else: make_net = lambda: libntf.Node2Vec(rowptr, col, init, seed=seed, device=parse_devices(self.device)[0])
             path = f"{self.output}/f{foldidx}.pt"
             _barrier()                                                     # torchrun: nobody looks for the file while rank 0 may still be writing the previous one
             if not _rank0_says(os.path.exists(path)):                      # gnn.py:402-405: a trained table is loaded, not retrained (rank 0 decides for the job)
@@ -166,19 +238,21 @@ class Gnn(T2v):
                 # the ranks - and no collective sits inside a loop whose trip count a rank decides for itself; the other ranks wait below and read rank 0's file
                 if dist_rank() == 0:
                     if w is None: w = self.writer(log_dir=f"{self.output}/logs4tboard/run_{int(time.time())}")
-                    self._train_fold(libntf, rowptr, col, init, n, member, splits, foldidx, off, m, w, path)
+                    self._train_fold(make_net, n_start, member, splits, foldidx, off, m, w, path)
                 _sync_torch_rng()                                          # (also the barrier) the trainer's loader shuffles consumed torch's CPU generator: the next fold's initial draw stays job-wide
             self.model = self._load_fold(path, off, n)
         if w is not None: w.close()
 
-    def _train_fold(self, libntf, rowptr, col, init, n, member, splits, foldidx, off, m, w, path):
-        """`_train_rw` (gnn.py:401-453) for one fold on this rank's device; writes f{k}.e{e}.pt / f{k}.pt"""
+    def _train_fold(self, make_net, n, member, splits, foldidx, off, m, w, path):
+        """`_train_rw` (gnn.py:401-453) for one fold on this rank's device; writes f{k}.e{e}.pt / f{k}.pt.  n: the loader's range - every node for n2v, the nodes of
+        the metapath's start type for m2v (MetaPath2Vec.loader: range(num_nodes_dict[metapath[0][0]]))"""
         b, lr = int(cfg_get(m, "b")), float(cfg_get(m, "lr"))
         wl, ctx, wn, ns = int(cfg_get(m, "wl")), int(cfg_get(m, "w")), int(cfg_get(m, "wn")), int(cfg_get(m, "ns"))
         spe = cfg_get(m, "spe")
         val_src, val_dst = member_team_edges(member, splits["folds"][foldidx]["valid"], off)
         assert len(val_src), "Empty valid member-team edge set!"
-        net = libntf.Node2Vec(rowptr, col, init, seed=int(self.seed or 0) + 7919 * int(foldidx), device=parse_devices(self.device)[0])
+        if self.name == "m2v": wl += 1              # MetaPath2Vec's walk_length counts STEPS, the device counts nodes per walk
+        net = make_net()
         scheduler = PlateauLR(lr, factor=0.1, patience=2)
         earlystopping = EarlyStopping(patience=int(cfg_get(m, "es")), verbose=True, delta=0, trace_func=log.info)
         cur_lr, e, t_loss, v_loss = lr, -1, 0.0, 0.0
@@ -209,6 +283,9 @@ class Gnn(T2v):
         from . import pyg_reader
         ref = pyg_reader.reference_table(path)      # restricted unpickler, the ONLY load of the file: the pickled cfg (omegaconf or not) resolves to inert holders, this plugin's
                                                     # node_order / node_offsets markers are plain builtins and come through it - plugin or reference is decided from those alone
+        if getattr(self, "name", "n2v") == "m2v":
+            return self._load_fold_m2v(path, ref, off, n)
+        self.blocks = {"skill": (off["skill"], off["member"]), "member": (off["member"], off["team"]), "team": (off["team"], n)}
         if ref["node_order"] is not None and ref["node_order"] != NODE_ORDER:
             raise RuntimeError(f"{path}: node order {ref['node_order']!r}, this build writes and reads {NODE_ORDER!r}")
         if ref["node_order"] == NODE_ORDER:
@@ -228,23 +305,39 @@ class Gnn(T2v):
         log.info(f"Loading the model {path} (trained by the reference: rows re-stacked from {[t for t, _ in blocks]} of {os.path.basename(graph)}) ...")
         return weight
 
+    def _load_fold_m2v(self, path, ref, off, n):
+        """MetaPath2Vec orders its row blocks by the sorted type names, whatever the process: a table without this plugin's marker (one the reference trained) is
+        accepted when its row count is total + 1, and refused otherwise; a marked one must carry this order and these offsets."""
+        want = tuple(off[t] for t in M2V_TYPES) + (n,)
+        if ref["node_order"] is not None:
+            if ref["node_order"] != M2V_ORDER:
+                raise RuntimeError(f"{path}: node order {ref['node_order']!r}, an m2v table of this build has {M2V_ORDER!r}")
+            if ref["node_offsets"] != want:
+                raise RuntimeError(f"{path}: written for node offsets {ref['node_offsets']}, teamsvecs gives {want}")
+        elif ref["weight"].shape[0] != n:
+            raise RuntimeError(f"{path}: {ref['weight'].shape[0]} rows without a node order marker; teamsvecs gives {n} "
+                               f"({' + '.join(M2V_TYPES)} + the dummy row)")
+        self.blocks = {t: (off[t], off[u]) for t, u in zip(M2V_TYPES, M2V_TYPES[1:] + ("dummy",))}
+        log.info(f"Loading the model {path} ...")
+        return ref["weight"]
+
     def _save(self, weight, foldidx, e, t_loss, v_loss, path):
-        """keys and order of gnn.py:445,453, + the node order the rows are sliced by; written whole, then moved into place.  Called by the training rank only: no collective"""
+        """keys and order of gnn.py:445,453, + the node order the rows are sliced by (the first row of each block, then the row count); written whole, then moved
+        into place.  Called by the training rank only: no collective"""
         import torch
         off = self.offsets
+        order = M2V_ORDER if self.name == "m2v" else NODE_ORDER
         tmp = f"{path}.tmp.{os.getpid()}"
         torch.save({"model_state_dict": {"embedding.weight": torch.from_numpy(np.ascontiguousarray(weight))}, "cfg": self.cfg, "f": foldidx, "e": e,
-                    "t_loss": t_loss, "v_loss": v_loss, "node_order": NODE_ORDER,
-                    "node_offsets": (off["skill"], off["member"], off["team"], int(weight.shape[0]))}, tmp)
+                    "t_loss": t_loss, "v_loss": v_loss, "node_order": order,
+                    "node_offsets": tuple(int(off[t]) for t in order.split("|") if t != "dummy") + (int(weight.shape[0]),)}, tmp)
         os.replace(tmp, path)
 
     def _node_emb(self, teamsvecs, node_type):
         if self.model is None:
             raise RuntimeError("no trained table: call learn() first")
-        skill = teamsvecs.get("original_skill", teamsvecs["skill"]) if hasattr(teamsvecs, "get") else teamsvecs["skill"]
-        S, M = skill.shape[1], teamsvecs["member"].shape[1]
-        off = {"skill": (0, S), "member": (S, S + M), "team": (S + M, self.model.shape[0])}[node_type]
-        return self.model[off[0]:off[1]]
+        lo, hi = self.blocks[node_type]          # the row blocks of the table _load_fold loaded
+        return self.model[lo:hi]
 
     def get_dense_vecs(self, teamsvecs, vectype="skill"):
         """gnn.py:484-486.  For 'skill' the table is also registered as teamsvecs['skill_table'] (see the module docstring)."""
