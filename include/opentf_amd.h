@@ -355,6 +355,17 @@ int  ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, int32_t wa
 int  ntf_n2v_last_windows(ntf_n2v* h, int64_t* n_pos, int64_t* n_neg, int32_t* context, int64_t* pos_rows, int64_t* neg_rows);
 int  ntf_n2v_get(ntf_n2v* h, int what /* 0 embedding.weight, 1 gradient */, float* host /* [num_nodes, d] */);
 int  ntf_n2v_edge_bce(ntf_n2v* h, const int64_t* src, const int64_t* dst, int64_t n, float* mean_bce);
+/* The optimiser of a handle (n2v or m2v).  kind 0: dense Adam, the default - every row moves every applied step through its moments.  kind 1: sparse Adam,
+ * torch.optim.SparseAdam as torch_geometric's examples train Node2Vec / MetaPath2Vec(sparse=True) - a different optimiser, not a faster dense Adam.  An applied
+ * step then updates only the TOUCHED rows: those whose id occurs anywhere (start or rest, positive or negative, the dummy row of a metapath handle included) in the
+ * window rows whose gradient is in the buffer, the rows of earlier apply = 0 calls still pending included.  Touched goes by the id, not by g != 0: a touched row
+ * whose summed gradient is exactly zero still decays its moments and moves.  Per element of a touched row, with b1 0.9, b2 0.999, eps 1e-8, t = applied steps so far:
+ *   m += (1 - b1) (g - m);  v += (1 - b2) (g g - v);  p -= lr sqrt(1 - b2^t) / (1 - b1^t) * m / (sqrt(v) + eps)        (torch.optim._functional.sparse_adam)
+ * every other row keeps the bits of p, m and v.  Afterwards the gradient is zero everywhere and no row is marked; ntf_n2v_get(what = 1) clears the marks with the
+ * gradient.  NTF_EINVAL: another kind.  NTF_ESTATE: an applied step has been taken, or a gradient is pending from apply = 0 calls.  A refused call changes nothing.
+ * ntf_n2v_moments: exp_avg and exp_avg_sq, [num_nodes, d] each without the pad columns, either pointer may be NULL; reads only, in both modes. */
+int  ntf_n2v_set_optimizer(ntf_n2v* h, int32_t kind /* 0 dense Adam, 1 sparse Adam */);
+int  ntf_n2v_moments(ntf_n2v* h, float* exp_avg /* [num_nodes, d] or NULL */, float* exp_avg_sq /* [num_nodes, d] or NULL */);
 
 /* ---- metapath2vec skill-embedding producer on the device                                   src/mdl/emb/gnn.py (`m2v` branch of the Gnn plugin, trained by _train_rw)
  * torch_geometric.nn.MetaPath2Vec 2.6.1 as published (restated in tests/m2v_reference.py): after the walks it IS node2vec - the same windows, loss, dense Adam and
@@ -375,7 +386,8 @@ int  ntf_n2v_edge_bce(ntf_n2v* h, const int64_t* src, const int64_t* dst, int64_
  * Refused with NTF_EINVAL, before anything is allocated / before the step index is taken, changing nothing: n_types outside 1 .. NTF_M2V_MAX_TYPES, n_hops outside
  * 1 .. NTF_M2V_MAX_HOPS, a type id outside [0, n_types), a negative count, hop_dst[i] != hop_src[i + 1], a rowptr that does not start at 0 or is not monotone, a column
  * outside its destination type, d outside 1 .. 256; at ntf_n2v_train_batch / ntf_n2v_walks: walk_length - 1 > n_hops on a metapath that is not a cycle
- * (hop_dst[n_hops - 1] != hop_src[0]), a start id outside the start type.  The optimiser is the dense Adam of the n2v section.
+ * (hop_dst[n_hops - 1] != hop_src[0]), a start id outside the start type.  The optimiser is the dense Adam of the n2v section, or its sparse Adam
+ * after ntf_n2v_set_optimizer(1).
  * The pairs of a metapath handle run through k_m2v_pairs, which sums the terms that land on the dummy row per workgroup before they reach the gradient (same terms, another
  * order of the f32 sums on that one row); the environment variable NTF_M2V_PAIRS=0, read by ntf_m2v_create, keeps node2vec's k_n2v_pairs for A/B runs. */
 #define NTF_M2V_MAX_TYPES 8

@@ -4,7 +4,8 @@
 //   loader  : per batch of start nodes, `walks_per_node` uniform random walks (p = q = 1) of `walk_length` nodes, cut into windows of
 //             `context_size`; negatives = the same start nodes followed by uniformly random nodes
 //   loss    : -mean log(sigmoid(<e_start, e_rest>) + 1e-15) over positive pairs  - mean log(1 - sigmoid(.) + 1e-15) over negative pairs
-//   update  : torch.optim.Adam on the dense embedding matrix (every row moves every step through its moments)
+//   update  : torch.optim.Adam on the dense embedding matrix (every row moves every step through its moments); opt-in (ntf_n2v_set_optimizer) torch.optim.SparseAdam
+//             over the rows the batch names: k_n2v_touch -> k_n2v_compact -> k_n2v_adam_rows
 // One wave per window row: the start row lives in registers (d / 64 values per lane), every rest row costs one coalesced row read, a wave
 // reduction and one coalesced f32 atomic row add (the forms that run at full rate on gfx950: 256 contiguous bytes per wave-instruction).
 // metapath2vec (torch_geometric.nn.MetaPath2Vec, the `m2v` method of the same plugin) is node2vec after the walks: ntf_m2v_create makes an ntf_n2v handle that carries a
@@ -39,6 +40,9 @@ struct ntf_n2v {
     const int64_t *win_p = nullptr, *win_n = nullptr; int64_t n_win_p = 0, n_win_n = 0; int win_ctx = 0;   // the last batch's window rows inside d_rows (ntf_n2v_last_windows)
     double* d_loss = nullptr;
     int64_t adam_t = 0; uint64_t seed = 0, step = 0;
+    // ntf_n2v_set_optimizer: 0 = dense Adam, 1 = sparse Adam over the rows the windows name.  d_touch: one bit per row (ceil(n / 32) words), set by k_n2v_touch and
+    // cleared by k_n2v_compact, which lists the marked rows in d_list and counts them in d_count.  pend_entries: the window entries whose gradient is in G (both modes)
+    int opt = 0; uint32_t* d_touch = nullptr; int64_t* d_list = nullptr; int64_t list_cap = 0; unsigned long long* d_count = nullptr; int64_t pend_entries = 0;
     bool m2v = false, cycle = false; m2v_path mp; int64_t start_count = 0;   // ntf_m2v_create: the metapath; rowptr / col above stay NULL, n = total + 1
     bool dummy_pairs = false;                                                // pairs through k_m2v_pairs: a metapath handle's default (NTF_M2V_PAIRS=0, read by ntf_m2v_create, turns it off)
     std::vector<void*> hop_bufs;                                           // the per-hop CSRs the metapath points into
@@ -223,6 +227,64 @@ __global__ void k_n2v_adam(float* __restrict__ p, float* __restrict__ g, float* 
     }
 }
 
+// ---- sparse Adam (torch.optim.SparseAdam: only the rows a batch names move, their moments decay only in the steps that name them; ntf_n2v_set_optimizer(1))
+// marks the row of every window entry, start or rest: one bit per row.  A hub is named hundreds of times a batch: the plain read keeps all but the first of them
+// off the atomic unit (a stale read costs one more atomic OR, nothing else).  `hot` (the dummy row of a metapath handle, -1 otherwise) is named by a sizeable
+// share of ALL entries: the whole grid is in flight before the first OR lands, so the read alone left hundreds of thousands of atomics on one address (0.51 ms
+// of a 2.26 ms batch at dblp shapes); of the lanes of a wave that would mark it, one does.
+__global__ __launch_bounds__(256) void k_n2v_touch(const int64_t* __restrict__ rows, int64_t n_entries, int64_t hot, uint32_t* __restrict__ bits) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t v = t < n_entries ? rows[t] : -1;        // no early return: the ballot is the whole wave's
+    uint32_t b = 0; bool need = false;
+    if (v >= 0) { b = 1u << (uint32_t)(v & 31); need = !(bits[v >> 5] & b); }
+    const bool on_hot = need && v == hot;
+    const unsigned long long hm = __ballot(on_hot);
+    if (on_hot && (int)(threadIdx.x & 63) != __ffsll(hm) - 1) need = false;
+    if (need) atomicOr(bits + (v >> 5), b);
+}
+// the marked rows as a list: one thread per bitmap word, a wave takes ONE slot range from the counter (inclusive scan of the popcounts, the last lane asks), every
+// lane writes the ids of its word behind those of the lanes before it and clears the word.  The order of the waves' ranges is not fixed; each row is listed once.
+__global__ __launch_bounds__(256) void k_n2v_compact(uint32_t* __restrict__ bits, int64_t n_words, int64_t* __restrict__ list, unsigned long long* __restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t word = w < n_words ? bits[w] : 0u;            // no early return: every lane takes part in the shuffles
+    if (word) bits[w] = 0u;
+    const int c = __popc(word);
+    int incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int up = __shfl_up(incl, o, 64); if (lane >= o) incl += up; }
+    const int total = __shfl(incl, 63, 64);
+    if (total == 0) return;                                // wave-uniform
+    unsigned long long base = 0;
+    if (lane == 63) base = atomicAdd(count, (unsigned long long)total);
+    const uint32_t lo = __shfl((uint32_t)base, 63, 64), hi = __shfl((uint32_t)(base >> 32), 63, 64);
+    int64_t at = (int64_t)(((unsigned long long)hi << 32) | lo) + (incl - c);
+    while (word) { list[at++] = w * 32 + (__ffs(word) - 1); word &= word - 1; }
+}
+// torch.optim._functional.sparse_adam on the listed rows, one wave per row (NV = d / 64 values per lane), and the row of G cleared for the next batch.
+// step = lr sqrt(1 - b2^t) / (1 - b1^t); omb1 = 1 - b1, omb2 = 1 - b2 (rounded once, on the host); eps is added to sqrt(v) itself - not k_n2v_adam's placement.
+// The grid strides over the count k_n2v_compact left on the device: no host read between the two.  A pad column has g = m = v = 0 and stays 0.
+template <int NV>
+__global__ __launch_bounds__(256) void k_n2v_adam_rows(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                       const int64_t* __restrict__ list, const unsigned long long* __restrict__ count, int d, float step,
+                                                       float omb1, float omb2, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t n = (int64_t)*count;
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += (int64_t)gridDim.x * 4) {
+        const int64_t o = list[i] * d + lane;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const int64_t q = o + 64 * k;
+            const float gg = g[q];
+            float mm = m[q], vv = v[q];
+            mm += omb1 * (gg - mm);
+            vv += omb2 * (gg * gg - vv);
+            p[q] -= step * (mm / (sqrtf(vv) + eps));
+            m[q] = mm; v[q] = vv; g[q] = 0.f;
+        }
+    }
+}
+
 // v_loss of _train_rw (gnn.py:420-431): mean BCE-with-logits of the held-out edges' scores against 1 = mean softplus(-score)
 __global__ __launch_bounds__(256) void k_n2v_edge_bce(const float* __restrict__ W, const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int64_t n, int d,
                                                       double* __restrict__ out) {
@@ -239,7 +301,8 @@ extern "C" void ntf_n2v_destroy(ntf_n2v* h) {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->st) hipStreamSynchronize(h->st);
-    for (void* p : {(void*)h->rowptr, (void*)h->col, (void*)h->W, (void*)h->G, (void*)h->M1, (void*)h->V2, (void*)h->d_batch, (void*)h->d_rows, (void*)h->d_loss})
+    for (void* p : {(void*)h->rowptr, (void*)h->col, (void*)h->W, (void*)h->G, (void*)h->M1, (void*)h->V2, (void*)h->d_batch, (void*)h->d_rows, (void*)h->d_loss,
+                    (void*)h->d_touch, (void*)h->d_list, (void*)h->d_count})
         if (p) hipFree(p);
     for (void* p : h->hop_bufs) if (p) hipFree(p);
     if (h->st) hipStreamDestroy(h->st);
@@ -374,6 +437,43 @@ extern "C" int ntf_n2v_walks(ntf_n2v* h, const int64_t* start, int64_t n, int32_
     return NTF_OK;
 }
 
+extern "C" int ntf_n2v_set_optimizer(ntf_n2v* h, int32_t kind) {
+    if (!h) return NTF_EINVAL;
+    if (kind != 0 && kind != 1) FAIL(h, NTF_EINVAL, "n2v: optimizer kind must be 0 (dense Adam) or 1 (sparse Adam)");
+    if (h->adam_t > 0 || h->pend_entries > 0) FAIL(h, NTF_ESTATE, "n2v: the optimizer is chosen before the first step and with no gradient pending");
+    if (kind == 1 && !h->d_touch) {
+        HIPCHK(h, hipSetDevice(h->device));
+        const int64_t words = (h->n + 31) / 32;
+        uint32_t* bits = nullptr; unsigned long long* cnt = nullptr;
+        int r = dev_alloc(h, &bits, words); if (r) return r;
+        if ((r = dev_alloc(h, &cnt, 1))) { hipFree(bits); return r; }
+        h->d_touch = bits; h->d_count = cnt;
+        HIPCHK(h, hipMemsetAsync(h->d_touch, 0, (size_t)words * 4, h->st));
+        HIPCHK(h, hipMemsetAsync(h->d_count, 0, 8, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
+    }
+    h->opt = kind;
+    return NTF_OK;
+}
+
+// the sparse step: marked rows -> list -> sparse_adam on the listed rows; the marks, the rows of G and the pending count are clear afterwards
+static void launch_sparse_adam(ntf_n2v* h, float lr) {
+    const double b1 = 0.9, b2 = 0.999;
+    const double bc1 = 1.0 - std::pow(b1, (double)h->adam_t), bc2 = 1.0 - std::pow(b2, (double)h->adam_t);
+    const float step = (float)((double)lr * std::sqrt(bc2) / bc1);
+    const int64_t words = (h->n + 31) / 32, cap = std::min<int64_t>(h->n, h->pend_entries);
+    if (cap <= 0) return;
+    hipMemsetAsync(h->d_count, 0, 8, h->st);
+    hipLaunchKernelGGL(k_n2v_compact, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, h->st, h->d_touch, words, h->d_list, h->d_count);
+    const dim3 grid((unsigned)std::min<int64_t>((cap + 3) / 4, 256 * 8)), block(256);
+    switch (h->d / 64) {
+        case 1: hipLaunchKernelGGL(k_n2v_adam_rows<1>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f); break;
+        case 2: hipLaunchKernelGGL(k_n2v_adam_rows<2>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f); break;
+        case 3: hipLaunchKernelGGL(k_n2v_adam_rows<3>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f); break;
+        default: hipLaunchKernelGGL(k_n2v_adam_rows<4>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f); break;
+    }
+}
+
 static void launch_pairs(ntf_n2v* h, const int64_t* rows, int64_t n_rows, int ctx, int positive) {
     if (n_rows <= 0 || ctx < 2) return;
     const float inv = 1.f / (float)(n_rows * (ctx - 1));
@@ -414,6 +514,9 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
         if (m2v_too_long(h, walk_length)) FAIL(h, NTF_EINVAL, "m2v: a walk longer than the metapath needs a metapath that ends on its start type");
         if ((r = stage_batch(h, batch, B))) return r;
     }
+    // the window entries of this call: what k_n2v_touch runs over, and with the pending ones the bound of the row list
+    const int64_t entries = injected ? (n_pos + n_neg) * context : (int64_t)B * walks_per_node * (1 + (int64_t)num_neg) * (walk_length + 1 - context) * context;
+    if (h->opt == 1 && (r = dev_grow(h, &h->d_list, &h->list_cap, std::min<int64_t>(h->n, h->pend_entries + entries)))) return r;
     HIPCHK(h, hipMemsetAsync(h->d_loss, 0, 8, h->st));
     const uint64_t step = h->step++;
     if (injected) {
@@ -446,8 +549,17 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
         h->win_p = win_p; h->win_n = win_n; h->n_win_p = pw * nw; h->n_win_n = ng * nw;
     }
     h->win_ctx = context;
-    if (apply) {
+    h->pend_entries += entries;
+    // sparse mode: the positive and the negative window rows lie back to back from win_p on, `entries` ids in all
+    if (h->opt == 1 && entries > 0) hipLaunchKernelGGL(k_n2v_touch, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, h->st, h->win_p, entries,
+                                                       h->m2v ? h->mp.total : (int64_t)-1, h->d_touch);
+    if (apply && h->opt == 1) {
         h->adam_t += 1;
+        launch_sparse_adam(h, lr);
+        h->pend_entries = 0;
+    } else if (apply) {
+        h->adam_t += 1;
+        h->pend_entries = 0;
         const double b1 = 0.9, b2 = 0.999;
         const double bc1 = 1.0 - std::pow(b1, (double)h->adam_t), bc2 = 1.0 - std::pow(b2, (double)h->adam_t);
         const int64_t np = h->n * h->d;
@@ -470,7 +582,21 @@ extern "C" int ntf_n2v_get(ntf_n2v* h, int what, float* host) {   // what: 0 = e
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->st));
     HIPCHK(h, hipMemcpy2D(host, (size_t)h->d_user * 4, what ? h->G : h->W, (size_t)h->d * 4, (size_t)h->d_user * 4, (size_t)h->n, hipMemcpyDeviceToHost));
-    if (what) HIPCHK(h, hipMemsetAsync(h->G, 0, (size_t)h->n * h->d * 4, h->st));   // reading the gradient consumes it
+    if (what) {   // reading the gradient consumes it, and with it the marks of the rows it named
+        HIPCHK(h, hipMemsetAsync(h->G, 0, (size_t)h->n * h->d * 4, h->st));
+        if (h->d_touch) HIPCHK(h, hipMemsetAsync(h->d_touch, 0, (size_t)((h->n + 31) / 32) * 4, h->st));
+        h->pend_entries = 0;
+    }
+    return NTF_OK;
+}
+
+extern "C" int ntf_n2v_moments(ntf_n2v* h, float* exp_avg, float* exp_avg_sq) {   // Adam's two moments [num_nodes, d], either may be NULL; reads only
+    if (!h) return NTF_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    const size_t row = (size_t)h->d_user * 4;
+    if (exp_avg) HIPCHK(h, hipMemcpy2D(exp_avg, row, h->M1, (size_t)h->d * 4, row, (size_t)h->n, hipMemcpyDeviceToHost));
+    if (exp_avg_sq) HIPCHK(h, hipMemcpy2D(exp_avg_sq, row, h->V2, (size_t)h->d * 4, row, (size_t)h->n, hipMemcpyDeviceToHost));
     return NTF_OK;
 }
 

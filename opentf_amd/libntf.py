@@ -17,6 +17,7 @@ NTF_MAX_LAYERS = 8
 NTF_MC_MAX_GROUP = 16     # Monte-Carlo passes per fused-MC launch at most (include/opentf_amd.h)
 NTF_MC_TILE_GROUP = 4     # 32-expert tiles a workgroup of that kernel carries across the passes
 NTF_EINVAL = -1
+NTF_ESTATE = -3
 INPUT_DENSE, INPUT_MEANPOOL, INPUT_MULTIHOT = 0, 1, 2
 NSD = {None: 0, "": 0, "None": 0, "uniform": 1, "unigram": 2, "unigram_b": 3}
 P_WEIGHT, P_BIAS, P_RHO_WEIGHT, P_RHO_BIAS = 0, 1, 2, 3
@@ -115,6 +116,8 @@ SYMBOLS = {
     "ntf_n2v_get": (C.c_int, [_P, C.c_int, _P]),
     "ntf_n2v_last_windows": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ntf_n2v_edge_bce": (C.c_int, [_P, _P, _P, _I64, _P]),
+    "ntf_n2v_set_optimizer": (C.c_int, [_P, _I32]),
+    "ntf_n2v_moments": (C.c_int, [_P, _P, _P]),
     "ntf_m2v_create": (C.c_int, [C.c_int, _I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _U64, C.POINTER(_P)]),
     "ntf_d2v_create": (C.c_int, [C.c_int, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _U64, C.POINTER(_P)]),
     "ntf_d2v_destroy": (None, [_P]),
@@ -644,17 +647,25 @@ class Engine(_Handle):
 
 
 class Node2Vec(_Handle):
-    """torch_geometric.nn.Node2Vec (p = q = 1) resident on one MI355X: embedding.weight [num_nodes, d] + dense Adam (include/opentf_amd.h)."""
+    """torch_geometric.nn.Node2Vec (p = q = 1) resident on one MI355X: embedding.weight [num_nodes, d] + dense Adam, or with sparse=True torch.optim.SparseAdam
+    over the rows a batch names (include/opentf_amd.h, ntf_n2v_set_optimizer)."""
 
     _CREATE, _DESTROY, _LAST_ERROR, _TAG = "ntf_n2v_create", "ntf_n2v_destroy", "ntf_n2v_last_error", " n2v"
 
-    def __init__(self, rowptr, col, init_weight, seed=0, device=0):
+    def __init__(self, rowptr, col, init_weight, seed=0, device=0, sparse=False):
         self.rowptr = np.ascontiguousarray(rowptr, dtype=np.int64); self.col = np.ascontiguousarray(col, dtype=np.int32)
         w = _f32(init_weight)
         self.num_nodes, self.d = w.shape
         if len(self.rowptr) != self.num_nodes + 1:
             raise NtfError("rowptr must have num_nodes + 1 entries")
         self._create(int(device), self.num_nodes, self.d, _ptr(self.rowptr), _ptr(self.col), _ptr(w), int(seed) & (2**64 - 1))
+        self.sparse = False
+        if sparse: self.set_optimizer(True)
+
+    def set_optimizer(self, sparse):
+        """dense Adam (False / 0) or sparse Adam (True / 1); refused once a step has been applied or while a gradient is pending"""
+        self._ck(lib().ntf_n2v_set_optimizer(self._h, int(bool(sparse))))
+        self.sparse = bool(sparse)
 
     def walks(self, start, walk_length, step=0):
         s = np.ascontiguousarray(start, dtype=np.int64)
@@ -691,6 +702,11 @@ class Node2Vec(_Handle):
         out = np.empty((self.num_nodes, self.d), dtype=np.float32)
         self._ck(lib().ntf_n2v_get(self._h, 1, _ptr(out))); return out
 
+    def moments(self):
+        """(exp_avg, exp_avg_sq) of the optimiser, [num_nodes, d] each"""
+        m = np.empty((self.num_nodes, self.d), dtype=np.float32); v = np.empty((self.num_nodes, self.d), dtype=np.float32)
+        self._ck(lib().ntf_n2v_moments(self._h, _ptr(m), _ptr(v))); return m, v
+
     def edge_bce(self, src, dst):
         s = np.ascontiguousarray(src, dtype=np.int64); t = np.ascontiguousarray(dst, dtype=np.int64); out = C.c_float()
         self._ck(lib().ntf_n2v_edge_bce(self._h, _ptr(s), _ptr(t), len(s), C.byref(out))); return out.value
@@ -704,7 +720,7 @@ class MetaPath2Vec(Node2Vec):
 
     _CREATE = "ntf_m2v_create"
 
-    def __init__(self, type_counts, hops, init_weight, seed=0, device=0):
+    def __init__(self, type_counts, hops, init_weight, seed=0, device=0, sparse=False):
         tc = np.ascontiguousarray(type_counts, dtype=np.int64).reshape(-1)
         w = _f32(init_weight)
         self.num_nodes, self.d = w.shape
@@ -721,6 +737,8 @@ class MetaPath2Vec(Node2Vec):
         rps = (C.c_void_p * max(len(hops), 1))(*[a.ctypes.data for a in self._rowptr])
         cls = (C.c_void_p * max(len(hops), 1))(*[a.ctypes.data if a.size else None for a in self._col])
         self._create(int(device), len(tc), _ptr(tc), len(hops), _ptr(hs), _ptr(hd), rps, cls, self.d, _ptr(w), int(seed) & (2**64 - 1))
+        self.sparse = False
+        if sparse: self.set_optimizer(True)
 
 
 class Doc2Vec(_Handle):

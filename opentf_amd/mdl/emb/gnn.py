@@ -7,7 +7,7 @@ What the caller (src/main.py:100-153) does and what it gets here:
       per fold: the 'stm' graph (skill - team - member) without the member-team edges of the test and of that fold's validation teams
       (gnn.py:84-116), `torch_geometric.nn.Node2Vec` (p = q = 1) trained by `_train_rw` (gnn.py:401-453: shuffled node batches, Adam,
       ReduceLROnPlateau on v_loss, EarlyStopping, `f{k}.pt` / `f{k}.e{e}.pt` checkpoints holding `embedding.weight`).  Here the walks,
-      the skip-gram loss, its gradient and the dense Adam run in `opentf_amd/csrc/ntf_n2v.hip`; control flow, file names and
+      the skip-gram loss, its gradient and the dense Adam (or, with `sparse: true` in the method's section, sparse Adam) run in `opentf_amd/csrc/ntf_n2v.hip`; control flow, file names and
       checkpoint keys are the reference's.  An existing `f{k}.pt` is loaded instead, as gnn.py:402-405 does: one written by THIS plugin carries the node order its rows are
       sliced by; one the reference trained follows the node-store order of ITS pickled graph (`{structure}.{dup_edge}.graph.pkl` beside the splits directory,
       gnn.py:21-23) - that file is read (opentf_amd/mdl/emb/pyg_reader.py: a restricted unpickler, no torch_geometric) and the rows are re-stacked; without the graph file
@@ -191,6 +191,10 @@ class Gnn(T2v):
     def _mcfg(self):
         return cfg_get(self.cfg, self.name)
 
+    def _sparse(self):
+        """the `sparse` key of the n2v / m2v section (Node2Vec / MetaPath2Vec(sparse=True) trained with torch.optim.SparseAdam); absent or false: dense Adam"""
+        return bool(cfg_get(self._mcfg(), "sparse"))
+
     def _dirname(self):
         m, g = self._mcfg(), cfg_get(self.cfg, "graph")
         structure = cfg_get(g, "structure")
@@ -198,7 +202,8 @@ class Gnn(T2v):
                 f".d{cfg_get(m, 'd')}.{cfg_get(g, 'dup_edge')}.{structure[1]}")
         name += ".pre" if cfg_get(g, "pre") else ""
         name += f".w{cfg_get(m, 'w')}.wl{cfg_get(m, 'wl')}.wn{cfg_get(m, 'wn')}"
-        return name + (f".{self.metapath_label}" if self.name == "m2v" and self.metapath_label else "")
+        name += f".{self.metapath_label}" if self.name == "m2v" and self.metapath_label else ""
+        return name + (".sparse" if self._sparse() else "")      # the last part: tables of the two optimisers never share an f{k}.pt
 
     def learn(self, teamsvecs, splits=None, time_indexes=None):
         import torch
@@ -229,8 +234,8 @@ class Gnn(T2v):
                 n_start = n
             self.offsets = off
             init = torch.nn.Embedding(n, d).weight.detach().numpy()       # the draw Node2Vec's / MetaPath2Vec's constructor makes (gnn.py:153-160): Embedding(count + 1, d) for m2v
-            if self.name == "m2v": make_net = lambda: libntf.MetaPath2Vec(counts, hops, init, seed=seed, device=parse_devices(self.device)[0])
-            else: make_net = lambda: libntf.Node2Vec(rowptr, col, init, seed=seed, device=parse_devices(self.device)[0])
+            if self.name == "m2v": make_net = lambda: libntf.MetaPath2Vec(counts, hops, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse())
+            else: make_net = lambda: libntf.Node2Vec(rowptr, col, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse())
             path = f"{self.output}/f{foldidx}.pt"
             _barrier()                                                     # torchrun: nobody looks for the file while rank 0 may still be writing the previous one
             if not _rank0_says(os.path.exists(path)):                      # gnn.py:402-405: a trained table is loaded, not retrained (rank 0 decides for the job)
