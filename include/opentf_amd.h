@@ -388,8 +388,9 @@ int  ntf_n2v_moments(ntf_n2v* h, float* exp_avg /* [num_nodes, d] or NULL */, fl
  * outside its destination type, d outside 1 .. 256; at ntf_n2v_train_batch / ntf_n2v_walks: walk_length - 1 > n_hops on a metapath that is not a cycle
  * (hop_dst[n_hops - 1] != hop_src[0]), a start id outside the start type.  The optimiser is the dense Adam of the n2v section, or its sparse Adam
  * after ntf_n2v_set_optimizer(1).
- * The pairs of a metapath handle run through k_m2v_pairs, which sums the terms that land on the dummy row per workgroup before they reach the gradient (same terms, another
- * order of the f32 sums on that one row); the environment variable NTF_M2V_PAIRS=0, read by ntf_m2v_create, keeps node2vec's k_n2v_pairs for A/B runs. */
+ * The pairs of a metapath handle run through the DUMMY form of the pair kernel (k_n2v_pairs<NV, true>), which sums the terms that land on the dummy row per workgroup before
+ * they reach the gradient (same terms, another order of the f32 sums on that one row); the environment variable NTF_M2V_PAIRS=0, read by ntf_m2v_create, keeps node2vec's
+ * plain form (k_n2v_pairs<NV, false>) for A/B runs. */
 #define NTF_M2V_MAX_TYPES 8
 #define NTF_M2V_MAX_HOPS  8
 int  ntf_m2v_create(int device, int32_t n_types, const int64_t* type_count /* [n_types], table order */,

@@ -492,18 +492,9 @@ extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32
     // PV-DM at the reference's window (src/mdl/emb/__config__.yaml: w = 5): word-vector additions deferred to one per kept position (k_d2v_epoch<.., 5>); NTF_D2V_DEFER=0: the plain kernel
     static const bool defer_ok = !(getenv("NTF_D2V_DEFER") && atoi(getenv("NTF_D2V_DEFER")) == 0);
     if (dm && window == 5 && defer_ok && h->dp >= 128) {     // (d = 64: the rows are 256 B and the plain kernel's shorter chain wins - 45.7 against 49.4 ms; d = 128 / 192 / 256: 55 / 78 / 98 against 66 / 102 / 133)
-        switch (h->dp / 64) {
-            case 2: hipLaunchKernelGGL((k_d2v_epoch<2, 5>), grid, block, 0, h->st, a, dm); break;
-            case 3: hipLaunchKernelGGL((k_d2v_epoch<3, 5>), grid, block, 0, h->st, a, dm); break;
-            default: hipLaunchKernelGGL((k_d2v_epoch<4, 5>), grid, block, 0, h->st, a, dm); break;
-        }
+        with_nv<2>(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL((k_d2v_epoch<decltype(nv)::value, 5>), grid, block, 0, h->st, a, dm); });   // <1, 5> is never launched, so never built
     } else
-    switch (h->dp / 64) {
-        case 1: hipLaunchKernelGGL(k_d2v_epoch<1>, grid, block, 0, h->st, a, dm); break;
-        case 2: hipLaunchKernelGGL(k_d2v_epoch<2>, grid, block, 0, h->st, a, dm); break;
-        case 3: hipLaunchKernelGGL(k_d2v_epoch<3>, grid, block, 0, h->st, a, dm); break;
-        default: hipLaunchKernelGGL(k_d2v_epoch<4>, grid, block, 0, h->st, a, dm); break;
-    }
+        with_nv(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL(k_d2v_epoch<decltype(nv)::value>, grid, block, 0, h->st, a, dm); });
     if (device_ms) HIPCHK(h, hipEventRecord(h->ev1, h->st));
     hipError_t s = hipGetLastError();
     if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("d2v kernel launch: ") + hipGetErrorString(s));
@@ -553,12 +544,7 @@ extern "C" int ntf_d2v_infer(ntf_d2v* h, int64_t n, const int64_t* q_ptr, const 
     const int64_t want = (n + 3) / 4;
     const dim3 grid(serial ? 1u : (unsigned)std::min<int64_t>(want, 256 * 16)), block(serial ? 64 : 256);
     if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
-    switch (h->dp / 64) {
-        case 1: hipLaunchKernelGGL(k_d2v_infer<1>, grid, block, 0, h->st, a); break;
-        case 2: hipLaunchKernelGGL(k_d2v_infer<2>, grid, block, 0, h->st, a); break;
-        case 3: hipLaunchKernelGGL(k_d2v_infer<3>, grid, block, 0, h->st, a); break;
-        default: hipLaunchKernelGGL(k_d2v_infer<4>, grid, block, 0, h->st, a); break;
-    }
+    with_nv(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL(k_d2v_infer<decltype(nv)::value>, grid, block, 0, h->st, a); });
     if (device_ms) HIPCHK(h, hipEventRecord(h->ev1, h->st));
     hipError_t s = hipGetLastError();
     if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("d2v infer kernel launch: ") + hipGetErrorString(s));

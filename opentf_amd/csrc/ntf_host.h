@@ -1,10 +1,11 @@
 // The host scaffold of every entry of the library, once: the check macros and allocators of a handle with an `err` string (ntf_engine, ntf_n2v, ntf_d2v,
-// ntf_knn), the RAII device buffer of the handle-less entries (ntf_metrics, ntf_auc, ntf_cooc) and the upload of a host table into padded device rows.
+// ntf_knn), the RAII device buffer of the handle-less entries (ntf_metrics, ntf_auc, ntf_cooc), the upload of a host table into padded device rows and the dispatch of a row width onto the kernels' NV template argument.
 #pragma once
 #include "../../include/opentf_amd.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 
 #define HIPCHK(h, call)                                                                                   \
     do {                                                                                                  \
@@ -55,6 +56,17 @@ struct DevBuf {
 inline hipError_t upload_padded(float* dst, int64_t dp, const float* src, int64_t d, int64_t rows) {
     if (dp != d) { const hipError_t s = hipMemset(dst, 0, (size_t)rows * dp * 4); if (s != hipSuccess) return s; }
     return hipMemcpy2D(dst, (size_t)dp * 4, src, (size_t)d * 4, (size_t)d * 4, (size_t)rows, hipMemcpyHostToDevice);
+}
+
+// a row width of nv = d / 64 in LO .. 4 sixty-fours as a compile-time constant: f(std::integral_constant<int, nv>()) and true; any other nv calls nothing and gives false.
+// LO > 1 keeps the widths below it from being instantiated at all (a kernel that is never launched does not enter the code object).
+template <int LO = 1, class F> bool with_nv(int nv, F&& f) {
+    if (nv < LO || nv > 4) return false;
+    if constexpr (LO <= 1) if (nv == 1) f(std::integral_constant<int, 1>());
+    if constexpr (LO <= 2) if (nv == 2) f(std::integral_constant<int, 2>());
+    if constexpr (LO <= 3) if (nv == 3) f(std::integral_constant<int, 3>());
+    if (nv == 4) f(std::integral_constant<int, 4>());
+    return true;
 }
 
 }  // namespace ntf

@@ -9,7 +9,9 @@
 // One wave per window row: the start row lives in registers (d / 64 values per lane), every rest row costs one coalesced row read, a wave
 // reduction and one coalesced f32 atomic row add (the forms that run at full rate on gfx950: 256 contiguous bytes per wave-instruction).
 // metapath2vec (torch_geometric.nn.MetaPath2Vec, the `m2v` method of the same plugin) is node2vec after the walks: ntf_m2v_create makes an ntf_n2v handle that carries a
-// metapath over per-hop CSRs, k_m2v_walks / k_m2v_negs draw its typed walks and negatives, k_m2v_pairs is k_n2v_pairs with the dummy row's terms summed per workgroup.
+// metapath over per-hop CSRs.  Its own kernels are k_m2v_walks / k_m2v_negs (typed walks and negatives; the draws are n2v_draw's, as k_n2v_walks' / k_n2v_negs'); every
+// other kernel serves both handle kinds: k_n2v_windows, k_n2v_adam, the three of sparse Adam, k_n2v_edge_bce, and the one pair kernel k_n2v_pairs<NV, DUMMY> - its
+// plain form is node2vec's, its DUMMY form (a metapath handle's default) sums the dummy row's terms per workgroup.
 #include "../../include/opentf_amd.h"
 #include "ntf_device.h"
 #include "ntf_host.h"
@@ -44,13 +46,21 @@ struct ntf_n2v {
     // cleared by k_n2v_compact, which lists the marked rows in d_list and counts them in d_count.  pend_entries: the window entries whose gradient is in G (both modes)
     int opt = 0; uint32_t* d_touch = nullptr; int64_t* d_list = nullptr; int64_t list_cap = 0; unsigned long long* d_count = nullptr; int64_t pend_entries = 0;
     bool m2v = false, cycle = false; m2v_path mp; int64_t start_count = 0;   // ntf_m2v_create: the metapath; rowptr / col above stay NULL, n = total + 1
-    bool dummy_pairs = false;                                                // pairs through k_m2v_pairs: a metapath handle's default (NTF_M2V_PAIRS=0, read by ntf_m2v_create, turns it off)
+    bool dummy_pairs = false;                                                // pairs through k_n2v_pairs<NV, true>: a metapath handle's default (NTF_M2V_PAIRS=0, read by ntf_m2v_create, turns it off)
     std::vector<void*> hop_bufs;                                           // the per-hop CSRs the metapath points into
     std::string err;
 };
 static thread_local std::string g_n2v_create_error;
 
 extern "C" const char* ntf_n2v_last_error(const ntf_n2v* h) { return h ? h->err.c_str() : g_n2v_create_error.c_str(); }
+
+// the draw of position s >= 1 of row r, for walks (base 0) and negatives (base N2V_NEG_BASE) of either handle kind: word (s - 1) & 3 of
+// Philox4x32-10(counter (r lo, r hi, base + ((s - 1) >> 2), step), key (k0, k1)).  `rnd` holds the block and is refilled every fourth position; s must go up by one from 1.
+constexpr uint32_t N2V_NEG_BASE = 0x4E454700u;
+__device__ __forceinline__ uint32_t n2v_draw(uint4& rnd, uint32_t base, int64_t r, int s, uint32_t k0, uint32_t k1, uint32_t step) {
+    if (((s - 1) & 3) == 0) rnd = philox4x32(make_uint4((uint32_t)r, (uint32_t)(r >> 32), base + (uint32_t)((s - 1) >> 2), step), make_uint2(k0, k1));
+    return ((s - 1) & 3) == 0 ? rnd.x : ((s - 1) & 3) == 1 ? rnd.y : ((s - 1) & 3) == 2 ? rnd.z : rnd.w;
+}
 
 // uniform random walk (torch_cluster / pyg-lib semantics for p = q = 1: a node without neighbours keeps the walk where it is).
 // Row r starts at batch[r % B] (`batch.repeat(walks_per_node)`); one thread per walk, one Philox call per 4 steps.
@@ -62,8 +72,7 @@ __global__ void k_n2v_walks(const int64_t* __restrict__ rowptr, const int32_t* _
     rw[r * wl] = cur;
     uint4 rnd = make_uint4(0, 0, 0, 0);
     for (int s = 1; s < wl; ++s) {
-        if (((s - 1) & 3) == 0) rnd = philox4x32(make_uint4((uint32_t)r, (uint32_t)(r >> 32), (uint32_t)((s - 1) >> 2), step), make_uint2(k0, k1));
-        const uint32_t u = ((s - 1) & 3) == 0 ? rnd.x : ((s - 1) & 3) == 1 ? rnd.y : ((s - 1) & 3) == 2 ? rnd.z : rnd.w;
+        const uint32_t u = n2v_draw(rnd, 0, r, s, k0, k1, step);
         const int64_t a = rowptr[cur], deg = rowptr[cur + 1] - a;
         if (deg > 0) cur = col[a + (int64_t)(((uint64_t)u * (uint64_t)deg) >> 32)];
         rw[r * wl + s] = cur;
@@ -77,8 +86,7 @@ __global__ void k_n2v_negs(const int64_t* __restrict__ batch, int64_t B, int64_t
     rw[r * wl] = batch[r % B];
     uint4 rnd = make_uint4(0, 0, 0, 0);
     for (int s = 1; s < wl; ++s) {
-        if (((s - 1) & 3) == 0) rnd = philox4x32(make_uint4((uint32_t)r, (uint32_t)(r >> 32), 0x4E454700u + (uint32_t)((s - 1) >> 2), step), make_uint2(k0, k1));
-        const uint32_t u = ((s - 1) & 3) == 0 ? rnd.x : ((s - 1) & 3) == 1 ? rnd.y : ((s - 1) & 3) == 2 ? rnd.z : rnd.w;
+        const uint32_t u = n2v_draw(rnd, N2V_NEG_BASE, r, s, k0, k1, step);
         rw[r * wl + s] = (int64_t)(((uint64_t)u * (uint64_t)num_nodes) >> 32);
     }
 }
@@ -92,8 +100,7 @@ __global__ void k_m2v_walks(const m2v_path mp, const int64_t* __restrict__ batch
     rw[r * wl] = mp.src_start[0] + cur;
     uint4 rnd = make_uint4(0, 0, 0, 0);
     for (int s = 1; s < wl; ++s) {
-        if (((s - 1) & 3) == 0) rnd = philox4x32(make_uint4((uint32_t)r, (uint32_t)(r >> 32), (uint32_t)((s - 1) >> 2), step), make_uint2(k0, k1));
-        const uint32_t u = ((s - 1) & 3) == 0 ? rnd.x : ((s - 1) & 3) == 1 ? rnd.y : ((s - 1) & 3) == 2 ? rnd.z : rnd.w;
+        const uint32_t u = n2v_draw(rnd, 0, r, s, k0, k1, step);
         const int hp = (s - 1) % mp.n_hops;
         if (cur >= 0) {
             const int64_t a = mp.rowptr[hp][cur], deg = mp.rowptr[hp][cur + 1] - a;
@@ -110,8 +117,7 @@ __global__ void k_m2v_negs(const m2v_path mp, const int64_t* __restrict__ batch,
     rw[r * wl] = mp.src_start[0] + batch[r % B];
     uint4 rnd = make_uint4(0, 0, 0, 0);
     for (int s = 1; s < wl; ++s) {
-        if (((s - 1) & 3) == 0) rnd = philox4x32(make_uint4((uint32_t)r, (uint32_t)(r >> 32), 0x4E454700u + (uint32_t)((s - 1) >> 2), step), make_uint2(k0, k1));
-        const uint32_t u = ((s - 1) & 3) == 0 ? rnd.x : ((s - 1) & 3) == 1 ? rnd.y : ((s - 1) & 3) == 2 ? rnd.z : rnd.w;
+        const uint32_t u = n2v_draw(rnd, N2V_NEG_BASE, r, s, k0, k1, step);
         const int hp = (s - 1) % mp.n_hops;
         rw[r * wl + s] = mp.dst_start[hp] + (int64_t)(((uint64_t)u * (uint64_t)mp.dst_count[hp]) >> 32);
     }
@@ -125,44 +131,14 @@ __global__ void k_n2v_windows(const int64_t* __restrict__ rw, int64_t n_walks, i
     out[t] = rw[r * wl + j + c];
 }
 
-// loss and gradient of one set of window rows; sign = +1 positive pairs, -1 negative pairs.  NV = d / 64 values per lane.
-template <int NV>
+// loss and gradient of one set of window rows; positive != 0: positive pairs, 0: negative pairs.  NV = d / 64 values per lane.  One wave per window row: every
+// term is one atomic row add on G (the rest row's per pair, the start row's once per window row).
+// DUMMY (a metapath handle's default): the same terms, but those that land on the `dummy` row (a rest row or a start row that is the dummy - every walk that met a
+// dead end names it from there on) do not go to G one atomic row add each: a wave keeps their sum in gd, the workgroup's four waves meet in LDS, and G[dummy]
+// takes one row add per workgroup that had such a term.  gd, any, the LDS array and the barrier exist only in that form; !DUMMY ignores `dummy`.
+template <int NV, bool DUMMY>
 __global__ __launch_bounds__(256) void k_n2v_pairs(const float* __restrict__ W, const int64_t* __restrict__ rows, int64_t n_rows, int ctx, int d,
-                                                   float inv_pairs, int positive, float* __restrict__ G, double* __restrict__ loss) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    float lsum = 0.f;
-    if (r < n_rows) {
-        const int64_t s = rows[r * ctx];
-        float hs[NV], gs[NV];
-#pragma unroll
-        for (int k = 0; k < NV; ++k) { hs[k] = W[s * d + lane + 64 * k]; gs[k] = 0.f; }
-        for (int c = 1; c < ctx; ++c) {
-            const int64_t v = rows[r * ctx + c];
-            float hv[NV], dot = 0.f;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) { hv[k] = W[v * d + lane + 64 * k]; dot += hs[k] * hv[k]; }
-            dot = wave_reduce_sum(dot);
-            const float sg = 1.f / (1.f + expf(-dot));
-            float coef;   // d loss / d dot
-            if (positive) { lsum -= logf(sg + 1e-15f); coef = -sg * (1.f - sg) / (sg + 1e-15f) * inv_pairs; }
-            else { lsum -= logf(1.f - sg + 1e-15f); coef = sg * (1.f - sg) / (1.f - sg + 1e-15f) * inv_pairs; }
-#pragma unroll
-            for (int k = 0; k < NV; ++k) { atomicAdd(G + v * d + lane + 64 * k, coef * hs[k]); gs[k] += coef * hv[k]; }
-        }
-#pragma unroll
-        for (int k = 0; k < NV; ++k) atomicAdd(G + s * d + lane + 64 * k, gs[k]);
-    }
-    if (lane == 0 && r < n_rows) atomicAdd(loss, (double)lsum * (double)inv_pairs);
-}
-
-// k_n2v_pairs for a metapath handle: the same terms, but those that land on the DUMMY row (a rest row or a start row that is the dummy - every walk that met a
-// dead end names it from there on) do not go to G one atomic row add each: a wave keeps their sum in registers, the workgroup's four waves meet in LDS, and
-// G[dummy] takes one row add per workgroup that had such a term.  Every other row goes the way k_n2v_pairs sends it.
-template <int NV>
-__global__ __launch_bounds__(256) void k_m2v_pairs(const float* __restrict__ W, const int64_t* __restrict__ rows, int64_t n_rows, int ctx, int d,
                                                    float inv_pairs, int positive, int64_t dummy, float* __restrict__ G, double* __restrict__ loss) {
-    __shared__ float sh[4][NV * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t r = (int64_t)blockIdx.x * 4 + wave;
     float lsum = 0.f, gd[NV];
@@ -184,7 +160,7 @@ __global__ __launch_bounds__(256) void k_m2v_pairs(const float* __restrict__ W, 
             float coef;   // d loss / d dot
             if (positive) { lsum -= logf(sg + 1e-15f); coef = -sg * (1.f - sg) / (sg + 1e-15f) * inv_pairs; }
             else { lsum -= logf(1.f - sg + 1e-15f); coef = sg * (1.f - sg) / (1.f - sg + 1e-15f) * inv_pairs; }
-            if (v == dummy) {
+            if (DUMMY && v == dummy) {
                 any = 1;
 #pragma unroll
                 for (int k = 0; k < NV; ++k) { gd[k] += coef * hs[k]; gs[k] += coef * hv[k]; }
@@ -193,7 +169,7 @@ __global__ __launch_bounds__(256) void k_m2v_pairs(const float* __restrict__ W, 
                 for (int k = 0; k < NV; ++k) { atomicAdd(G + v * d + lane + 64 * k, coef * hs[k]); gs[k] += coef * hv[k]; }
             }
         }
-        if (s == dummy) {
+        if (DUMMY && s == dummy) {
             any = 1;
 #pragma unroll
             for (int k = 0; k < NV; ++k) gd[k] += gs[k];
@@ -203,10 +179,13 @@ __global__ __launch_bounds__(256) void k_m2v_pairs(const float* __restrict__ W, 
         }
     }
     if (lane == 0 && r < n_rows) atomicAdd(loss, (double)lsum * (double)inv_pairs);
+    if constexpr (DUMMY) {
+        __shared__ float sh[4][NV * 64];
 #pragma unroll
-    for (int k = 0; k < NV; ++k) sh[wave][lane + 64 * k] = gd[k];
-    if (__syncthreads_or(any))          // every thread of the workgroup arrives here (no early return above)
-        for (int q = threadIdx.x; q < NV * 64; q += 256) atomicAdd(G + dummy * d + q, (sh[0][q] + sh[1][q]) + (sh[2][q] + sh[3][q]));
+        for (int k = 0; k < NV; ++k) sh[wave][lane + 64 * k] = gd[k];
+        if (__syncthreads_or(any))          // every thread of the workgroup arrives here (no early return above)
+            for (int q = threadIdx.x; q < NV * 64; q += 256) atomicAdd(G + dummy * d + q, (sh[0][q] + sh[1][q]) + (sh[2][q] + sh[3][q]));
+    }
 }
 
 // dense Adam that also clears the gradient for the next batch (one pass over the four buffers)
@@ -309,6 +288,34 @@ extern "C" void ntf_n2v_destroy(ntf_n2v* h) {
     delete h;
 }
 
+// what ntf_n2v_create and ntf_m2v_create share once their arguments are checked: the device, the handle over a table [n, d] and its stream, the caller's graph
+// (`graph(h, ok)` sets its fields and uploads its CSRs: it returns its first failed allocation's code and ands its copies into ok), the four tables and the loss
+// cell, the padded upload, the zeroing.  A failure leaves its text in g_n2v_create_error and frees what was made (ntf_n2v_destroy).
+// Any embedding size 1..256 (data.embedding.d is free in the reference): a device row is padded to a multiple of 64 floats (h->d, what the kernels see); the pad
+// columns of the table are zero and stay zero - their gradient is a multiple of another row's zero pad, and Adam leaves a zero parameter with zero moments where it is
+template <class Graph>
+static int n2v_create_on_device(int device, int64_t n, int32_t d, const float* init_weight, uint64_t seed, ntf_n2v** out, Graph&& graph) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_n2v_create_error = "no such HIP device (there is no CPU fallback)"; return NTF_EHIP; }
+    hipSetDevice(device);
+    ntf_n2v* h = new ntf_n2v();
+    h->device = device; h->n = n; h->d_user = d; h->d = (d + 63) / 64 * 64; h->seed = seed;
+    if (hipStreamCreate(&h->st) != hipSuccess) { g_n2v_create_error = "hipStreamCreate failed"; delete h; return NTF_EHIP; }
+    bool ok = true;
+    auto H = [&](hipError_t s) { ok = ok && s == hipSuccess; };
+    int rc = graph(h, ok);
+    auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
+    const int64_t np = n * h->d;
+    A(dev_alloc(h, &h->W, np)); A(dev_alloc(h, &h->G, np)); A(dev_alloc(h, &h->M1, np)); A(dev_alloc(h, &h->V2, np)); A(dev_alloc(h, &h->d_loss, 2));
+    if (rc != NTF_OK) { g_n2v_create_error = h->err; ntf_n2v_destroy(h); return rc; }
+    H(upload_padded(h->W, h->d, init_weight, d, n));
+    H(hipMemsetAsync(h->G, 0, np * 4, h->st)); H(hipMemsetAsync(h->M1, 0, np * 4, h->st)); H(hipMemsetAsync(h->V2, 0, np * 4, h->st));
+    H(hipStreamSynchronize(h->st));
+    if (!ok) { g_n2v_create_error = "device initialisation failed"; ntf_n2v_destroy(h); return NTF_EHIP; }
+    *out = h;
+    return NTF_OK;
+}
+
 extern "C" int ntf_n2v_create(int device, int64_t num_nodes, int32_t d, const int64_t* rowptr, const int32_t* col, const float* init_weight, uint64_t seed, ntf_n2v** out) {
     if (!out) { g_n2v_create_error = "out is NULL"; return NTF_EINVAL; }
     *out = nullptr;
@@ -316,31 +323,14 @@ extern "C" int ntf_n2v_create(int device, int64_t num_nodes, int32_t d, const in
     const int64_t nnz = rowptr[num_nodes];
     for (int64_t i = 0; i < num_nodes; ++i) if (rowptr[i + 1] < rowptr[i]) { g_n2v_create_error = "n2v: rowptr not monotone"; return NTF_EINVAL; }
     for (int64_t p = 0; p < nnz; ++p) if (col[p] < 0 || col[p] >= num_nodes) { g_n2v_create_error = "n2v: neighbour id out of range"; return NTF_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_n2v_create_error = "no such HIP device (there is no CPU fallback)"; return NTF_EHIP; }
-    hipSetDevice(device);
-    ntf_n2v* h = new ntf_n2v();
-    // any embedding size 1..256 (round 6; data.embedding.d is free in the reference): a device row is padded to a multiple of 64 floats (h->d, what the kernels see); the pad
-    // columns of the table are zero and stay zero - their gradient is a multiple of another row's zero pad, and Adam leaves a zero parameter with zero moments where it is
-    h->device = device; h->n = num_nodes; h->d_user = d; h->d = (d + 63) / 64 * 64; h->nnz = nnz; h->seed = seed;
-    const int du = d; d = h->d;
-    int rc = NTF_OK;
-    auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
-    if (hipStreamCreate(&h->st) != hipSuccess) { g_n2v_create_error = "hipStreamCreate failed"; delete h; return NTF_EHIP; }
-    const int64_t np = num_nodes * d;
-    A(dev_alloc(h, &h->rowptr, num_nodes + 1)); A(dev_alloc(h, &h->col, std::max<int64_t>(nnz, 1)));
-    A(dev_alloc(h, &h->W, np)); A(dev_alloc(h, &h->G, np)); A(dev_alloc(h, &h->M1, np)); A(dev_alloc(h, &h->V2, np)); A(dev_alloc(h, &h->d_loss, 2));
-    if (rc != NTF_OK) { g_n2v_create_error = h->err; ntf_n2v_destroy(h); return rc; }
-    bool ok = true;
-    auto H = [&](hipError_t s) { ok = ok && s == hipSuccess; };
-    H(hipMemcpy(h->rowptr, rowptr, (num_nodes + 1) * 8, hipMemcpyHostToDevice));
-    if (nnz) H(hipMemcpy(h->col, col, nnz * 4, hipMemcpyHostToDevice));
-    H(upload_padded(h->W, d, init_weight, du, num_nodes));
-    H(hipMemsetAsync(h->G, 0, np * 4, h->st)); H(hipMemsetAsync(h->M1, 0, np * 4, h->st)); H(hipMemsetAsync(h->V2, 0, np * 4, h->st));
-    H(hipStreamSynchronize(h->st));
-    if (!ok) { g_n2v_create_error = "device initialisation failed"; ntf_n2v_destroy(h); return NTF_EHIP; }
-    *out = h;
-    return NTF_OK;
+    return n2v_create_on_device(device, num_nodes, d, init_weight, seed, out, [&](ntf_n2v* h, bool& ok) {
+        h->nnz = nnz;
+        if (int r = dev_alloc(h, &h->rowptr, num_nodes + 1)) return r;
+        if (int r = dev_alloc(h, &h->col, std::max<int64_t>(nnz, 1))) return r;
+        ok = ok && hipMemcpy(h->rowptr, rowptr, (num_nodes + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
+        if (nnz) ok = ok && hipMemcpy(h->col, col, nnz * 4, hipMemcpyHostToDevice) == hipSuccess;
+        return (int)NTF_OK;
+    });
 }
 
 // metapath2vec: an ntf_n2v handle over [total + 1, d] that carries a metapath (include/opentf_amd.h); everything is checked on the host before anything is allocated
@@ -368,40 +358,24 @@ extern "C" int ntf_m2v_create(int device, int32_t n_types, const int64_t* type_c
         if (nnz[i] > 0 && !hop_col[i]) return bad("m2v: a hop with edges has no column array");
         for (int64_t p = 0; p < nnz[i]; ++p) if (hop_col[i][p] < 0 || hop_col[i][p] >= nd) return bad("m2v: neighbour id outside its destination type");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_n2v_create_error = "no such HIP device (there is no CPU fallback)"; return NTF_EHIP; }
-    hipSetDevice(device);
-    ntf_n2v* h = new ntf_n2v();
-    h->device = device; h->n = total + 1; h->d_user = d; h->d = (d + 63) / 64 * 64; h->seed = seed;   // rows padded as in ntf_n2v_create
-    h->m2v = true; h->cycle = hop_dst[n_hops - 1] == hop_src[0]; h->start_count = type_count[hop_src[0]];
-    h->mp.n_hops = n_hops; h->mp.total = total;
-    h->dummy_pairs = true;                                                  // 3.32 against 4.73 ms per batch at dblp shapes (profiles/m2v_bench.md); 0 keeps the plain k_n2v_pairs
-    if (const char* e = getenv("NTF_M2V_PAIRS")) h->dummy_pairs = atoi(e) != 0;
-    int rc = NTF_OK;
-    auto A = [&](int r) { if (rc == NTF_OK) rc = r; };
-    if (hipStreamCreate(&h->st) != hipSuccess) { g_n2v_create_error = "hipStreamCreate failed"; delete h; return NTF_EHIP; }
-    const int64_t np = h->n * h->d;
-    bool ok = true;
-    auto H = [&](hipError_t s) { ok = ok && s == hipSuccess; };
-    for (int i = 0; i < n_hops && rc == NTF_OK; ++i) {
-        const int64_t ns = type_count[hop_src[i]];
-        int64_t* rp = nullptr; int32_t* cl = nullptr;
-        A(dev_alloc(h, &rp, ns + 1)); h->hop_bufs.push_back(rp);
-        A(dev_alloc(h, &cl, std::max<int64_t>(nnz[i], 1))); h->hop_bufs.push_back(cl);
-        if (rc != NTF_OK) break;
-        H(hipMemcpy(rp, hop_rowptr[i], (ns + 1) * 8, hipMemcpyHostToDevice));
-        if (nnz[i]) H(hipMemcpy(cl, hop_col[i], nnz[i] * 4, hipMemcpyHostToDevice));
-        h->mp.rowptr[i] = rp; h->mp.col[i] = cl;
-        h->mp.src_start[i] = start[hop_src[i]]; h->mp.dst_start[i] = start[hop_dst[i]]; h->mp.dst_count[i] = type_count[hop_dst[i]];
-    }
-    A(dev_alloc(h, &h->W, np)); A(dev_alloc(h, &h->G, np)); A(dev_alloc(h, &h->M1, np)); A(dev_alloc(h, &h->V2, np)); A(dev_alloc(h, &h->d_loss, 2));
-    if (rc != NTF_OK) { g_n2v_create_error = h->err; ntf_n2v_destroy(h); return rc; }
-    H(upload_padded(h->W, h->d, init_weight, d, h->n));
-    H(hipMemsetAsync(h->G, 0, np * 4, h->st)); H(hipMemsetAsync(h->M1, 0, np * 4, h->st)); H(hipMemsetAsync(h->V2, 0, np * 4, h->st));
-    H(hipStreamSynchronize(h->st));
-    if (!ok) { g_n2v_create_error = "device initialisation failed"; ntf_n2v_destroy(h); return NTF_EHIP; }
-    *out = h;
-    return NTF_OK;
+    return n2v_create_on_device(device, total + 1, d, init_weight, seed, out, [&](ntf_n2v* h, bool& ok) {
+        h->m2v = true; h->cycle = hop_dst[n_hops - 1] == hop_src[0]; h->start_count = type_count[hop_src[0]];
+        h->mp.n_hops = n_hops; h->mp.total = total;
+        h->dummy_pairs = true;                                                  // 3.32 against 4.73 ms per batch at dblp shapes (profiles/m2v_bench.md); 0 keeps the plain form
+        if (const char* e = getenv("NTF_M2V_PAIRS")) h->dummy_pairs = atoi(e) != 0;
+        for (int i = 0; i < n_hops; ++i) {
+            const int64_t ns = type_count[hop_src[i]];
+            int64_t* rp = nullptr; int32_t* cl = nullptr;
+            int rc = dev_alloc(h, &rp, ns + 1); h->hop_bufs.push_back(rp);
+            if (rc == NTF_OK) { rc = dev_alloc(h, &cl, std::max<int64_t>(nnz[i], 1)); h->hop_bufs.push_back(cl); }
+            if (rc != NTF_OK) return rc;
+            ok = ok && hipMemcpy(rp, hop_rowptr[i], (ns + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
+            if (nnz[i]) ok = ok && hipMemcpy(cl, hop_col[i], nnz[i] * 4, hipMemcpyHostToDevice) == hipSuccess;
+            h->mp.rowptr[i] = rp; h->mp.col[i] = cl;
+            h->mp.src_start[i] = start[hop_src[i]]; h->mp.dst_start[i] = start[hop_dst[i]]; h->mp.dst_count[i] = type_count[hop_dst[i]];
+        }
+        return (int)NTF_OK;
+    });
 }
 
 static void n2v_key(const ntf_n2v* h, uint64_t step, int tensor, uint32_t& k0, uint32_t& k1) {
@@ -422,6 +396,19 @@ static int need_rows(ntf_n2v* h, int64_t elems) {
     h->win_p = h->win_n = nullptr; h->n_win_p = h->n_win_n = 0; h->win_ctx = 0;   // every writer of d_rows comes through here
     return dev_grow(h, &h->d_rows, &h->rows_cap, elems);
 }
+// the walks / the negative rows of call `step` from the staged batch of B start nodes into rw [n_rows, wl]: the typed kernel on a metapath handle, the untyped one otherwise
+static void launch_walks(ntf_n2v* h, int64_t B, int64_t n_rows, int wl, uint64_t step, int64_t* rw) {
+    uint32_t k0, k1; n2v_key(h, step, 0, k0, k1);
+    const dim3 grid((unsigned)((n_rows + 255) / 256)), block(256);
+    if (h->m2v) hipLaunchKernelGGL(k_m2v_walks, grid, block, 0, h->st, h->mp, h->d_batch, B, n_rows, wl, k0, k1, (uint32_t)step, rw);
+    else hipLaunchKernelGGL(k_n2v_walks, grid, block, 0, h->st, h->rowptr, h->col, h->d_batch, B, n_rows, wl, k0, k1, (uint32_t)step, rw);
+}
+static void launch_negs(ntf_n2v* h, int64_t B, int64_t n_rows, int wl, uint64_t step, int64_t* rw) {
+    uint32_t k0, k1; n2v_key(h, step, 1, k0, k1);
+    const dim3 grid((unsigned)((n_rows + 255) / 256)), block(256);
+    if (h->m2v) hipLaunchKernelGGL(k_m2v_negs, grid, block, 0, h->st, h->mp, h->d_batch, B, n_rows, wl, k0, k1, (uint32_t)step, rw);
+    else hipLaunchKernelGGL(k_n2v_negs, grid, block, 0, h->st, h->d_batch, B, n_rows, wl, h->n, k0, k1, (uint32_t)step, rw);
+}
 
 extern "C" int ntf_n2v_walks(ntf_n2v* h, const int64_t* start, int64_t n, int32_t walk_length, uint64_t step, int64_t* out_host) {
     if (!h || !start || n < 1 || walk_length < 1 || !out_host) return NTF_EINVAL;
@@ -429,9 +416,7 @@ extern "C" int ntf_n2v_walks(ntf_n2v* h, const int64_t* start, int64_t n, int32_
     if (m2v_too_long(h, walk_length)) FAIL(h, NTF_EINVAL, "m2v: a walk longer than the metapath needs a metapath that ends on its start type");
     int r = stage_batch(h, start, n); if (r) return r;
     if ((r = need_rows(h, n * walk_length))) return r;
-    uint32_t k0, k1; n2v_key(h, step, 0, k0, k1);
-    if (h->m2v) hipLaunchKernelGGL(k_m2v_walks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->mp, h->d_batch, n, n, walk_length, k0, k1, (uint32_t)step, h->d_rows);
-    else hipLaunchKernelGGL(k_n2v_walks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->rowptr, h->col, h->d_batch, n, n, walk_length, k0, k1, (uint32_t)step, h->d_rows);
+    launch_walks(h, n, n, walk_length, step, h->d_rows);
     HIPCHK(h, hipMemcpyAsync(out_host, h->d_rows, n * walk_length * 8, hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));
     return NTF_OK;
@@ -456,44 +441,44 @@ extern "C" int ntf_n2v_set_optimizer(ntf_n2v* h, int32_t kind) {
     return NTF_OK;
 }
 
-// the sparse step: marked rows -> list -> sparse_adam on the listed rows; the marks, the rows of G and the pending count are clear afterwards
-static void launch_sparse_adam(ntf_n2v* h, float lr) {
+// Adam's constants at step t >= 1 (torch's defaults), in f64: what both launches below round their float arguments from
+struct adam_consts { double b1, b2, bc1, bc2; float eps; };
+static adam_consts adam_at(int64_t t) {
     const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - std::pow(b1, (double)h->adam_t), bc2 = 1.0 - std::pow(b2, (double)h->adam_t);
-    const float step = (float)((double)lr * std::sqrt(bc2) / bc1);
+    return {b1, b2, 1.0 - std::pow(b1, (double)t), 1.0 - std::pow(b2, (double)t), 1e-8f};
+}
+// the dense step over the whole table; G is clear afterwards
+static void launch_dense_adam(ntf_n2v* h, float lr) {
+    const adam_consts c = adam_at(h->adam_t);
+    const int64_t np = h->n * h->d;
+    const int blocks = (int)std::min<int64_t>((np / 4 + 255) / 256, 256 * 8);
+    hipLaunchKernelGGL(k_n2v_adam, dim3(blocks), dim3(256), 0, h->st, h->W, h->G, h->M1, h->V2, np, lr / (float)c.bc1, (float)c.b1, (float)c.b2, c.eps, (float)std::sqrt(c.bc2));
+}
+// the sparse step: marked rows -> list -> sparse_adam on the listed rows; the marks and the rows of G are clear afterwards
+static void launch_sparse_adam(ntf_n2v* h, float lr) {
+    const adam_consts c = adam_at(h->adam_t);
+    const float step = (float)((double)lr * std::sqrt(c.bc2) / c.bc1);
     const int64_t words = (h->n + 31) / 32, cap = std::min<int64_t>(h->n, h->pend_entries);
     if (cap <= 0) return;
     hipMemsetAsync(h->d_count, 0, 8, h->st);
     hipLaunchKernelGGL(k_n2v_compact, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, h->st, h->d_touch, words, h->d_list, h->d_count);
     const dim3 grid((unsigned)std::min<int64_t>((cap + 3) / 4, 256 * 8)), block(256);
-    switch (h->d / 64) {
-        case 1: hipLaunchKernelGGL(k_n2v_adam_rows<1>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f); break;
-        case 2: hipLaunchKernelGGL(k_n2v_adam_rows<2>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f); break;
-        case 3: hipLaunchKernelGGL(k_n2v_adam_rows<3>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f); break;
-        default: hipLaunchKernelGGL(k_n2v_adam_rows<4>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step, (float)(1.0 - b1), (float)(1.0 - b2), 1e-8f); break;
-    }
+    with_nv(h->d / 64, [&](auto nv) {
+        hipLaunchKernelGGL(k_n2v_adam_rows<decltype(nv)::value>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step,
+                           (float)(1.0 - c.b1), (float)(1.0 - c.b2), c.eps);
+    });
 }
 
 static void launch_pairs(ntf_n2v* h, const int64_t* rows, int64_t n_rows, int ctx, int positive) {
     if (n_rows <= 0 || ctx < 2) return;
     const float inv = 1.f / (float)(n_rows * (ctx - 1));
     const dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
-    if (h->dummy_pairs) {
-        const int64_t dummy = h->mp.total;
-        switch (h->d / 64) {
-            case 1: hipLaunchKernelGGL(k_m2v_pairs<1>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss); break;
-            case 2: hipLaunchKernelGGL(k_m2v_pairs<2>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss); break;
-            case 3: hipLaunchKernelGGL(k_m2v_pairs<3>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss); break;
-            default: hipLaunchKernelGGL(k_m2v_pairs<4>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss); break;
-        }
-        return;
-    }
-    switch (h->d / 64) {
-        case 1: hipLaunchKernelGGL(k_n2v_pairs<1>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, h->G, h->d_loss); break;
-        case 2: hipLaunchKernelGGL(k_n2v_pairs<2>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, h->G, h->d_loss); break;
-        case 3: hipLaunchKernelGGL(k_n2v_pairs<3>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, h->G, h->d_loss); break;
-        default: hipLaunchKernelGGL(k_n2v_pairs<4>, grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, h->G, h->d_loss); break;
-    }
+    const int64_t dummy = h->mp.total;          // read by the dummy form alone
+    with_nv(h->d / 64, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        if (h->dummy_pairs) hipLaunchKernelGGL((k_n2v_pairs<NV, true>), grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss);
+        else hipLaunchKernelGGL((k_n2v_pairs<NV, false>), grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss);
+    });
 }
 
 extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, int32_t walk_length, int32_t context, int32_t walks_per_node, int32_t num_neg,
@@ -533,16 +518,11 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
         if ((r = need_rows(h, (pw + ng) * walk_length + (pw + ng) * nw * context))) return r;
         int64_t* rw_p = h->d_rows; int64_t* rw_n = rw_p + pw * walk_length;
         int64_t* win_p = rw_n + ng * walk_length; int64_t* win_n = win_p + pw * nw * context;
-        uint32_t k0, k1;
-        n2v_key(h, step, 0, k0, k1);
-        if (h->m2v) hipLaunchKernelGGL(k_m2v_walks, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, h->st, h->mp, h->d_batch, (int64_t)B, pw, walk_length, k0, k1, (uint32_t)step, rw_p);
-        else hipLaunchKernelGGL(k_n2v_walks, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, h->st, h->rowptr, h->col, h->d_batch, (int64_t)B, pw, walk_length, k0, k1, (uint32_t)step, rw_p);
+        launch_walks(h, B, pw, walk_length, step, rw_p);
         hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((pw * nw * context + 255) / 256)), dim3(256), 0, h->st, rw_p, pw, walk_length, context, win_p);
         launch_pairs(h, win_p, pw * nw, context, 1);
         if (ng) {
-            n2v_key(h, step, 1, k0, k1);
-            if (h->m2v) hipLaunchKernelGGL(k_m2v_negs, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, h->st, h->mp, h->d_batch, (int64_t)B, ng, walk_length, k0, k1, (uint32_t)step, rw_n);
-            else hipLaunchKernelGGL(k_n2v_negs, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, h->st, h->d_batch, (int64_t)B, ng, walk_length, h->n, k0, k1, (uint32_t)step, rw_n);
+            launch_negs(h, B, ng, walk_length, step, rw_n);
             hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((ng * nw * context + 255) / 256)), dim3(256), 0, h->st, rw_n, ng, walk_length, context, win_n);
             launch_pairs(h, win_n, ng * nw, context, 0);
         }
@@ -553,18 +533,10 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
     // sparse mode: the positive and the negative window rows lie back to back from win_p on, `entries` ids in all
     if (h->opt == 1 && entries > 0) hipLaunchKernelGGL(k_n2v_touch, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, h->st, h->win_p, entries,
                                                        h->m2v ? h->mp.total : (int64_t)-1, h->d_touch);
-    if (apply && h->opt == 1) {
+    if (apply) {
         h->adam_t += 1;
-        launch_sparse_adam(h, lr);
+        if (h->opt == 1) launch_sparse_adam(h, lr); else launch_dense_adam(h, lr);
         h->pend_entries = 0;
-    } else if (apply) {
-        h->adam_t += 1;
-        h->pend_entries = 0;
-        const double b1 = 0.9, b2 = 0.999;
-        const double bc1 = 1.0 - std::pow(b1, (double)h->adam_t), bc2 = 1.0 - std::pow(b2, (double)h->adam_t);
-        const int64_t np = h->n * h->d;
-        const int blocks = (int)std::min<int64_t>((np / 4 + 255) / 256, 256 * 8);
-        hipLaunchKernelGGL(k_n2v_adam, dim3(blocks), dim3(256), 0, h->st, h->W, h->G, h->M1, h->V2, np, lr / (float)bc1, (float)b1, (float)b2, 1e-8f, (float)std::sqrt(bc2));
     }
     if (loss_out) {
         double l = 0;

@@ -2,8 +2,8 @@
 member -> team -> skill -> team -> member, batches of 1000 start members with the reference's settings (w 5 / wl 5 steps = 6 nodes / wn 10 / ns 5), d = 128.
 The member edges of 15 % test teams and of one of three validation folds of the rest are dropped, as Gnn.learn drops them.
 
-  python profiles/m2v_time.py            the dummy share, the A/B of the two pair kernels in alternating rounds, an n2v batch on the same node count
-  python profiles/m2v_time.py kernels 0  a short run of one route (0 = k_n2v_pairs, 1 = k_m2v_pairs) for a kernel trace (rocprofv3 --kernel-trace --stats -- python ...)
+  python profiles/m2v_time.py            the dummy share, the A/B of the two forms of the pair kernel in alternating rounds, an n2v batch on the same node count
+  python profiles/m2v_time.py kernels 0  a short run of one route (0 = k_n2v_pairs<NV, false>, 1 = k_n2v_pairs<NV, true>, the dummy form) for a kernel trace (rocprofv3 --kernel-trace --stats -- python ...)
 Results: profiles/m2v_bench.md."""
 import os
 import sys
@@ -69,8 +69,8 @@ ms = [[], []]
 for r in range(rounds):
     for route in ((0, 1) if r % 2 == 0 else (1, 0)):
         ms[route].append(run(nets[route], k, 1 + r * k, M))
-    print(f"round {r}: k_n2v_pairs {ms[0][-1]:.3f} ms, k_m2v_pairs {ms[1][-1]:.3f} ms per batch", flush=True)
-for route, name in ((0, "k_n2v_pairs"), (1, "k_m2v_pairs")):
+    print(f"round {r}: pairs plain {ms[0][-1]:.3f} ms, pairs dummy {ms[1][-1]:.3f} ms per batch", flush=True)
+for route, name in ((0, "pairs plain (k_n2v_pairs<2, false>)"), (1, "pairs dummy (k_n2v_pairs<2, true>)")):
     a = np.array(ms[route])
     print(f"{name}: mean {a.mean():.3f} ms, median {np.median(a):.3f}, min {a.min():.3f}, max {a.max():.3f}, spread (max - min) {a.max() - a.min():.3f} over {rounds} rounds of {k} batches")
 for net in nets: net.close()

@@ -1,9 +1,9 @@
-"""metapath2vec producer on the MI355X (ntf_m2v_create, k_m2v_walks / k_m2v_negs / k_m2v_pairs in opentf_amd/csrc/ntf_n2v.hip) against tests/m2v_reference.py:
+"""metapath2vec producer on the MI355X (ntf_m2v_create, k_m2v_walks / k_m2v_negs / k_n2v_pairs<NV, DUMMY> in opentf_amd/csrc/ntf_n2v.hip) against tests/m2v_reference.py:
 typed walks and negatives replayed bit for bit from the Philox counters, native batches against the float64 reference of tests/test_gpu_n2v_parity.py inside its
 bars (dummy row included), Adam over applied native steps, every refusal of the contract, the `Gnn_m2v` plugin on toy dblp and a learning-signal check.
 
-The helpers (graph, metapaths, tables, replay) need no GPU.  Both pair kernels are run: NTF_M2V_PAIRS=0 sends a metapath handle's pairs through the plain
-k_n2v_pairs, 1 through k_m2v_pairs (the dummy row's terms summed per workgroup).
+The helpers (graph, metapaths, tables, replay) need no GPU.  Both forms of the pair kernel are run: NTF_M2V_PAIRS=0 sends a metapath handle's pairs through the
+plain k_n2v_pairs<NV, false>, 1 through k_n2v_pairs<NV, true> (the dummy row's terms summed per workgroup), at every NV = 1 .. 4 (d = 9, 65, 129, 256).
 
 Metapaths: member -> team -> member (2 hops), member -> team -> skill -> team -> member (4 hops), skill -> team -> member (2 hops, 3 node positions, NOT a
 cycle: it admits walks of at most 3 nodes, longer ones are refused - so its walk lengths are {2, 3}, the cycles' are {2, 5, 9}).
@@ -91,7 +91,7 @@ def table(name, d):
     return (W * (0.03 + 0.16 * torch.rand(n, 1, generator=gen)) * float(np.sqrt(128.0 / d))).float().numpy()
 
 
-NATIVE_SIZES = [9, 129]
+NATIVE_SIZES = [9, 65, 129, 256]
 # step -> (B, nodes per walk, context, walks per node, negatives): several windows per walk; one window per walk (the reference's shape); no negatives
 NATIVE_STEPS = ((16, 9, 4, 3, 2), (13, 5, 5, 2, 1), (16, 6, 3, 1, 0))
 # the Adam test's: few negatives, so that some rows are named in no step and others not in every step
@@ -193,7 +193,7 @@ def test_negatives_replay_bit_for_bit_in_window_row_order(name):
 @pytest.mark.parametrize("pairs", [0, 1])
 @pytest.mark.parametrize("d", NATIVE_SIZES)
 def test_native_batches_match_float64_with_the_dummy_row(d, pairs, monkeypatch):
-    """walks -> windows -> pairs, negatives -> windows -> pairs on a metapath handle, through either pair kernel: loss and every gradient element inside the
+    """walks -> windows -> pairs, negatives -> windows -> pairs on a metapath handle, through either form of the pair kernel: loss and every gradient element inside the
     bars of tests/test_gpu_n2v_parity.py.  The dummy row is named by a sizeable share of the pairs - a wrong aggregation of its terms shows on that row."""
     p = path(NATIVE_PATH)
     W = table(NATIVE_PATH, d)

@@ -2,7 +2,7 @@
 
 tests/test_gpu_n2v.py compares one injected batch on the 54-node toy graph with torch f32 autograd at 2e-5 of the LARGEST gradient.  Here: every
 gradient element against float64 inside a bar derived from the kernel's own roundings (`ref_pairs`); embedding sizes on both sides of every 64-lane
-boundary (1, 9, 65, 129, 192, 193, 256 - 129 and 192 are the only ones that run `k_n2v_pairs<3>`); the f32 saturation of the reference's
+boundary (1, 9, 65, 129, 192, 193, 256 - 129 and 192 are the only ones that run `k_n2v_pairs<3, false>`); the f32 saturation of the reference's
 `-log(1 - sigmoid(x) + 1e-15)`; what `Gnn.learn` really runs (walks -> windows -> pairs, negatives -> windows -> pairs) replayed from the Philox
 counters; Adam over steps in which a row is sometimes named and sometimes not; `ntf_n2v_edge_bce`; the refusals of the contract.
 
