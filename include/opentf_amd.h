@@ -332,7 +332,7 @@ int ntf_csr_result_fetch(ntf_csr_result* r, int64_t* indptr, int32_t* indices, u
 void ntf_csr_result_free(ntf_csr_result* r);
 
 /* ---- node2vec skill-embedding producer on the device                    src/mdl/emb/gnn.py:153-168 (model), 401-453 (_train_rw)
- * torch_geometric.nn.Node2Vec with p = q = 1 as the reference configures it (src/mdl/emb/__config__.yaml:58-70): uniform random walks over
+ * torch_geometric.nn.Node2Vec as the reference configures it (src/mdl/emb/__config__.yaml:58-70; p = q = 1 unless ntf_n2v_set_walk_bias says otherwise): uniform random walks over
  * a homogeneous CSR graph (rowptr [num_nodes+1] int64, col int32), windows of `context` nodes, negatives = start node + uniformly random
  * nodes, loss = -mean log(sigmoid(<start, rest>) + 1e-15) - mean log(1 - sigmoid(.) + 1e-15), dense Adam on embedding.weight [num_nodes, d]
  * (1 <= d <= 256: device rows are padded to a multiple of 64 floats, the pad stays zero; init_weight = the nn.Embedding initial draw, supplied by the host so that a seed reproduces torch's).
@@ -366,6 +366,31 @@ int  ntf_n2v_edge_bce(ntf_n2v* h, const int64_t* src, const int64_t* dst, int64_
  * ntf_n2v_moments: exp_avg and exp_avg_sq, [num_nodes, d] each without the pad columns, either pointer may be NULL; reads only, in both modes. */
 int  ntf_n2v_set_optimizer(ntf_n2v* h, int32_t kind /* 0 dense Adam, 1 sparse Adam */);
 int  ntf_n2v_moments(ntf_n2v* h, float* exp_avg /* [num_nodes, d] or NULL */, float* exp_avg_sq /* [num_nodes, d] or NULL */);
+/* node2vec's walk bias: the return parameter p and the in-out parameter q of torch_geometric.nn.Node2Vec (src/mdl/emb/__config__.yaml:69-70), i.e. torch_cluster's
+ * random_walk(rowptr, col, start, walk_length, p, q) as published, restated in tests/n2v_bias_reference.py (the package is not installed: that file is the pin).
+ * With p == 1 && q == 1 (the default) a handle walks uniformly: k_n2v_walks, its draw slots, its bits - whether the entry was never called, called with (1, 1), or
+ * set to something else in between.  With any other pair the walks of ntf_n2v_walks and the positive walks of ntf_n2v_train_batch are the biased walks below;
+ * negatives, windows, pairs, both optimisers, ntf_n2v_edge_bce and ntf_n2v_last_windows are untouched, and call t of a handle still draws what ntf_n2v_walks(step = t)
+ * draws.  Walks carry no state between calls: the entry may be called at any time and takes no step index.
+ * A walk stands on v and came from t (t == v at the start and after a stay).  deg(v) == 0: it stays.  deg(v) == 1: it takes the only neighbour.  Position 1: a
+ * uniform neighbour of v.  Later positions with deg(v) >= 2: x is drawn over the ENTRIES of v's CSR row (a repeated id counts once per entry) with probability
+ * proportional to 1 / p when x == t (class 0), 1 when t occurs in the CSR row of x (class 1; torch_cluster's is_neighbor(x, t) looks in the row of x), 1 / q otherwise
+ * (class 2).  torch_cluster rejects against max(1 / p, 1, 1 / q) without a bound on the attempts; the device rejects NTF_N2V_BIAS_TRIES times and then takes the
+ * step by an exact inverse-CDF scan of v's row over the same integer weights (the whole wave scans the row), so the mixture is the same distribution.
+ * The draws: thr[k] = (uint64) floor(prob_k * 4294967296.0), prob_0 = (1 / p) / mx, prob_1 = 1 / mx, prob_2 = (1 / q) / mx, mx = max(1 / p, 1, 1 / q), in IEEE
+ * double in that order of operations; thr lies in [1, 2^32].  Walk r of call `step` consumes 32-bit words w_0, w_1, ..: w_i is word i & 3 of Philox4x32-10(counter
+ * (r lo, r hi, NTF_N2V_BIAS_BASE + (i >> 2), (uint32) step), key n2v_key(seed, step, 0)).  Only steps that draw consume words (no slot per position, unlike the
+ * uniform walk).  deg(v) <= 1: no word.  Position 1, deg >= 2: one word u, x = col[a + ((u * deg) >> 32)].  Position >= 2, deg >= 2: per attempt two words u_c, u_a,
+ * candidate c = col[a + ((u_c * deg) >> 32)], accepted iff (uint64) u_a < thr[class(c, t)].  After NTF_N2V_BIAS_TRIES rejections two more words u_hi, u_lo (in
+ * that order), U = (u_hi << 32) | u_lo, total = sum over the row's entries of thr[class(col[a + j], t)] (< 2^63), target = (U * total) >> 64, x = col[a + j*] for
+ * the smallest j* whose inclusive prefix sum exceeds target.  NTF_N2V_BIAS_TRIES is a design constant, not a tolerance.
+ * Refused, changing nothing (the bias in force stays; the text is in ntf_n2v_last_error): NTF_EINVAL for a p or q that is not finite or lies outside [1e-4, 1e4]
+ * (the range keeps every thr >= 1); NTF_ESTATE on a metapath handle (MetaPath2Vec has no p / q); NTF_EINVAL when some CSR row's neighbour ids are not in ascending
+ * order (repeats allowed) - the search for t in the row of x is a binary search; the order is checked on the device once, the first time a pair other than (1, 1)
+ * is set, and a handle refused for it goes on working unbiased. */
+#define NTF_N2V_BIAS_TRIES 16
+#define NTF_N2V_BIAS_BASE  0x42494153u
+int  ntf_n2v_set_walk_bias(ntf_n2v* h, double p, double q);
 
 /* ---- metapath2vec skill-embedding producer on the device                                   src/mdl/emb/gnn.py (`m2v` branch of the Gnn plugin, trained by _train_rw)
  * torch_geometric.nn.MetaPath2Vec 2.6.1 as published (restated in tests/m2v_reference.py): after the walks it IS node2vec - the same windows, loss, dense Adam and

@@ -1,7 +1,7 @@
 // node2vec skill-embedding producer on the MI355X: the table E [S, d] that the team2vec gather (k_gather_pool) consumes.
 // Replaces the node2vec branch of the reference, src/mdl/emb/gnn.py:153-168 (torch_geometric.nn.Node2Vec, pinned 2.6.1 in requirements.txt:51,
 // not installed here: its published algorithm is restated in oracle/n2v_oracle.py) and its training loop _train_rw, gnn.py:401-453:
-//   loader  : per batch of start nodes, `walks_per_node` uniform random walks (p = q = 1) of `walk_length` nodes, cut into windows of
+//   loader  : per batch of start nodes, `walks_per_node` random walks (uniform at p = q = 1, else biased: ntf_n2v_set_walk_bias) of `walk_length` nodes, cut into windows of
 //             `context_size`; negatives = the same start nodes followed by uniformly random nodes
 //   loss    : -mean log(sigmoid(<e_start, e_rest>) + 1e-15) over positive pairs  - mean log(1 - sigmoid(.) + 1e-15) over negative pairs
 //   update  : torch.optim.Adam on the dense embedding matrix (every row moves every step through its moments); opt-in (ntf_n2v_set_optimizer) torch.optim.SparseAdam
@@ -48,6 +48,9 @@ struct ntf_n2v {
     bool m2v = false, cycle = false; m2v_path mp; int64_t start_count = 0;   // ntf_m2v_create: the metapath; rowptr / col above stay NULL, n = total + 1
     bool dummy_pairs = false;                                                // pairs through k_n2v_pairs<NV, true>: a metapath handle's default (NTF_M2V_PAIRS=0, read by ntf_m2v_create, turns it off)
     std::vector<void*> hop_bufs;                                           // the per-hop CSRs the metapath points into
+    // ntf_n2v_set_walk_bias: biased = some (p, q) other than (1, 1) is in force and the walks go through k_n2v_walks_biased with these thresholds;
+    // rows_ascending: -1 = not looked at yet, 0 / 1 = what k_n2v_rows_ascending found (asked once, the first time a bias is set)
+    bool biased = false; unsigned long long bias_thr[3] = {0, 0, 0}; int rows_ascending = -1;
     std::string err;
 };
 static thread_local std::string g_n2v_create_error;
@@ -62,7 +65,7 @@ __device__ __forceinline__ uint32_t n2v_draw(uint4& rnd, uint32_t base, int64_t 
     return ((s - 1) & 3) == 0 ? rnd.x : ((s - 1) & 3) == 1 ? rnd.y : ((s - 1) & 3) == 2 ? rnd.z : rnd.w;
 }
 
-// uniform random walk (torch_cluster / pyg-lib semantics for p = q = 1: a node without neighbours keeps the walk where it is).
+// uniform random walk, the walk of a handle whose bias is (1, 1) (torch_cluster / pyg-lib semantics: a node without neighbours keeps the walk where it is).
 // Row r starts at batch[r % B] (`batch.repeat(walks_per_node)`); one thread per walk, one Philox call per 4 steps.
 __global__ void k_n2v_walks(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int64_t* __restrict__ batch, int64_t B,
                             int64_t n_walks, int wl, uint32_t k0, uint32_t k1, uint32_t step, int64_t* __restrict__ rw) {
@@ -77,6 +80,107 @@ __global__ void k_n2v_walks(const int64_t* __restrict__ rowptr, const int32_t* _
         if (deg > 0) cur = col[a + (int64_t)(((uint64_t)u * (uint64_t)deg) >> 32)];
         rw[r * wl + s] = cur;
     }
+}
+// ---- biased (p, q) second-order walks: torch_cluster's random_walk(rowptr, col, start, walk_length, p, q) as include/opentf_amd.h pins it (ntf_n2v_set_walk_bias).
+// thr[k] = floor(prob_k * 2^32) of the classes 0: x == t (1 / p), 1: t is in the CSR row of x (1), 2: otherwise (1 / q), each over max(1 / p, 1, 1 / q)
+struct n2v_bias { unsigned long long thr[3]; };
+// class of candidate x for a walk that came from t: lower bound of t in the ascending row of x (repeats allowed), at most 31 probes of a row below 2^31 entries
+__device__ __forceinline__ int n2v_bias_class(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t x, int64_t t) {
+    if (x == t) return 0;
+    int64_t lo = rowptr[x]; const int64_t end = rowptr[x + 1]; int64_t hi = end;
+    while (lo < hi) { const int64_t mid = lo + ((hi - lo) >> 1); if ((int64_t)col[mid] < t) lo = mid + 1; else hi = mid; }
+    return lo < end && (int64_t)col[lo] == t ? 1 : 2;
+}
+// the class's threshold by selects: the three stay in scalar registers (an index into the by-value array would send it to scratch)
+__device__ __forceinline__ unsigned long long n2v_bias_thr(const n2v_bias& b, int k) { return k == 0 ? b.thr[0] : k == 1 ? b.thr[1] : b.thr[2]; }
+// word i of a walk's stream: word i & 3 of Philox4x32-10(counter (r lo, r hi, NTF_N2V_BIAS_BASE + (i >> 2), step), key); only steps that draw advance i
+__device__ __forceinline__ uint32_t n2v_bias_word(uint4& rnd, uint32_t& i, int64_t r, uint32_t k0, uint32_t k1, uint32_t step) {
+    if ((i & 3) == 0) rnd = philox4x32(make_uint4((uint32_t)r, (uint32_t)(r >> 32), NTF_N2V_BIAS_BASE + (i >> 2), step), make_uint2(k0, k1));
+    const uint32_t w = (i & 3) == 0 ? rnd.x : (i & 3) == 1 ? rnd.y : (i & 3) == 2 ? rnd.z : rnd.w;
+    ++i;
+    return w;
+}
+__device__ __forceinline__ unsigned long long wave_bcast_u64(unsigned long long v, int src) {
+    return ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src, 64);
+}
+__device__ __forceinline__ unsigned long long wave_shfl_up_u64(unsigned long long v, int o) {
+    return ((unsigned long long)(uint32_t)__shfl_up((int)(uint32_t)(v >> 32), o, 64) << 32) | (uint32_t)__shfl_up((int)(uint32_t)v, o, 64);
+}
+// One thread per walk, like k_n2v_walks.  A step of a walk on a node of degree >= 2, past position 1, is drawn in two stages.  Stage 1, per lane: up to
+// NTF_N2V_BIAS_TRIES rejection attempts (a candidate load and a binary search each).  Stage 2, for the lanes still undecided, one lane at a time with the WHOLE wave:
+// the exact inverse-CDF scan of the row over the same integer weights - 64 entries a stride, a 64-bit wave prefix sum carried across the strides, first the total,
+// then the crossing of target = (U * total) >> 64 - so a hub row of 1e5 entries costs 2 * ceil(deg / 64) strides, not one lane's 1e5 probes.  Stage 2 crosses lanes:
+// it sits outside every lane-dependent branch and loop, and a lane with r >= n_walks does not return - it stays as an idle participant (live = false).
+// Integer arithmetic throughout: the walk does not depend on how the scan is split over the lanes, and the host replay (tests/n2v_bias_reference.py) pins it.
+__global__ __launch_bounds__(256) void k_n2v_walks_biased(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int64_t* __restrict__ batch,
+                                                          int64_t B, int64_t n_walks, int wl, uint32_t k0, uint32_t k1, uint32_t step, const n2v_bias bias,
+                                                          int64_t* __restrict__ rw) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = r < n_walks;
+    int64_t cur = live ? batch[r % B] : 0, prev = cur;
+    if (live) rw[r * wl] = cur;
+    uint4 rnd = make_uint4(0, 0, 0, 0);
+    uint32_t nw = 0;                                        // words consumed so far
+    for (int s = 1; s < wl; ++s) {                          // wave-uniform trip count
+        int64_t a = 0, deg = 0, next = cur;
+        unsigned long long U = 0;
+        bool undecided = false;
+        if (live) {
+            a = rowptr[cur]; deg = rowptr[cur + 1] - a;
+            if (deg == 1) next = col[a];
+            else if (deg >= 2 && s == 1) next = col[a + (int64_t)(((uint64_t)n2v_bias_word(rnd, nw, r, k0, k1, step) * (uint64_t)deg) >> 32)];
+            else if (deg >= 2) {
+                undecided = true;
+                for (int k = 0; k < NTF_N2V_BIAS_TRIES && undecided; ++k) {
+                    const uint32_t uc = n2v_bias_word(rnd, nw, r, k0, k1, step), ua = n2v_bias_word(rnd, nw, r, k0, k1, step);
+                    const int64_t c = col[a + (int64_t)(((uint64_t)uc * (uint64_t)deg) >> 32)];
+                    if ((unsigned long long)ua < n2v_bias_thr(bias, n2v_bias_class(rowptr, col, c, prev))) { next = c; undecided = false; }
+                }
+                if (undecided) {
+                    const uint32_t uhi = n2v_bias_word(rnd, nw, r, k0, k1, step), ulo = n2v_bias_word(rnd, nw, r, k0, k1, step);
+                    U = ((unsigned long long)uhi << 32) | ulo;
+                }
+            }
+        }
+        // stage 2: every lane of the wave is here
+        for (unsigned long long pend = __ballot(undecided); pend; pend &= pend - 1) {
+            const int o = __ffsll(pend) - 1;
+            const int64_t oa = (int64_t)wave_bcast_u64((unsigned long long)a, o), odeg = (int64_t)wave_bcast_u64((unsigned long long)deg, o);
+            const int64_t ot = (int64_t)wave_bcast_u64((unsigned long long)prev, o);
+            const unsigned long long oU = wave_bcast_u64(U, o);
+            unsigned long long total = 0;                   // < 2^63: below 2^31 entries of at most 2^32 each
+            for (int64_t j = lane; j < odeg; j += 64) total += n2v_bias_thr(bias, n2v_bias_class(rowptr, col, col[oa + j], ot));
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) total += wave_bcast_u64(total, lane ^ m);
+            const unsigned long long target = __umul64hi(oU, total);      // < total: a crossing exists
+            unsigned long long carry = 0;
+            int64_t at = odeg - 1;
+            for (int64_t base = 0; base < odeg; base += 64) {             // wave-uniform trip count and exit
+                const int64_t j = base + lane;
+                unsigned long long incl = j < odeg ? n2v_bias_thr(bias, n2v_bias_class(rowptr, col, col[oa + j], ot)) : 0ull;
+#pragma unroll
+                for (int m = 1; m < 64; m <<= 1) { const unsigned long long up = wave_shfl_up_u64(incl, m); if (lane >= m) incl += up; }
+                incl += carry;
+                const unsigned long long hit = __ballot(j < odeg && incl > target);
+                if (hit) { at = base + (__ffsll(hit) - 1); break; }
+                carry = wave_bcast_u64(incl, 63);
+            }
+            const int64_t x = col[oa + at];
+            if (lane == o) next = x;
+        }
+        prev = cur; cur = next;
+        if (live) rw[r * wl + s] = cur;
+    }
+}
+// the ascending order the binary search of n2v_bias_class needs: one thread per CSR entry p >= 1, out of order when col[p] < col[p - 1] inside one row (p is
+// no row's first entry: lower bound of p in rowptr).  Run once per handle, the first time a bias is set.
+__global__ void k_n2v_rows_ascending(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t n, int64_t nnz, int* __restrict__ bad) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
+    if (p >= nnz || col[p] >= col[p - 1]) return;
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { const int64_t mid = lo + ((hi - lo) >> 1); if (rowptr[mid] < p) lo = mid + 1; else hi = mid; }
+    if (rowptr[lo] != p) *bad = 1;
 }
 // negative rows: start node followed by uniformly random nodes (`torch.randint(num_nodes, ...)`), start = batch[r % B]
 __global__ void k_n2v_negs(const int64_t* __restrict__ batch, int64_t B, int64_t n_rows, int wl, int64_t num_nodes, uint32_t k0, uint32_t k1, uint32_t step,
@@ -396,12 +500,16 @@ static int need_rows(ntf_n2v* h, int64_t elems) {
     h->win_p = h->win_n = nullptr; h->n_win_p = h->n_win_n = 0; h->win_ctx = 0;   // every writer of d_rows comes through here
     return dev_grow(h, &h->d_rows, &h->rows_cap, elems);
 }
-// the walks / the negative rows of call `step` from the staged batch of B start nodes into rw [n_rows, wl]: the typed kernel on a metapath handle, the untyped one otherwise
+// the walks / the negative rows of call `step` from the staged batch of B start nodes into rw [n_rows, wl]: the typed kernel on a metapath handle, the untyped one
+// otherwise - uniform, or biased while a (p, q) other than (1, 1) is in force
 static void launch_walks(ntf_n2v* h, int64_t B, int64_t n_rows, int wl, uint64_t step, int64_t* rw) {
     uint32_t k0, k1; n2v_key(h, step, 0, k0, k1);
     const dim3 grid((unsigned)((n_rows + 255) / 256)), block(256);
     if (h->m2v) hipLaunchKernelGGL(k_m2v_walks, grid, block, 0, h->st, h->mp, h->d_batch, B, n_rows, wl, k0, k1, (uint32_t)step, rw);
-    else hipLaunchKernelGGL(k_n2v_walks, grid, block, 0, h->st, h->rowptr, h->col, h->d_batch, B, n_rows, wl, k0, k1, (uint32_t)step, rw);
+    else if (h->biased) {
+        const n2v_bias bias = {{h->bias_thr[0], h->bias_thr[1], h->bias_thr[2]}};
+        hipLaunchKernelGGL(k_n2v_walks_biased, grid, block, 0, h->st, h->rowptr, h->col, h->d_batch, B, n_rows, wl, k0, k1, (uint32_t)step, bias, rw);
+    } else hipLaunchKernelGGL(k_n2v_walks, grid, block, 0, h->st, h->rowptr, h->col, h->d_batch, B, n_rows, wl, k0, k1, (uint32_t)step, rw);
 }
 static void launch_negs(ntf_n2v* h, int64_t B, int64_t n_rows, int wl, uint64_t step, int64_t* rw) {
     uint32_t k0, k1; n2v_key(h, step, 1, k0, k1);
@@ -438,6 +546,37 @@ extern "C" int ntf_n2v_set_optimizer(ntf_n2v* h, int32_t kind) {
         HIPCHK(h, hipStreamSynchronize(h->st));
     }
     h->opt = kind;
+    return NTF_OK;
+}
+
+// node2vec's return / in-out parameters.  (1, 1) is the uniform walk again (k_n2v_walks, its slots, its bits); any other pair sends the walks through
+// k_n2v_walks_biased.  Walks carry no state between calls, so the entry may come at any time and takes no step index.  A refused call changes nothing.
+extern "C" int ntf_n2v_set_walk_bias(ntf_n2v* h, double p, double q) {
+    if (!h) return NTF_EINVAL;
+    if (!std::isfinite(p) || !std::isfinite(q) || p < 1e-4 || p > 1e4 || q < 1e-4 || q > 1e4) FAIL(h, NTF_EINVAL, "n2v: walk bias p and q must be finite and in [1e-4, 1e4]");
+    if (h->m2v) FAIL(h, NTF_ESTATE, "m2v: a metapath handle takes no walk bias (MetaPath2Vec has no p / q)");
+    if (p == 1.0 && q == 1.0) { h->biased = false; return NTF_OK; }
+    if (h->rows_ascending < 0) {
+        HIPCHK(h, hipSetDevice(h->device));
+        int* d_bad = nullptr; int bad = 0;
+        if (int r = dev_alloc(h, &d_bad, 1)) return r;
+        hipError_t s = hipMemsetAsync(d_bad, 0, sizeof(int), h->st);
+        if (s == hipSuccess && h->nnz > 1) {
+            hipLaunchKernelGGL(k_n2v_rows_ascending, dim3((unsigned)((h->nnz - 1 + 255) / 256)), dim3(256), 0, h->st, h->rowptr, h->col, h->n, h->nnz, d_bad);
+            s = hipGetLastError();
+        }
+        if (s == hipSuccess) s = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, h->st);
+        if (s == hipSuccess) s = hipStreamSynchronize(h->st);
+        hipFree(d_bad);
+        if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("n2v: checking the order of the CSR rows: ") + hipGetErrorString(s));
+        h->rows_ascending = bad ? 0 : 1;
+    }
+    if (!h->rows_ascending) FAIL(h, NTF_EINVAL, "n2v: a walk bias needs every CSR row's neighbour ids in ascending order (repeats allowed); this graph has a row that is not");
+    // IEEE double, in this order of operations: a Python float computes the same bits (tests/n2v_bias_reference.py `thresholds`)
+    const double ip = 1.0 / p, iq = 1.0 / q, mx = std::max(ip, std::max(1.0, iq));
+    const double prob[3] = {ip / mx, 1.0 / mx, iq / mx};
+    for (int k = 0; k < 3; ++k) h->bias_thr[k] = (unsigned long long)std::floor(prob[k] * 4294967296.0);      // in [1, 2^32] over the accepted range
+    h->biased = true;
     return NTF_OK;
 }
 

@@ -118,6 +118,7 @@ SYMBOLS = {
     "ntf_n2v_edge_bce": (C.c_int, [_P, _P, _P, _I64, _P]),
     "ntf_n2v_set_optimizer": (C.c_int, [_P, _I32]),
     "ntf_n2v_moments": (C.c_int, [_P, _P, _P]),
+    "ntf_n2v_set_walk_bias": (C.c_int, [_P, C.c_double, C.c_double]),
     "ntf_m2v_create": (C.c_int, [C.c_int, _I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _U64, C.POINTER(_P)]),
     "ntf_d2v_create": (C.c_int, [C.c_int, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _U64, C.POINTER(_P)]),
     "ntf_d2v_destroy": (None, [_P]),
@@ -647,12 +648,13 @@ class Engine(_Handle):
 
 
 class Node2Vec(_Handle):
-    """torch_geometric.nn.Node2Vec (p = q = 1) resident on one MI355X: embedding.weight [num_nodes, d] + dense Adam, or with sparse=True torch.optim.SparseAdam
-    over the rows a batch names (include/opentf_amd.h, ntf_n2v_set_optimizer)."""
+    """torch_geometric.nn.Node2Vec resident on one MI355X: embedding.weight [num_nodes, d] + dense Adam, or with sparse=True torch.optim.SparseAdam
+    over the rows a batch names (include/opentf_amd.h, ntf_n2v_set_optimizer).  p, q: the return and in-out parameters of the walks (ntf_n2v_set_walk_bias);
+    (1, 1), the default, is the uniform walk."""
 
     _CREATE, _DESTROY, _LAST_ERROR, _TAG = "ntf_n2v_create", "ntf_n2v_destroy", "ntf_n2v_last_error", " n2v"
 
-    def __init__(self, rowptr, col, init_weight, seed=0, device=0, sparse=False):
+    def __init__(self, rowptr, col, init_weight, seed=0, device=0, sparse=False, p=1.0, q=1.0):
         self.rowptr = np.ascontiguousarray(rowptr, dtype=np.int64); self.col = np.ascontiguousarray(col, dtype=np.int32)
         w = _f32(init_weight)
         self.num_nodes, self.d = w.shape
@@ -660,7 +662,15 @@ class Node2Vec(_Handle):
             raise NtfError("rowptr must have num_nodes + 1 entries")
         self._create(int(device), self.num_nodes, self.d, _ptr(self.rowptr), _ptr(self.col), _ptr(w), int(seed) & (2**64 - 1))
         self.sparse = False
+        self.p, self.q = 1.0, 1.0
         if sparse: self.set_optimizer(True)
+        if float(p) != 1.0 or float(q) != 1.0: self.set_walk_bias(p, q)
+
+    def set_walk_bias(self, p, q):
+        """node2vec's p (return) and q (in-out), each in [1e-4, 1e4]; (1, 1) is the uniform walk again.  Any time: walks carry no state between calls.  Refused on a
+        metapath handle, and on a graph with a CSR row that is not ascending (the handle then goes on unbiased)"""
+        self._ck(lib().ntf_n2v_set_walk_bias(self._h, float(p), float(q)))
+        self.p, self.q = float(p), float(q)
 
     def set_optimizer(self, sparse):
         """dense Adam (False / 0) or sparse Adam (True / 1); refused once a step has been applied or while a gradient is pending"""

@@ -5,7 +5,7 @@
 What the caller (src/main.py:100-153) does and what it gets here:
   * `t2v = cls(output, acceleration, seed, cfg, method)`; `t2v.learn(teamsvecs, splits)`                       (main.py:112,122)
       per fold: the 'stm' graph (skill - team - member) without the member-team edges of the test and of that fold's validation teams
-      (gnn.py:84-116), `torch_geometric.nn.Node2Vec` (p = q = 1) trained by `_train_rw` (gnn.py:401-453: shuffled node batches, Adam,
+      (gnn.py:84-116), `torch_geometric.nn.Node2Vec` (its `p` / `q` read from the n2v section, absent = 1) trained by `_train_rw` (gnn.py:401-453: shuffled node batches, Adam,
       ReduceLROnPlateau on v_loss, EarlyStopping, `f{k}.pt` / `f{k}.e{e}.pt` checkpoints holding `embedding.weight`).  Here the walks,
       the skip-gram loss, its gradient and the dense Adam (or, with `sparse: true` in the method's section, sparse Adam) run in `opentf_amd/csrc/ntf_n2v.hip`; control flow, file names and
       checkpoint keys are the reference's.  An existing `f{k}.pt` is loaded instead, as gnn.py:402-405 does: one written by THIS plugin carries the node order its rows are
@@ -195,6 +195,12 @@ class Gnn(T2v):
         """the `sparse` key of the n2v / m2v section (Node2Vec / MetaPath2Vec(sparse=True) trained with torch.optim.SparseAdam); absent or false: dense Adam"""
         return bool(cfg_get(self._mcfg(), "sparse"))
 
+    def _bias(self):
+        """(p, q) of the n2v section (src/mdl/emb/__config__.yaml:69-70), absent = 1.0; m2v ignores the keys, as MetaPath2Vec has neither"""
+        if self.name != "n2v": return 1.0, 1.0
+        p, q = cfg_get(self._mcfg(), "p"), cfg_get(self._mcfg(), "q")
+        return (1.0 if p is None else float(p)), (1.0 if q is None else float(q))
+
     def _dirname(self):
         m, g = self._mcfg(), cfg_get(self.cfg, "graph")
         structure = cfg_get(g, "structure")
@@ -203,6 +209,8 @@ class Gnn(T2v):
         name += ".pre" if cfg_get(g, "pre") else ""
         name += f".w{cfg_get(m, 'w')}.wl{cfg_get(m, 'wl')}.wn{cfg_get(m, 'wn')}"
         name += f".{self.metapath_label}" if self.name == "m2v" and self.metapath_label else ""
+        p, q = self._bias()
+        name += f".p{float(p)}.q{float(q)}" if (p != 1.0 or q != 1.0) else ""      # default runs keep the reference's name; biased tables never share an f{k}.pt with them
         return name + (".sparse" if self._sparse() else "")      # the last part: tables of the two optimisers never share an f{k}.pt
 
     def learn(self, teamsvecs, splits=None, time_indexes=None):
@@ -235,7 +243,9 @@ class Gnn(T2v):
             self.offsets = off
             init = torch.nn.Embedding(n, d).weight.detach().numpy()       # the draw Node2Vec's / MetaPath2Vec's constructor makes (gnn.py:153-160): Embedding(count + 1, d) for m2v
             if self.name == "m2v": make_net = lambda: libntf.MetaPath2Vec(counts, hops, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse())
-            else: make_net = lambda: libntf.Node2Vec(rowptr, col, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse())
+            else:
+                p, q = self._bias()
+                make_net = lambda: libntf.Node2Vec(rowptr, col, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse(), p=p, q=q)
             path = f"{self.output}/f{foldidx}.pt"
             _barrier()                                                     # torchrun: nobody looks for the file while rank 0 may still be writing the previous one
             if not _rank0_says(os.path.exists(path)):                      # gnn.py:402-405: a trained table is loaded, not retrained (rank 0 decides for the job)
