@@ -366,6 +366,26 @@ int  ntf_n2v_edge_bce(ntf_n2v* h, const int64_t* src, const int64_t* dst, int64_
  * ntf_n2v_moments: exp_avg and exp_avg_sq, [num_nodes, d] each without the pad columns, either pointer may be NULL; reads only, in both modes. */
 int  ntf_n2v_set_optimizer(ntf_n2v* h, int32_t kind /* 0 dense Adam, 1 sparse Adam */);
 int  ntf_n2v_moments(ntf_n2v* h, float* exp_avg /* [num_nodes, d] or NULL */, float* exp_avg_sq /* [num_nodes, d] or NULL */);
+/* Lazy dense Adam: the table, the moments and the held-out loss of kind 0 above - bit for bit, given bit-identical gradients - while an applied step writes only
+ * the rows its windows name.  It is a mode of the DENSE optimiser (kind stays 0), not a third optimiser: under dense Adam a row whose gradient is zero in step t
+ * still moves,  m = b1 m;  v = b2 v;  p -= lr_t / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps),  from nothing but its own p, m, v and the step's two constants.
+ * A lazy handle leaves such a row where it is, keeps the steps applied to every row (`applied[row]` <= steps) and the constants of the last `window` steps in a ring,
+ * and brings a row up to date - the skipped steps, in order, each with its own constants, with the dense kernel's operations - before anything reads it:
+ *   ntf_n2v_train_batch  the rows the call's windows name (with those of pending apply = 0 calls), before its pairs; an applied step then runs on exactly those rows.
+ *                        When `window` steps have been applied since every row was last current, one full flush (every row to the present step) comes first
+ *   ntf_n2v_get(what = 0), ntf_n2v_moments   a full flush first: what they return is dense Adam's
+ *   ntf_n2v_edge_bce     the endpoints' rows alone when no gradient is pending; a full flush while one is (the pending rows' marks are left alone)
+ *   ntf_n2v_get(what = 1), ntf_n2v_walks, ntf_n2v_last_windows   read no table row: nothing is brought up to date
+ * A row whose moments are all +0 is unchanged by a zero-gradient step and is not rewritten; a full flush leaves its `applied` where it was (a row no window or
+ * edge ever named stays at 0).  Works on both handle kinds (the dummy row of a metapath handle is a row like any other) and with both forms of the pair kernel.
+ * ntf_n2v_set_lazy: window 0 = off (plain dense Adam, the default), window >= 1 = on with a ring of that many steps (a full flush every `window` applied steps at
+ * the latest; 8 bytes a step).  NTF_EINVAL: window < 0.  NTF_ESTATE: a sparse handle (kind 1), an applied step has been taken, or a gradient is pending -
+ * ntf_n2v_set_optimizer's rule; and ntf_n2v_set_optimizer(h, 1) on a lazy handle is NTF_ESTATE.  A refused call changes nothing.  On a lazy handle an applied
+ * ntf_n2v_train_batch whose step count would no longer fit the per-row uint32 is refused with NTF_ESTATE.
+ * ntf_n2v_lazy_state: reads only and flushes NOTHING: applied [num_nodes] (may be NULL) as the device holds it, *steps = applied steps of the handle, *flushes =
+ * full flushes so far (either may be NULL).  NTF_ESTATE on a handle that is not lazy.  It exists so that a test can see rows really being left behind. */
+int  ntf_n2v_set_lazy(ntf_n2v* h, int32_t window /* 0 off, >= 1 ring of that many steps */);
+int  ntf_n2v_lazy_state(ntf_n2v* h, uint32_t* applied /* [num_nodes] or NULL */, int64_t* steps, int64_t* flushes);
 /* node2vec's walk bias: the return parameter p and the in-out parameter q of torch_geometric.nn.Node2Vec (src/mdl/emb/__config__.yaml:69-70), i.e. torch_cluster's
  * random_walk(rowptr, col, start, walk_length, p, q) as published, restated in tests/n2v_bias_reference.py (the package is not installed: that file is the pin).
  * With p == 1 && q == 1 (the default) a handle walks uniformly: k_n2v_walks, its draw slots, its bits - whether the entry was never called, called with (1, 1), or

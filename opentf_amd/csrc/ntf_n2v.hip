@@ -6,11 +6,13 @@
 //   loss    : -mean log(sigmoid(<e_start, e_rest>) + 1e-15) over positive pairs  - mean log(1 - sigmoid(.) + 1e-15) over negative pairs
 //   update  : torch.optim.Adam on the dense embedding matrix (every row moves every step through its moments); opt-in (ntf_n2v_set_optimizer) torch.optim.SparseAdam
 //             over the rows the batch names: k_n2v_touch -> k_n2v_compact -> k_n2v_adam_rows
+//             opt-in too (ntf_n2v_set_lazy) LAZY dense Adam: dense Adam's table bit for bit, only the rows a batch names written - k_n2v_touch -> k_n2v_compact_keep ->
+//             k_n2v_catchup_rows before the pairs, k_n2v_catchup_rows<NV, true> after them, k_n2v_catchup_all where a reader wants the whole table
 // One wave per window row: the start row lives in registers (d / 64 values per lane), every rest row costs one coalesced row read, a wave
 // reduction and one coalesced f32 atomic row add (the forms that run at full rate on gfx950: 256 contiguous bytes per wave-instruction).
 // metapath2vec (torch_geometric.nn.MetaPath2Vec, the `m2v` method of the same plugin) is node2vec after the walks: ntf_m2v_create makes an ntf_n2v handle that carries a
 // metapath over per-hop CSRs.  Its own kernels are k_m2v_walks / k_m2v_negs (typed walks and negatives; the draws are n2v_draw's, as k_n2v_walks' / k_n2v_negs'); every
-// other kernel serves both handle kinds: k_n2v_windows, k_n2v_adam, the three of sparse Adam, k_n2v_edge_bce, and the one pair kernel k_n2v_pairs<NV, DUMMY> - its
+// other kernel serves both handle kinds: k_n2v_windows, k_n2v_adam, the three of sparse Adam, those of lazy dense Adam, k_n2v_edge_bce, and the one pair kernel k_n2v_pairs<NV, DUMMY> - its
 // plain form is node2vec's, its DUMMY form (a metapath handle's default) sums the dummy row's terms per workgroup.
 #include "../../include/opentf_amd.h"
 #include "ntf_device.h"
@@ -51,6 +53,10 @@ struct ntf_n2v {
     // ntf_n2v_set_walk_bias: biased = some (p, q) other than (1, 1) is in force and the walks go through k_n2v_walks_biased with these thresholds;
     // rows_ascending: -1 = not looked at yet, 0 / 1 = what k_n2v_rows_ascending found (asked once, the first time a bias is set)
     bool biased = false; unsigned long long bias_thr[3] = {0, 0, 0}; int rows_ascending = -1;
+    // ntf_n2v_set_lazy: lazy_window > 0 = dense Adam that writes only the rows a batch names (opt stays 0).  d_applied [n]: the Adam steps applied to each row
+    // (<= adam_t); d_ring [lazy_window]: slot s % lazy_window holds (lr / bc1, sqrt(bc2)) of step s, for the steps lazy_base + 1 .. adam_t - every row is at
+    // lazy_base or later; lazy_flushes: full flushes (k_n2v_catchup_all) so far.  d_touch / d_list / d_count are the sparse route's
+    int lazy_window = 0; uint32_t* d_applied = nullptr; float2* d_ring = nullptr; int64_t lazy_base = 0, lazy_flushes = 0;
     std::string err;
 };
 static thread_local std::string g_n2v_create_error;
@@ -327,11 +333,12 @@ __global__ __launch_bounds__(256) void k_n2v_touch(const int64_t* __restrict__ r
 }
 // the marked rows as a list: one thread per bitmap word, a wave takes ONE slot range from the counter (inclusive scan of the popcounts, the last lane asks), every
 // lane writes the ids of its word behind those of the lanes before it and clears the word.  The order of the waves' ranges is not fixed; each row is listed once.
-__global__ __launch_bounds__(256) void k_n2v_compact(uint32_t* __restrict__ bits, int64_t n_words, int64_t* __restrict__ list, unsigned long long* __restrict__ count) {
+template <bool CLEAR>
+__device__ __forceinline__ void n2v_compact(uint32_t* __restrict__ bits, int64_t n_words, int64_t* __restrict__ list, unsigned long long* __restrict__ count) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t word = w < n_words ? bits[w] : 0u;            // no early return: every lane takes part in the shuffles
-    if (word) bits[w] = 0u;
+    if (CLEAR && word) bits[w] = 0u;
     const int c = __popc(word);
     int incl = c;
 #pragma unroll
@@ -343,6 +350,13 @@ __global__ __launch_bounds__(256) void k_n2v_compact(uint32_t* __restrict__ bits
     const uint32_t lo = __shfl((uint32_t)base, 63, 64), hi = __shfl((uint32_t)(base >> 32), 63, 64);
     int64_t at = (int64_t)(((unsigned long long)hi << 32) | lo) + (incl - c);
     while (word) { list[at++] = w * 32 + (__ffs(word) - 1); word &= word - 1; }
+}
+__global__ __launch_bounds__(256) void k_n2v_compact(uint32_t* __restrict__ bits, int64_t n_words, int64_t* __restrict__ list, unsigned long long* __restrict__ count) {
+    n2v_compact<true>(bits, n_words, list, count);
+}
+// the same list with the marks left standing (lazy dense Adam lists the rows BEFORE the pairs and keeps the marks of a gradient that stays pending)
+__global__ __launch_bounds__(256) void k_n2v_compact_keep(uint32_t* __restrict__ bits, int64_t n_words, int64_t* __restrict__ list, unsigned long long* __restrict__ count) {
+    n2v_compact<false>(bits, n_words, list, count);
 }
 // torch.optim._functional.sparse_adam on the listed rows, one wave per row (NV = d / 64 values per lane), and the row of G cleared for the next batch.
 // step = lr sqrt(1 - b2^t) / (1 - b1^t); omb1 = 1 - b1, omb2 = 1 - b2 (rounded once, on the host); eps is added to sqrt(v) itself - not k_n2v_adam's placement.
@@ -368,6 +382,83 @@ __global__ __launch_bounds__(256) void k_n2v_adam_rows(float* __restrict__ p, fl
     }
 }
 
+// ---- lazy dense Adam (ntf_n2v_set_lazy): k_n2v_adam's table, bit for bit, with only the rows a batch names written.  A row whose gradient is zero in step t
+// takes k_n2v_adam's update with g = 0 (n2v_adam_elem) from nothing but its own p, m, v and the step's two constants, so a row left behind at step `applied[row]` is brought to `upto` by
+// running the steps applied + 1 .. upto in order, in registers, each with its own ring entry (wave-uniform).  There is no closed form (eps, the bias corrections,
+// a changing lr) and no early exit: 0.9 * min_denormal rounds back to min_denormal, a moment never reaches zero.  The one shortcut: a row whose m and v are all
+// +0 bits is unchanged by such a step and is not loaded further.  One wave per row, NV = d / 64 values per lane.
+// one element of k_n2v_adam's step for the lazy kernels below.  Sharing one inline function with k_n2v_adam was tried and MOVED that kernel: inside the function the
+// compiler contracted m as fma(1 - b1, g, b1 m) where k_n2v_adam has fma(b1, m, (1 - b1) g) - another rounding (profiles/n2v_lazy_check.md).  So k_n2v_adam
+// keeps its text, and this copy spells out, with contraction off, the operations that kernel's code performs: the products (1 - b1) g, (1 - b2) g and b2 v are
+// rounded, the three sums are fused.  sqrtf and both divisions are correctly rounded in either.  tests/test_gpu_n2v_lazy.py holds the two together bit for bit.
+__device__ __forceinline__ void n2v_adam_elem(float& p, float& m, float& v, float g, float lr_over_bc1, float b1, float b2, float eps, float bc2_sqrt) {
+#pragma clang fp contract(off)
+    const float mg = (1.f - b1) * g, vg = (1.f - b2) * g, vb = b2 * v;
+    m = __builtin_fmaf(b1, m, mg);
+    v = __builtin_fmaf(g, vg, vb);
+    p = __builtin_fmaf(-lr_over_bc1, m / (sqrtf(v) / bc2_sqrt + eps), p);
+}
+// one row, by its wave: the zero-gradient steps applied[row] + 1 .. upto, each with its ring entry.
+//   GRAD: after the catch-up the row takes step upto + 1 with its row of G (constants lr_over_bc1 / bc2_sqrt, the kernel's own), the row of G is cleared and
+//         applied = upto + 1
+//   ALL : a row without moments keeps its `applied` (k_n2v_catchup_all leaves the rows nothing ever named at 0); otherwise applied = upto
+template <int NV, bool GRAD, bool ALL>
+__device__ __forceinline__ void n2v_catchup(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, uint32_t* __restrict__ applied,
+                                            const float2* __restrict__ ring, uint32_t window, int64_t row, int d, int lane, uint32_t upto, float lr_over_bc1,
+                                            float b1, float b2, float eps, float bc2_sqrt) {
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)applied[row]);
+    if (!GRAD && a >= upto) return;                          // current: nothing but `applied` was read
+    const int64_t o = row * d + lane;
+    float pp[NV], mm[NV], vv[NV];
+    bool nz = false;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) { mm[k] = m[o + 64 * k]; vv[k] = v[o + 64 * k]; nz = nz || (__float_as_uint(mm[k]) | __float_as_uint(vv[k])) != 0u; }
+    const bool run = a < upto && __ballot(nz) != 0ull;        // wave-uniform
+    if (GRAD || run) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) pp[k] = p[o + 64 * k];
+    }
+    if (run) {
+        uint32_t slot = (a + 1u) % window;
+        for (uint32_t s = a; s < upto; ++s) {
+            const float2 c = ring[slot];
+            slot = slot + 1u == window ? 0u : slot + 1u;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) n2v_adam_elem(pp[k], mm[k], vv[k], 0.f, c.x, b1, b2, eps, c.y);
+        }
+    }
+    if (GRAD) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) { n2v_adam_elem(pp[k], mm[k], vv[k], g[o + 64 * k], lr_over_bc1, b1, b2, eps, bc2_sqrt); g[o + 64 * k] = 0.f; }
+    }
+    if (GRAD || run) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) { p[o + 64 * k] = pp[k]; m[o + 64 * k] = mm[k]; v[o + 64 * k] = vv[k]; }
+    }
+    if (lane == 0 && (GRAD || run || !ALL)) applied[row] = GRAD ? upto + 1u : upto;
+}
+// the listed rows (k_n2v_compact / k_n2v_compact_keep; the grid strides over the count left on the device, as k_n2v_adam_rows does).  GRAD: the step of the batch
+// itself; its first lane also files the step's constants in the ring (`ring_slot` = the slot of step upto + 1, which no catch-up of this launch reads: they stop at upto)
+template <int NV, bool GRAD>
+__global__ __launch_bounds__(256) void k_n2v_catchup_rows(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                          uint32_t* __restrict__ applied, const float2* __restrict__ ring, float2* ring_slot, uint32_t window,
+                                                          const int64_t* __restrict__ list, const unsigned long long* __restrict__ count, int d, uint32_t upto,
+                                                          float lr_over_bc1, float b1, float b2, float eps, float bc2_sqrt) {
+    const int lane = threadIdx.x & 63;
+    if (GRAD && blockIdx.x == 0 && threadIdx.x == 0) *ring_slot = make_float2(lr_over_bc1, bc2_sqrt);
+    const int64_t n = (int64_t)*count;
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += (int64_t)gridDim.x * 4)
+        n2v_catchup<NV, GRAD, false>(p, g, m, v, applied, ring, window, list[i], d, lane, upto, lr_over_bc1, b1, b2, eps, bc2_sqrt);
+}
+// every row (the full flush): a row that is current costs the read of its `applied`
+template <int NV>
+__global__ __launch_bounds__(256) void k_n2v_catchup_all(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, uint32_t* __restrict__ applied,
+                                                         const float2* __restrict__ ring, uint32_t window, int64_t n, int d, uint32_t upto, float b1, float b2, float eps) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (int64_t)gridDim.x * 4)
+        n2v_catchup<NV, false, true>(p, nullptr, m, v, applied, ring, window, row, d, lane, upto, 0.f, b1, b2, eps, 0.f);
+}
+
 // v_loss of _train_rw (gnn.py:420-431): mean BCE-with-logits of the held-out edges' scores against 1 = mean softplus(-score)
 __global__ __launch_bounds__(256) void k_n2v_edge_bce(const float* __restrict__ W, const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int64_t n, int d,
                                                       double* __restrict__ out) {
@@ -385,7 +476,7 @@ extern "C" void ntf_n2v_destroy(ntf_n2v* h) {
     hipSetDevice(h->device);
     if (h->st) hipStreamSynchronize(h->st);
     for (void* p : {(void*)h->rowptr, (void*)h->col, (void*)h->W, (void*)h->G, (void*)h->M1, (void*)h->V2, (void*)h->d_batch, (void*)h->d_rows, (void*)h->d_loss,
-                    (void*)h->d_touch, (void*)h->d_list, (void*)h->d_count})
+                    (void*)h->d_touch, (void*)h->d_list, (void*)h->d_count, (void*)h->d_applied, (void*)h->d_ring})
         if (p) hipFree(p);
     for (void* p : h->hop_bufs) if (p) hipFree(p);
     if (h->st) hipStreamDestroy(h->st);
@@ -534,6 +625,7 @@ extern "C" int ntf_n2v_set_optimizer(ntf_n2v* h, int32_t kind) {
     if (!h) return NTF_EINVAL;
     if (kind != 0 && kind != 1) FAIL(h, NTF_EINVAL, "n2v: optimizer kind must be 0 (dense Adam) or 1 (sparse Adam)");
     if (h->adam_t > 0 || h->pend_entries > 0) FAIL(h, NTF_ESTATE, "n2v: the optimizer is chosen before the first step and with no gradient pending");
+    if (kind == 1 && h->lazy_window) FAIL(h, NTF_ESTATE, "n2v: a lazy dense handle takes no sparse Adam (ntf_n2v_set_lazy(h, 0) first)");
     if (kind == 1 && !h->d_touch) {
         HIPCHK(h, hipSetDevice(h->device));
         const int64_t words = (h->n + 31) / 32;
@@ -546,6 +638,51 @@ extern "C" int ntf_n2v_set_optimizer(ntf_n2v* h, int32_t kind) {
         HIPCHK(h, hipStreamSynchronize(h->st));
     }
     h->opt = kind;
+    return NTF_OK;
+}
+
+// lazy dense Adam on or off (include/opentf_amd.h).  Everything is allocated before anything of the handle changes: a refused call changes nothing
+extern "C" int ntf_n2v_set_lazy(ntf_n2v* h, int32_t window) {
+    if (!h) return NTF_EINVAL;
+    if (window < 0) FAIL(h, NTF_EINVAL, "n2v: the lazy window is 0 (off) or a number of steps >= 1");
+    if (h->opt == 1) FAIL(h, NTF_ESTATE, "n2v: lazy dense Adam is a mode of the dense optimizer; this handle runs sparse Adam");
+    if (h->adam_t > 0 || h->pend_entries > 0) FAIL(h, NTF_ESTATE, "n2v: the lazy mode is chosen before the first step and with no gradient pending");
+    if (window == 0 || window == h->lazy_window) { h->lazy_window = window; return NTF_OK; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t words = (h->n + 31) / 32;
+    uint32_t *bits = nullptr, *applied = nullptr; unsigned long long* cnt = nullptr; float2* ring = nullptr;
+    int r = dev_alloc(h, &ring, window);
+    if (!r && !h->d_applied) r = dev_alloc(h, &applied, h->n);
+    if (!r && !h->d_touch) { r = dev_alloc(h, &bits, words); if (!r) r = dev_alloc(h, &cnt, 1); }
+    hipError_t s = hipSuccess;
+    if (!r) {
+        if (applied) s = hipMemsetAsync(applied, 0, (size_t)h->n * 4, h->st);
+        if (s == hipSuccess && bits) s = hipMemsetAsync(bits, 0, (size_t)words * 4, h->st);
+        if (s == hipSuccess && cnt) s = hipMemsetAsync(cnt, 0, 8, h->st);
+        if (s == hipSuccess) s = hipStreamSynchronize(h->st);
+    }
+    if (r || s != hipSuccess) {
+        for (void* q : {(void*)ring, (void*)applied, (void*)bits, (void*)cnt}) if (q) hipFree(q);
+        if (r) return r;
+        FAIL(h, NTF_EHIP, std::string("n2v: clearing the lazy state: ") + hipGetErrorString(s));
+    }
+    if (h->d_ring) hipFree(h->d_ring);
+    h->d_ring = ring;
+    if (applied) h->d_applied = applied;
+    if (bits) { h->d_touch = bits; h->d_count = cnt; }
+    h->lazy_window = window; h->lazy_base = 0;
+    return NTF_OK;
+}
+extern "C" int ntf_n2v_lazy_state(ntf_n2v* h, uint32_t* applied, int64_t* steps, int64_t* flushes) {
+    if (!h) return NTF_EINVAL;
+    if (!h->lazy_window) FAIL(h, NTF_ESTATE, "n2v: not a lazy handle (ntf_n2v_set_lazy)");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (applied) {
+        HIPCHK(h, hipMemcpyAsync(applied, h->d_applied, (size_t)h->n * 4, hipMemcpyDeviceToHost, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
+    }
+    if (steps) *steps = h->adam_t;
+    if (flushes) *flushes = h->lazy_flushes;
     return NTF_OK;
 }
 
@@ -608,6 +745,46 @@ static void launch_sparse_adam(ntf_n2v* h, float lr) {
     });
 }
 
+// ---- lazy dense Adam, host side.  The marked rows as a list of at most `cap` rows (the caller has grown d_list to that); keep: the marks stay
+static void lazy_list(ntf_n2v* h, bool keep) {
+    const int64_t words = (h->n + 31) / 32;
+    hipMemsetAsync(h->d_count, 0, 8, h->st);
+    if (keep) hipLaunchKernelGGL(k_n2v_compact_keep, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, h->st, h->d_touch, words, h->d_list, h->d_count);
+    else hipLaunchKernelGGL(k_n2v_compact, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, h->st, h->d_touch, words, h->d_list, h->d_count);
+}
+// the listed rows brought to step adam_t
+static void lazy_catchup_rows(ntf_n2v* h, int64_t cap) {
+    const adam_consts c = adam_at(1);                         // b1, b2 and eps alone: every step's own two constants come from the ring
+    const dim3 grid((unsigned)std::min<int64_t>((std::max<int64_t>(cap, 1) + 3) / 4, 256 * 8)), block(256);
+    with_nv(h->d / 64, [&](auto nv) {
+        hipLaunchKernelGGL((k_n2v_catchup_rows<decltype(nv)::value, false>), grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_applied, h->d_ring, (float2*)nullptr,
+                           (uint32_t)h->lazy_window, h->d_list, h->d_count, h->d, (uint32_t)h->adam_t, 0.f, (float)c.b1, (float)c.b2, c.eps, 0.f);
+    });
+}
+// the full flush: every row to step adam_t, after which the ring is free again.  It reads no mark, so a pending gradient's marks survive it
+static void lazy_flush(ntf_n2v* h) {
+    if (h->adam_t == h->lazy_base) return;                   // every row is there already
+    const adam_consts c = adam_at(1);                         // b1, b2 and eps alone: every step's own two constants come from the ring
+    const dim3 grid((unsigned)std::min<int64_t>((h->n + 3) / 4, 256 * 32)), block(256);
+    with_nv(h->d / 64, [&](auto nv) {
+        hipLaunchKernelGGL(k_n2v_catchup_all<decltype(nv)::value>, grid, block, 0, h->st, h->W, h->M1, h->V2, h->d_applied, h->d_ring, (uint32_t)h->lazy_window, h->n, h->d,
+                           (uint32_t)h->adam_t, (float)c.b1, (float)c.b2, c.eps);
+    });
+    h->lazy_base = h->adam_t; h->lazy_flushes += 1;
+}
+// the step of the batch on the listed rows (already at adam_t - 1, the step before): k_n2v_adam's two constants, rounded as launch_dense_adam rounds them, go to
+// the kernel and from its first lane into the ring (the caller has made room in it).  G and the marks are clear afterwards
+static void launch_lazy_adam(ntf_n2v* h, float lr, int64_t cap) {
+    const adam_consts c = adam_at(h->adam_t);
+    const dim3 grid((unsigned)std::min<int64_t>((std::max<int64_t>(cap, 1) + 3) / 4, 256 * 8)), block(256);
+    with_nv(h->d / 64, [&](auto nv) {
+        hipLaunchKernelGGL((k_n2v_catchup_rows<decltype(nv)::value, true>), grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_applied, h->d_ring,
+                           h->d_ring + h->adam_t % h->lazy_window, (uint32_t)h->lazy_window, h->d_list, h->d_count, h->d, (uint32_t)(h->adam_t - 1),
+                           lr / (float)c.bc1, (float)c.b1, (float)c.b2, c.eps, (float)std::sqrt(c.bc2));
+    });
+    hipMemsetAsync(h->d_touch, 0, (size_t)((h->n + 31) / 32) * 4, h->st);
+}
+
 static void launch_pairs(ntf_n2v* h, const int64_t* rows, int64_t n_rows, int ctx, int positive) {
     if (n_rows <= 0 || ctx < 2) return;
     const float inv = 1.f / (float)(n_rows * (ctx - 1));
@@ -640,15 +817,19 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
     }
     // the window entries of this call: what k_n2v_touch runs over, and with the pending ones the bound of the row list
     const int64_t entries = injected ? (n_pos + n_neg) * context : (int64_t)B * walks_per_node * (1 + (int64_t)num_neg) * (walk_length + 1 - context) * context;
-    if (h->opt == 1 && (r = dev_grow(h, &h->d_list, &h->list_cap, std::min<int64_t>(h->n, h->pend_entries + entries)))) return r;
+    const bool lazy = h->lazy_window > 0;                    // the dense and the sparse path below are what they were; the lazy one defers the pairs
+    if (lazy && apply && h->adam_t >= 0xFFFFFFFFll) FAIL(h, NTF_ESTATE, "n2v: the step count of a lazy handle no longer fits its per-row counter (uint32)");
+    if ((h->opt == 1 || lazy) && (r = dev_grow(h, &h->d_list, &h->list_cap, std::min<int64_t>(h->n, h->pend_entries + entries)))) return r;
     HIPCHK(h, hipMemsetAsync(h->d_loss, 0, 8, h->st));
     const uint64_t step = h->step++;
     if (injected) {
         if (n_pos) HIPCHK(h, hipMemcpyAsync(h->d_rows, inj_pos, n_pos * context * 8, hipMemcpyHostToDevice, h->st));
         if (n_neg) HIPCHK(h, hipMemcpyAsync(h->d_rows + n_pos * context, inj_neg, n_neg * context * 8, hipMemcpyHostToDevice, h->st));
         HIPCHK(h, hipStreamSynchronize(h->st));
-        launch_pairs(h, h->d_rows, n_pos, context, 1);
-        launch_pairs(h, h->d_rows + n_pos * context, n_neg, context, 0);
+        if (!lazy) {
+            launch_pairs(h, h->d_rows, n_pos, context, 1);
+            launch_pairs(h, h->d_rows + n_pos * context, n_neg, context, 0);
+        }
         h->win_p = h->d_rows; h->win_n = h->d_rows + n_pos * context; h->n_win_p = n_pos; h->n_win_n = n_neg;
     } else {
         const int nw = walk_length + 1 - context;
@@ -659,22 +840,35 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
         int64_t* win_p = rw_n + ng * walk_length; int64_t* win_n = win_p + pw * nw * context;
         launch_walks(h, B, pw, walk_length, step, rw_p);
         hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((pw * nw * context + 255) / 256)), dim3(256), 0, h->st, rw_p, pw, walk_length, context, win_p);
-        launch_pairs(h, win_p, pw * nw, context, 1);
+        if (!lazy) launch_pairs(h, win_p, pw * nw, context, 1);
         if (ng) {
             launch_negs(h, B, ng, walk_length, step, rw_n);
             hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((ng * nw * context + 255) / 256)), dim3(256), 0, h->st, rw_n, ng, walk_length, context, win_n);
-            launch_pairs(h, win_n, ng * nw, context, 0);
+            if (!lazy) launch_pairs(h, win_n, ng * nw, context, 0);
         }
         h->win_p = win_p; h->win_n = win_n; h->n_win_p = pw * nw; h->n_win_n = ng * nw;
     }
     h->win_ctx = context;
     h->pend_entries += entries;
+    const int64_t lazy_cap = std::min<int64_t>(h->n, h->pend_entries);
+    if (lazy) {
+        // the pairs read W only at the rows the windows name: mark them, list them with the rows earlier apply = 0 calls marked (current already: an empty loop),
+        // bring them to adam_t, and only then run the pairs - in the order the dense path launches them
+        if (entries > 0) hipLaunchKernelGGL(k_n2v_touch, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, h->st, h->win_p, entries,
+                                            h->m2v ? h->mp.total : (int64_t)-1, h->d_touch);
+        lazy_list(h, true);
+        lazy_catchup_rows(h, lazy_cap);
+        launch_pairs(h, h->win_p, h->n_win_p, context, 1);
+        launch_pairs(h, h->win_n, h->n_win_n, context, 0);
+    }
     // sparse mode: the positive and the negative window rows lie back to back from win_p on, `entries` ids in all
     if (h->opt == 1 && entries > 0) hipLaunchKernelGGL(k_n2v_touch, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, h->st, h->win_p, entries,
                                                        h->m2v ? h->mp.total : (int64_t)-1, h->d_touch);
     if (apply) {
+        if (lazy && h->adam_t - h->lazy_base == h->lazy_window) lazy_flush(h);       // the ring is full: every row to adam_t, and its slots are free
         h->adam_t += 1;
-        if (h->opt == 1) launch_sparse_adam(h, lr); else launch_dense_adam(h, lr);
+        if (lazy) launch_lazy_adam(h, lr, lazy_cap);
+        else if (h->opt == 1) launch_sparse_adam(h, lr); else launch_dense_adam(h, lr);
         h->pend_entries = 0;
     }
     if (loss_out) {
@@ -691,6 +885,7 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
 extern "C" int ntf_n2v_get(ntf_n2v* h, int what, float* host) {   // what: 0 = embedding.weight, 1 = its gradient (as the last batch with apply = 0 left it)
     if (!h || !host || what < 0 || what > 1) return NTF_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
+    if (h->lazy_window && what == 0) lazy_flush(h);          // the table a reader sees is dense Adam's at step adam_t
     HIPCHK(h, hipStreamSynchronize(h->st));
     HIPCHK(h, hipMemcpy2D(host, (size_t)h->d_user * 4, what ? h->G : h->W, (size_t)h->d * 4, (size_t)h->d_user * 4, (size_t)h->n, hipMemcpyDeviceToHost));
     if (what) {   // reading the gradient consumes it, and with it the marks of the rows it named
@@ -704,6 +899,7 @@ extern "C" int ntf_n2v_get(ntf_n2v* h, int what, float* host) {   // what: 0 = e
 extern "C" int ntf_n2v_moments(ntf_n2v* h, float* exp_avg, float* exp_avg_sq) {   // Adam's two moments [num_nodes, d], either may be NULL; reads only
     if (!h) return NTF_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
+    if (h->lazy_window) lazy_flush(h);
     HIPCHK(h, hipStreamSynchronize(h->st));
     const size_t row = (size_t)h->d_user * 4;
     if (exp_avg) HIPCHK(h, hipMemcpy2D(exp_avg, row, h->M1, (size_t)h->d * 4, row, (size_t)h->n, hipMemcpyDeviceToHost));
@@ -727,8 +923,15 @@ extern "C" int ntf_n2v_edge_bce(ntf_n2v* h, const int64_t* src, const int64_t* d
     HIPCHK(h, hipSetDevice(h->device));
     for (int64_t i = 0; i < n; ++i) if (src[i] < 0 || src[i] >= h->n || dst[i] < 0 || dst[i] >= h->n) FAIL(h, NTF_EINVAL, "n2v: edge endpoint out of range");
     int r = need_rows(h, 2 * n); if (r) return r;
+    const bool lazy_rows = h->lazy_window > 0 && h->pend_entries == 0;     // no gradient pending: the bitmap is free for the endpoints
+    if (lazy_rows && (r = dev_grow(h, &h->d_list, &h->list_cap, std::min<int64_t>(h->n, 2 * n)))) return r;
     HIPCHK(h, hipMemcpyAsync(h->d_rows, src, n * 8, hipMemcpyHostToDevice, h->st));
     HIPCHK(h, hipMemcpyAsync(h->d_rows + n, dst, n * 8, hipMemcpyHostToDevice, h->st));
+    if (lazy_rows) {                                        // only the rows read are brought to adam_t
+        hipLaunchKernelGGL(k_n2v_touch, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, h->st, h->d_rows, 2 * n, (int64_t)-1, h->d_touch);
+        lazy_list(h, false);
+        lazy_catchup_rows(h, std::min<int64_t>(h->n, 2 * n));
+    } else if (h->lazy_window) lazy_flush(h);               // a gradient is pending and its marks must survive: the full flush reads none
     HIPCHK(h, hipMemsetAsync(h->d_loss + 1, 0, 8, h->st));
     hipLaunchKernelGGL(k_n2v_edge_bce, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->st, h->W, h->d_rows, h->d_rows + n, n, h->d, h->d_loss + 1);
     double l = 0;

@@ -119,6 +119,8 @@ SYMBOLS = {
     "ntf_n2v_set_optimizer": (C.c_int, [_P, _I32]),
     "ntf_n2v_moments": (C.c_int, [_P, _P, _P]),
     "ntf_n2v_set_walk_bias": (C.c_int, [_P, C.c_double, C.c_double]),
+    "ntf_n2v_set_lazy": (C.c_int, [_P, _I32]),
+    "ntf_n2v_lazy_state": (C.c_int, [_P, _P, _P, _P]),
     "ntf_m2v_create": (C.c_int, [C.c_int, _I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _U64, C.POINTER(_P)]),
     "ntf_d2v_create": (C.c_int, [C.c_int, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _U64, C.POINTER(_P)]),
     "ntf_d2v_destroy": (None, [_P]),
@@ -650,20 +652,23 @@ class Engine(_Handle):
 class Node2Vec(_Handle):
     """torch_geometric.nn.Node2Vec resident on one MI355X: embedding.weight [num_nodes, d] + dense Adam, or with sparse=True torch.optim.SparseAdam
     over the rows a batch names (include/opentf_amd.h, ntf_n2v_set_optimizer).  p, q: the return and in-out parameters of the walks (ntf_n2v_set_walk_bias);
-    (1, 1), the default, is the uniform walk."""
+    (1, 1), the default, is the uniform walk.  lazy=True (or a window in steps): dense Adam's table, bit for bit, with only the rows a batch names written
+    (ntf_n2v_set_lazy); not with sparse."""
 
     _CREATE, _DESTROY, _LAST_ERROR, _TAG = "ntf_n2v_create", "ntf_n2v_destroy", "ntf_n2v_last_error", " n2v"
+    LAZY_WINDOW = 4096          # lazy=True: a full flush every 4096 applied steps at the latest, a ring of 32 KB
 
-    def __init__(self, rowptr, col, init_weight, seed=0, device=0, sparse=False, p=1.0, q=1.0):
+    def __init__(self, rowptr, col, init_weight, seed=0, device=0, sparse=False, p=1.0, q=1.0, lazy=False):
         self.rowptr = np.ascontiguousarray(rowptr, dtype=np.int64); self.col = np.ascontiguousarray(col, dtype=np.int32)
         w = _f32(init_weight)
         self.num_nodes, self.d = w.shape
         if len(self.rowptr) != self.num_nodes + 1:
             raise NtfError("rowptr must have num_nodes + 1 entries")
         self._create(int(device), self.num_nodes, self.d, _ptr(self.rowptr), _ptr(self.col), _ptr(w), int(seed) & (2**64 - 1))
-        self.sparse = False
+        self.sparse = False; self.lazy = 0
         self.p, self.q = 1.0, 1.0
         if sparse: self.set_optimizer(True)
+        if lazy: self.set_lazy(lazy)
         if float(p) != 1.0 or float(q) != 1.0: self.set_walk_bias(p, q)
 
     def set_walk_bias(self, p, q):
@@ -676,6 +681,19 @@ class Node2Vec(_Handle):
         """dense Adam (False / 0) or sparse Adam (True / 1); refused once a step has been applied or while a gradient is pending"""
         self._ck(lib().ntf_n2v_set_optimizer(self._h, int(bool(sparse))))
         self.sparse = bool(sparse)
+
+    def set_lazy(self, window):
+        """lazy dense Adam: True = the default window (LAZY_WINDOW steps), False / 0 = off, otherwise the ring's size in steps; refused on a sparse handle, once a
+        step has been applied or while a gradient is pending"""
+        w = self.LAZY_WINDOW if window is True else int(window)
+        self._ck(lib().ntf_n2v_set_lazy(self._h, w))
+        self.lazy = w
+
+    def lazy_state(self):
+        """(applied [num_nodes] uint32: the Adam steps each row has taken, applied steps of the handle, full flushes so far); reads only, flushes nothing"""
+        a = np.empty(self.num_nodes, dtype=np.uint32); steps, flushes = C.c_int64(), C.c_int64()
+        self._ck(lib().ntf_n2v_lazy_state(self._h, _ptr(a), C.byref(steps), C.byref(flushes)))
+        return a, steps.value, flushes.value
 
     def walks(self, start, walk_length, step=0):
         s = np.ascontiguousarray(start, dtype=np.int64)
@@ -730,7 +748,7 @@ class MetaPath2Vec(Node2Vec):
 
     _CREATE = "ntf_m2v_create"
 
-    def __init__(self, type_counts, hops, init_weight, seed=0, device=0, sparse=False):
+    def __init__(self, type_counts, hops, init_weight, seed=0, device=0, sparse=False, lazy=False):
         tc = np.ascontiguousarray(type_counts, dtype=np.int64).reshape(-1)
         w = _f32(init_weight)
         self.num_nodes, self.d = w.shape
@@ -747,8 +765,9 @@ class MetaPath2Vec(Node2Vec):
         rps = (C.c_void_p * max(len(hops), 1))(*[a.ctypes.data for a in self._rowptr])
         cls = (C.c_void_p * max(len(hops), 1))(*[a.ctypes.data if a.size else None for a in self._col])
         self._create(int(device), len(tc), _ptr(tc), len(hops), _ptr(hs), _ptr(hd), rps, cls, self.d, _ptr(w), int(seed) & (2**64 - 1))
-        self.sparse = False
+        self.sparse = False; self.lazy = 0
         if sparse: self.set_optimizer(True)
+        if lazy: self.set_lazy(lazy)
 
 
 class Doc2Vec(_Handle):

@@ -7,7 +7,7 @@ What the caller (src/main.py:100-153) does and what it gets here:
       per fold: the 'stm' graph (skill - team - member) without the member-team edges of the test and of that fold's validation teams
       (gnn.py:84-116), `torch_geometric.nn.Node2Vec` (its `p` / `q` read from the n2v section, absent = 1) trained by `_train_rw` (gnn.py:401-453: shuffled node batches, Adam,
       ReduceLROnPlateau on v_loss, EarlyStopping, `f{k}.pt` / `f{k}.e{e}.pt` checkpoints holding `embedding.weight`).  Here the walks,
-      the skip-gram loss, its gradient and the dense Adam (or, with `sparse: true` in the method's section, sparse Adam) run in `opentf_amd/csrc/ntf_n2v.hip`; control flow, file names and
+      the skip-gram loss, its gradient and the dense Adam (or, with `sparse: true` in the method's section, sparse Adam; with `lazy: true`, dense Adam writing only the rows a batch names) run in `opentf_amd/csrc/ntf_n2v.hip`; control flow, file names and
       checkpoint keys are the reference's.  An existing `f{k}.pt` is loaded instead, as gnn.py:402-405 does: one written by THIS plugin carries the node order its rows are
       sliced by; one the reference trained follows the node-store order of ITS pickled graph (`{structure}.{dup_edge}.graph.pkl` beside the splits directory,
       gnn.py:21-23) - that file is read (opentf_amd/mdl/emb/pyg_reader.py: a restricted unpickler, no torch_geometric) and the rows are re-stacked; without the graph file
@@ -184,6 +184,8 @@ class Gnn(T2v):
         self.metapath, self.metapath_label = _metapath(cfg) if self.name == "m2v" else (None, None)      # refused here, before any device call
         if self.metapath and int(cfg_get(self._mcfg(), "wl") or 0) > len(self.metapath) and self.metapath[-1][2] != self.metapath[0][0]:
             raise ValueError("m2v: wl steps outrun the metapath, which does not end on its start type")
+        if self._lazy() and self._sparse():     # before any device call, as above
+            raise ValueError(f"{self.name}: `lazy` is a mode of dense Adam and `sparse` another optimiser; set one of them")
         self.writer = summary_writer()
         self.offsets = None
         self.blocks = None      # {node type: (first row, end row)} of the loaded table
@@ -194,6 +196,11 @@ class Gnn(T2v):
     def _sparse(self):
         """the `sparse` key of the n2v / m2v section (Node2Vec / MetaPath2Vec(sparse=True) trained with torch.optim.SparseAdam); absent or false: dense Adam"""
         return bool(cfg_get(self._mcfg(), "sparse"))
+
+    def _lazy(self):
+        """the `lazy` key of the n2v / m2v section: dense Adam that writes only the rows a batch names (ntf_n2v_set_lazy).  The table is dense Adam's, bit for bit,
+        so the key is not part of the directory name and a lazy run may load or leave an f{k}.pt of a plain dense run"""
+        return bool(cfg_get(self._mcfg(), "lazy"))
 
     def _bias(self):
         """(p, q) of the n2v section (src/mdl/emb/__config__.yaml:69-70), absent = 1.0; m2v ignores the keys, as MetaPath2Vec has neither"""
@@ -242,10 +249,10 @@ class Gnn(T2v):
                 n_start = n
             self.offsets = off
             init = torch.nn.Embedding(n, d).weight.detach().numpy()       # the draw Node2Vec's / MetaPath2Vec's constructor makes (gnn.py:153-160): Embedding(count + 1, d) for m2v
-            if self.name == "m2v": make_net = lambda: libntf.MetaPath2Vec(counts, hops, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse())
+            if self.name == "m2v": make_net = lambda: libntf.MetaPath2Vec(counts, hops, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse(), lazy=self._lazy())
             else:
                 p, q = self._bias()
-                make_net = lambda: libntf.Node2Vec(rowptr, col, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse(), p=p, q=q)
+                make_net = lambda: libntf.Node2Vec(rowptr, col, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse(), p=p, q=q, lazy=self._lazy())
             path = f"{self.output}/f{foldidx}.pt"
             _barrier()                                                     # torchrun: nobody looks for the file while rank 0 may still be writing the previous one
             if not _rank0_says(os.path.exists(path)):                      # gnn.py:402-405: a trained table is loaded, not retrained (rank 0 decides for the job)
