@@ -138,6 +138,15 @@ SYMBOLS = {
     "ntf_k_fill_sign": (C.c_int, [_P, _U64, _U64, C.c_int, C.c_int, C.c_int, _P]),
 }
 
+# every symbol declared in include/opentf_amd_fair.h (the fair stage: a header and a table of its own, NTF_ABI_VERSION unchanged)
+NTF_FAIR_MAX_GROUPS, NTF_FAIR_MAX_K = 64, 2048
+FAIR_DET_GREEDY, FAIR_DET_CONS, FAIR_DET_RELAXED = 0, 1, 2
+FAIR_ALGORITHMS = {"det_greedy": FAIR_DET_GREEDY, "det_cons": FAIR_DET_CONS, "det_relaxed": FAIR_DET_RELAXED}
+FAIR_SYMBOLS = {
+    "ntf_fair_rerank": (C.c_int, [C.c_int, _I32, _P, _P, _I64, _I32, _P, _I64, _I32, _P, _I64, _I32, _P, _P, _P]),
+    "ntf_fair_metrics": (C.c_int, [C.c_int, _P, _I64, _I32, _P, _I64, _I32, _P, _I64, _P, _I32, _P, _P]),
+}
+
 _lib = None
 
 
@@ -151,6 +160,9 @@ def lib():
         l = C.CDLL(_LIB_PATH)
         for name, (res, args) in SYMBOLS.items():
             fn = getattr(l, name)  # AttributeError if the library does not export a declared symbol
+            fn.restype, fn.argtypes = res, args
+        for name, (res, args) in FAIR_SYMBOLS.items():
+            fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         if l.ntf_abi_version() != NTF_ABI_VERSION:
             raise NtfError("libopentf_amd.so ABI version mismatch")
@@ -176,6 +188,55 @@ def infer_mc_plan(experts, h, passes, budget_bytes):
     if rc != 0:
         raise NtfError(f"ntf_infer_mc_plan failed ({rc})")
     return g.value, r.value
+
+
+def _fair_inputs(idx, group, p):
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    if idx.ndim != 2:
+        raise NtfError(f"ranked ids must be [n, K], got {idx.shape}")
+    group = np.ascontiguousarray(group, dtype=np.uint8).reshape(-1)
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    if p.ndim == 1: p = p.reshape(1, -1)
+    if p.ndim != 2:
+        raise NtfError(f"the target distribution must be [G], [1, G] or [n, G], got {p.shape}")
+    return idx, group, p
+
+
+def fair_rerank(cand_idx, cand_val, group, p, algorithm, k_out=None, device=0, want_pos=False):
+    """ntf_fair_rerank (include/opentf_amd_fair.h): cand_idx [n, K] int32 ranked best first, cand_val [n, K] f32 or None, group [n_experts] uint8, p [G], [1, G] or
+    [n, G] f64, algorithm one of FAIR_ALGORITHMS (a name or its code), k_out (None: K).  -> (out_idx [n, k_out] int32, out_val [n, k_out] f32 or None[, out_pos])"""
+    idx, group, p = _fair_inputs(cand_idx, group, p)
+    val = None if cand_val is None else _f32(cand_val)
+    if val is not None and val.shape != idx.shape:
+        raise NtfError(f"cand_val {val.shape} does not match cand_idx {idx.shape}")
+    alg = FAIR_ALGORITHMS.get(algorithm, algorithm)
+    if isinstance(alg, str):
+        raise NtfError(f"unknown fair algorithm {algorithm!r}: one of {sorted(FAIR_ALGORITHMS)}")
+    n, K = idx.shape
+    k_out = K if k_out is None else int(k_out)
+    shape = (n, max(k_out, 0))
+    out_idx = np.empty(shape, dtype=np.int32)
+    out_val = None if val is None else np.empty(shape, dtype=np.float32)
+    out_pos = np.empty(shape, dtype=np.int32) if want_pos else None
+    rc = lib().ntf_fair_rerank(int(device), int(alg), _ptr(idx), _ptr(val), n, K, _ptr(group), len(group), p.shape[1], _ptr(p), p.shape[0], k_out,
+                               _ptr(out_idx), _ptr(out_val), _ptr(out_pos))
+    if rc != 0:
+        raise NtfError(f"ntf_fair_rerank failed ({rc})" + (": an argument outside the contract of include/opentf_amd_fair.h" if rc == NTF_EINVAL else ""))
+    return (out_idx, out_val, out_pos) if want_pos else (out_idx, out_val)
+
+
+def fair_metrics(idx, group, p, cutoffs, device=0, ndkl=True, skew=True):
+    """ntf_fair_metrics (include/opentf_amd_fair.h) of the ranked ids idx [n, K]: -> (ndkl [n, n_cut] f64 or None, skew [n, n_cut, G] f64 or None)"""
+    idx, group, p = _fair_inputs(idx, group, p)
+    cu = np.ascontiguousarray(np.asarray(cutoffs, dtype=np.int32).reshape(-1))
+    n, K = idx.shape
+    G = p.shape[1]
+    out_n = np.empty((n, len(cu)), dtype=np.float64) if ndkl else None
+    out_s = np.empty((n, len(cu), G), dtype=np.float64) if skew else None
+    rc = lib().ntf_fair_metrics(int(device), _ptr(idx), n, K, _ptr(group), len(group), G, _ptr(p), p.shape[0], _ptr(cu), len(cu), _ptr(out_n), _ptr(out_s))
+    if rc != 0:
+        raise NtfError(f"ntf_fair_metrics failed ({rc})" + (": an argument outside the contract of include/opentf_amd_fair.h" if rc == NTF_EINVAL else ""))
+    return out_n, out_s
 
 
 class DeviceView:

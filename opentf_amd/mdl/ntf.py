@@ -1,8 +1,8 @@
 """Plugin base mirroring the reference's `mdl.ntf.Ntf` (src/mdl/ntf.py:5-31): same constructor, attributes,
-output-directory naming and method names.  `evaluate` / `adila` are the reference's post-hoc CPU metrics
-(src/mdl/ntf.py:32-134) and are out of this build's scope: when the classes of
-this package are mounted inside the reference tree they inherit those two methods from the
-reference's own `Ntf`; standalone they raise.
+output-directory naming and method names.  `evaluate` / `adila` are the reference's post-hoc stages
+(src/mdl/ntf.py:32-134): when the classes of this package are mounted inside the
+reference tree they inherit those two methods from the reference's own `Ntf`; standalone,
+`evaluate` scores on the device (evl.metric) and `adila` re-ranks and scores on the device (evl.fair).
 """
 from __future__ import annotations
 
@@ -215,4 +215,27 @@ class Ntf:
         return self._engine(teamsvecs, int(cfg_get(self.cfg, "b")), train=False)[0]
 
     def adila(self, teamsvecs, splits, faircfg):
-        raise NotImplementedError("adila() is the reference's fairness stage (src/mdl/ntf.py:108-134); see INTEGRATION.md")
+        """Fair stage (the reference's src/mdl/ntf.py:108-134 hands it to a submodule it does not ship): every test-set prediction file `_pred_jobs` lists is ranked
+        `k_max` deep, re-ranked on the device towards the target distribution of the protected attribute (`evl.fair`: DetGreedy / DetCons / DetRelaxed) and both
+        lists are scored for fairness and utility.  Beside each prediction file, with `stem = evl.fair.fair_stem(file, spec)`: `stem.rerank.pred` ({'y_pred': sparse
+        COO of the re-ranked ids with their values, 'ranked': the ids in rank order, int32 [n, k_max], 'uncertainty': None}), `stem.faireval.csv` and
+        `stem.utileval.csv` (before / after columns).  faircfg keys: algorithm, notion, attribute, k_max, cutoffs (`evl.fair.FairSpec`).  File names, keys and the
+        popularity rule are this package's own; mounted in the reference tree the plugin inherits the reference's adila() instead."""
+        import torch
+        from ..evl import fair
+        assert os.path.isdir(self.output), f"No folder for {self.output} exist!"
+        if dist_rank() != 0:        # torchrun: ONE writer, as in evaluate()
+            _dist_barrier(); return
+        spec = fair.FairSpec.from_cfg(faircfg)
+        group, names = spec.groups(teamsvecs["member"])
+        M = int(teamsvecs["member"].shape[1])
+        for job in _pred_jobs(self.output, splits, False, bool(cfg_get(faircfg, "per_epoch"))):
+            rows = np.asarray(splits["test"], dtype=np.int64)
+            idx, val, faireval, utileval = fair.fair_predictions(teamsvecs, rows, _read_pred(job.path), spec, group, names)
+            stem = fair.fair_stem(job.path, spec)
+            r = np.repeat(np.arange(len(rows), dtype=np.int64), idx.shape[1])
+            y = torch.sparse_coo_tensor(torch.from_numpy(np.stack([r, idx.reshape(-1).astype(np.int64)])), torch.from_numpy(val.reshape(-1)), size=(len(rows), M)).coalesce()
+            torch.save({"y_pred": y, "ranked": idx, "uncertainty": None}, f"{stem}.rerank.pred", pickle_protocol=4)
+            faireval.to_csv(f"{stem}.faireval.csv")
+            utileval.to_csv(f"{stem}.utileval.csv")
+        _dist_barrier()   # rank 0 wrote: the other ranks (waiting at the top) may go on
