@@ -6,8 +6,14 @@
 //   loss    : -mean log(sigmoid(<e_start, e_rest>) + 1e-15) over positive pairs  - mean log(1 - sigmoid(.) + 1e-15) over negative pairs
 //   update  : torch.optim.Adam on the dense embedding matrix (every row moves every step through its moments); opt-in (ntf_n2v_set_optimizer) torch.optim.SparseAdam
 //             over the rows the batch names: k_n2v_touch -> k_n2v_compact -> k_n2v_adam_rows
-//             opt-in too (ntf_n2v_set_lazy) LAZY dense Adam: dense Adam's table bit for bit, only the rows a batch names written - k_n2v_touch -> k_n2v_compact_keep ->
+//             opt-in too (ntf_n2v_set_lazy) LAZY dense Adam: dense Adam's table bit for bit, only the rows a batch names written - k_n2v_touch -> k_n2v_compact<false> ->
 //             k_n2v_catchup_rows before the pairs, k_n2v_catchup_rows<NV, true> after them, k_n2v_catchup_all where a reader wants the whole table
+// One training step (ntf_n2v_train_batch) for the three of them, every stage written once: the checks; the WINDOWS (make_windows: walks, negatives, both window
+// launches - or upload_windows for injected rows); ACCUMULATE: not dense - mark the rows the windows name; lazy - list them, marks kept, and bring them to adam_t;
+// then the positive pairs, then the negative pairs; APPLY (apply != 0): lazy flushes a full ring, adam_t goes up, the mode's own launch runs; the loss is read.
+// So sparse marks before the pairs, not after them, and launches them behind the negative windows as lazy does.  Nothing sees other inputs for it: one stream;
+// walks, negatives and windows touch none of W, G, the loss cell and the bitmap; k_n2v_touch reads the window rows and writes only the bitmap, which the pairs
+// do not read; positive pairs still precede negative ones.  A native DENSE batch keeps each sign's pairs right behind its window launch (make_windows' pairs_now).
 // One wave per window row: the start row lives in registers (d / 64 values per lane), every rest row costs one coalesced row read, a wave
 // reduction and one coalesced f32 atomic row add (the forms that run at full rate on gfx950: 256 contiguous bytes per wave-instruction).
 // metapath2vec (torch_geometric.nn.MetaPath2Vec, the `m2v` method of the same plugin) is node2vec after the walks: ntf_m2v_create makes an ntf_n2v handle that carries a
@@ -34,6 +40,13 @@ struct m2v_path {
     int64_t src_start[NTF_M2V_MAX_HOPS] = {}, dst_start[NTF_M2V_MAX_HOPS] = {}, dst_count[NTF_M2V_MAX_HOPS] = {};
 };
 
+// the row list of a sparse or a lazy handle.  bits: one bit per row (ceil(n / 32) words), set by k_n2v_touch; k_n2v_compact lists the marked rows in list [cap]
+// and counts them in count, and clears the marks unless told to keep them.  Absent (all null) on a handle that was never anything but dense
+struct n2v_rowlist { uint32_t* bits = nullptr; int64_t* list = nullptr; int64_t cap = 0; unsigned long long* count = nullptr; };
+// what lazy dense Adam adds to it.  window > 0 = on: dense Adam that writes only the rows a batch names.  applied [n]: the Adam steps applied to each row
+// (<= adam_t); ring [window]: slot s % window holds (lr / bc1, sqrt(bc2)) of step s, for the steps base + 1 .. adam_t - every row is at base or later;
+// flushes: full flushes (k_n2v_catchup_all) so far
+struct n2v_lazy { int window = 0; uint32_t* applied = nullptr; float2* ring = nullptr; int64_t base = 0, flushes = 0; };
 struct ntf_n2v {
     int device = 0; hipStream_t st = nullptr;
     int64_t n = 0; int d = 0, d_user = 0; int64_t nnz = 0;      // d: the device row stride (a multiple of 64); d_user: the embedding size the host sees
@@ -44,21 +57,18 @@ struct ntf_n2v {
     const int64_t *win_p = nullptr, *win_n = nullptr; int64_t n_win_p = 0, n_win_n = 0; int win_ctx = 0;   // the last batch's window rows inside d_rows (ntf_n2v_last_windows)
     double* d_loss = nullptr;
     int64_t adam_t = 0; uint64_t seed = 0, step = 0;
-    // ntf_n2v_set_optimizer: 0 = dense Adam, 1 = sparse Adam over the rows the windows name.  d_touch: one bit per row (ceil(n / 32) words), set by k_n2v_touch and
-    // cleared by k_n2v_compact, which lists the marked rows in d_list and counts them in d_count.  pend_entries: the window entries whose gradient is in G (both modes)
-    int opt = 0; uint32_t* d_touch = nullptr; int64_t* d_list = nullptr; int64_t list_cap = 0; unsigned long long* d_count = nullptr; int64_t pend_entries = 0;
+    // ntf_n2v_set_optimizer: opt 0 = dense Adam, 1 = sparse Adam; ntf_n2v_set_lazy: lz.window > 0 (opt stays 0) - read through mode().  pend_entries: the window entries whose gradient is in G
+    int opt = 0; n2v_rowlist rl; n2v_lazy lz; int64_t pend_entries = 0;
     bool m2v = false, cycle = false; m2v_path mp; int64_t start_count = 0;   // ntf_m2v_create: the metapath; rowptr / col above stay NULL, n = total + 1
     bool dummy_pairs = false;                                                // pairs through k_n2v_pairs<NV, true>: a metapath handle's default (NTF_M2V_PAIRS=0, read by ntf_m2v_create, turns it off)
     std::vector<void*> hop_bufs;                                           // the per-hop CSRs the metapath points into
     // ntf_n2v_set_walk_bias: biased = some (p, q) other than (1, 1) is in force and the walks go through k_n2v_walks_biased with these thresholds;
     // rows_ascending: -1 = not looked at yet, 0 / 1 = what k_n2v_rows_ascending found (asked once, the first time a bias is set)
     bool biased = false; unsigned long long bias_thr[3] = {0, 0, 0}; int rows_ascending = -1;
-    // ntf_n2v_set_lazy: lazy_window > 0 = dense Adam that writes only the rows a batch names (opt stays 0).  d_applied [n]: the Adam steps applied to each row
-    // (<= adam_t); d_ring [lazy_window]: slot s % lazy_window holds (lr / bc1, sqrt(bc2)) of step s, for the steps lazy_base + 1 .. adam_t - every row is at
-    // lazy_base or later; lazy_flushes: full flushes (k_n2v_catchup_all) so far.  d_touch / d_list / d_count are the sparse route's
-    int lazy_window = 0; uint32_t* d_applied = nullptr; float2* d_ring = nullptr; int64_t lazy_base = 0, lazy_flushes = 0;
     std::string err;
 };
+enum n2v_mode { N2V_DENSE, N2V_SPARSE, N2V_LAZY };
+static n2v_mode mode(const ntf_n2v* h) { return h->lz.window > 0 ? N2V_LAZY : h->opt == 1 ? N2V_SPARSE : N2V_DENSE; }
 static thread_local std::string g_n2v_create_error;
 
 extern "C" const char* ntf_n2v_last_error(const ntf_n2v* h) { return h ? h->err.c_str() : g_n2v_create_error.c_str(); }
@@ -333,8 +343,9 @@ __global__ __launch_bounds__(256) void k_n2v_touch(const int64_t* __restrict__ r
 }
 // the marked rows as a list: one thread per bitmap word, a wave takes ONE slot range from the counter (inclusive scan of the popcounts, the last lane asks), every
 // lane writes the ids of its word behind those of the lanes before it and clears the word.  The order of the waves' ranges is not fixed; each row is listed once.
+// !CLEAR: the same list with the marks left standing (lazy dense Adam lists the rows BEFORE the pairs and keeps the marks of a gradient that stays pending)
 template <bool CLEAR>
-__device__ __forceinline__ void n2v_compact(uint32_t* __restrict__ bits, int64_t n_words, int64_t* __restrict__ list, unsigned long long* __restrict__ count) {
+__global__ __launch_bounds__(256) void k_n2v_compact(uint32_t* __restrict__ bits, int64_t n_words, int64_t* __restrict__ list, unsigned long long* __restrict__ count) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t word = w < n_words ? bits[w] : 0u;            // no early return: every lane takes part in the shuffles
@@ -350,13 +361,6 @@ __device__ __forceinline__ void n2v_compact(uint32_t* __restrict__ bits, int64_t
     const uint32_t lo = __shfl((uint32_t)base, 63, 64), hi = __shfl((uint32_t)(base >> 32), 63, 64);
     int64_t at = (int64_t)(((unsigned long long)hi << 32) | lo) + (incl - c);
     while (word) { list[at++] = w * 32 + (__ffs(word) - 1); word &= word - 1; }
-}
-__global__ __launch_bounds__(256) void k_n2v_compact(uint32_t* __restrict__ bits, int64_t n_words, int64_t* __restrict__ list, unsigned long long* __restrict__ count) {
-    n2v_compact<true>(bits, n_words, list, count);
-}
-// the same list with the marks left standing (lazy dense Adam lists the rows BEFORE the pairs and keeps the marks of a gradient that stays pending)
-__global__ __launch_bounds__(256) void k_n2v_compact_keep(uint32_t* __restrict__ bits, int64_t n_words, int64_t* __restrict__ list, unsigned long long* __restrict__ count) {
-    n2v_compact<false>(bits, n_words, list, count);
 }
 // torch.optim._functional.sparse_adam on the listed rows, one wave per row (NV = d / 64 values per lane), and the row of G cleared for the next batch.
 // step = lr sqrt(1 - b2^t) / (1 - b1^t); omb1 = 1 - b1, omb2 = 1 - b2 (rounded once, on the host); eps is added to sqrt(v) itself - not k_n2v_adam's placement.
@@ -437,7 +441,7 @@ __device__ __forceinline__ void n2v_catchup(float* __restrict__ p, float* __rest
     }
     if (lane == 0 && (GRAD || run || !ALL)) applied[row] = GRAD ? upto + 1u : upto;
 }
-// the listed rows (k_n2v_compact / k_n2v_compact_keep; the grid strides over the count left on the device, as k_n2v_adam_rows does).  GRAD: the step of the batch
+// the listed rows (k_n2v_compact; the grid strides over the count left on the device, as k_n2v_adam_rows does).  GRAD: the step of the batch
 // itself; its first lane also files the step's constants in the ring (`ring_slot` = the slot of step upto + 1, which no catch-up of this launch reads: they stop at upto)
 template <int NV, bool GRAD>
 __global__ __launch_bounds__(256) void k_n2v_catchup_rows(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -476,7 +480,7 @@ extern "C" void ntf_n2v_destroy(ntf_n2v* h) {
     hipSetDevice(h->device);
     if (h->st) hipStreamSynchronize(h->st);
     for (void* p : {(void*)h->rowptr, (void*)h->col, (void*)h->W, (void*)h->G, (void*)h->M1, (void*)h->V2, (void*)h->d_batch, (void*)h->d_rows, (void*)h->d_loss,
-                    (void*)h->d_touch, (void*)h->d_list, (void*)h->d_count, (void*)h->d_applied, (void*)h->d_ring})
+                    (void*)h->rl.bits, (void*)h->rl.list, (void*)h->rl.count, (void*)h->lz.applied, (void*)h->lz.ring})
         if (p) hipFree(p);
     for (void* p : h->hop_bufs) if (p) hipFree(p);
     if (h->st) hipStreamDestroy(h->st);
@@ -621,21 +625,43 @@ extern "C" int ntf_n2v_walks(ntf_n2v* h, const int64_t* start, int64_t n, int32_
     return NTF_OK;
 }
 
+// ---- the row list, host side: what sparse and lazy Adam share.  rowlist_make: the bitmap and the counter of a handle that has none, allocated and cleared into
+// `made` (left empty where the handle has them); the stream is idle on return.  Nothing of the handle changes: the caller commits `made` once all it needs is there
+static int64_t rowlist_words(const ntf_n2v* h) { return (h->n + 31) / 32; }
+static int rowlist_make(ntf_n2v* h, n2v_rowlist* made) {
+    HIPCHK(h, hipSetDevice(h->device));
+    int r = NTF_OK; hipError_t s = hipSuccess;
+    if (!h->rl.bits) {
+        if (!(r = dev_alloc(h, &made->bits, rowlist_words(h)))) r = dev_alloc(h, &made->count, 1);
+        if (!r && (s = hipMemsetAsync(made->bits, 0, (size_t)rowlist_words(h) * 4, h->st)) == hipSuccess) s = hipMemsetAsync(made->count, 0, 8, h->st);
+    }
+    if (!r && s == hipSuccess) s = hipStreamSynchronize(h->st);
+    if (!r && s != hipSuccess) { h->err = std::string("n2v: clearing the row marks: ") + hipGetErrorString(s); r = NTF_EHIP; }
+    if (r) { hipFree(made->bits); hipFree(made->count); *made = n2v_rowlist(); }
+    return r;
+}
+// marks the rows of n ids (k_n2v_touch; `hot`: the row a sizeable share of them names, -1 for none)
+static void rowlist_mark(ntf_n2v* h, const int64_t* ids, int64_t n, int64_t hot) {
+    if (n > 0) hipLaunchKernelGGL(k_n2v_touch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, ids, n, hot, h->rl.bits);
+}
+// the marked rows into rl.list (the caller has grown it to their bound), their number into rl.count; keep: the marks stay
+static void rowlist_list(ntf_n2v* h, bool keep) {
+    hipMemsetAsync(h->rl.count, 0, 8, h->st);
+    hipLaunchKernelGGL((keep ? k_n2v_compact<false> : k_n2v_compact<true>), dim3((unsigned)((rowlist_words(h) + 255) / 256)), dim3(256), 0, h->st, h->rl.bits,
+                       rowlist_words(h), h->rl.list, h->rl.count);
+}
+// the grid of a kernel that strides over the listed rows, one wave a row, for a list of at most `cap` rows
+static dim3 rowlist_grid(int64_t cap) { return dim3((unsigned)std::min<int64_t>((std::max<int64_t>(cap, 1) + 3) / 4, 256 * 8)); }
+
 extern "C" int ntf_n2v_set_optimizer(ntf_n2v* h, int32_t kind) {
     if (!h) return NTF_EINVAL;
     if (kind != 0 && kind != 1) FAIL(h, NTF_EINVAL, "n2v: optimizer kind must be 0 (dense Adam) or 1 (sparse Adam)");
     if (h->adam_t > 0 || h->pend_entries > 0) FAIL(h, NTF_ESTATE, "n2v: the optimizer is chosen before the first step and with no gradient pending");
-    if (kind == 1 && h->lazy_window) FAIL(h, NTF_ESTATE, "n2v: a lazy dense handle takes no sparse Adam (ntf_n2v_set_lazy(h, 0) first)");
-    if (kind == 1 && !h->d_touch) {
-        HIPCHK(h, hipSetDevice(h->device));
-        const int64_t words = (h->n + 31) / 32;
-        uint32_t* bits = nullptr; unsigned long long* cnt = nullptr;
-        int r = dev_alloc(h, &bits, words); if (r) return r;
-        if ((r = dev_alloc(h, &cnt, 1))) { hipFree(bits); return r; }
-        h->d_touch = bits; h->d_count = cnt;
-        HIPCHK(h, hipMemsetAsync(h->d_touch, 0, (size_t)words * 4, h->st));
-        HIPCHK(h, hipMemsetAsync(h->d_count, 0, 8, h->st));
-        HIPCHK(h, hipStreamSynchronize(h->st));
+    if (kind == 1 && h->lz.window) FAIL(h, NTF_ESTATE, "n2v: a lazy dense handle takes no sparse Adam (ntf_n2v_set_lazy(h, 0) first)");
+    if (kind == 1) {
+        n2v_rowlist made;
+        if (int r = rowlist_make(h, &made)) return r;
+        if (made.bits) h->rl = made;
     }
     h->opt = kind;
     return NTF_OK;
@@ -647,42 +673,32 @@ extern "C" int ntf_n2v_set_lazy(ntf_n2v* h, int32_t window) {
     if (window < 0) FAIL(h, NTF_EINVAL, "n2v: the lazy window is 0 (off) or a number of steps >= 1");
     if (h->opt == 1) FAIL(h, NTF_ESTATE, "n2v: lazy dense Adam is a mode of the dense optimizer; this handle runs sparse Adam");
     if (h->adam_t > 0 || h->pend_entries > 0) FAIL(h, NTF_ESTATE, "n2v: the lazy mode is chosen before the first step and with no gradient pending");
-    if (window == 0 || window == h->lazy_window) { h->lazy_window = window; return NTF_OK; }
+    if (window == 0 || window == h->lz.window) { h->lz.window = window; return NTF_OK; }
     HIPCHK(h, hipSetDevice(h->device));
-    const int64_t words = (h->n + 31) / 32;
-    uint32_t *bits = nullptr, *applied = nullptr; unsigned long long* cnt = nullptr; float2* ring = nullptr;
+    n2v_rowlist made; uint32_t* applied = nullptr; float2* ring = nullptr;
     int r = dev_alloc(h, &ring, window);
-    if (!r && !h->d_applied) r = dev_alloc(h, &applied, h->n);
-    if (!r && !h->d_touch) { r = dev_alloc(h, &bits, words); if (!r) r = dev_alloc(h, &cnt, 1); }
-    hipError_t s = hipSuccess;
-    if (!r) {
-        if (applied) s = hipMemsetAsync(applied, 0, (size_t)h->n * 4, h->st);
-        if (s == hipSuccess && bits) s = hipMemsetAsync(bits, 0, (size_t)words * 4, h->st);
-        if (s == hipSuccess && cnt) s = hipMemsetAsync(cnt, 0, 8, h->st);
-        if (s == hipSuccess) s = hipStreamSynchronize(h->st);
-    }
-    if (r || s != hipSuccess) {
-        for (void* q : {(void*)ring, (void*)applied, (void*)bits, (void*)cnt}) if (q) hipFree(q);
-        if (r) return r;
-        FAIL(h, NTF_EHIP, std::string("n2v: clearing the lazy state: ") + hipGetErrorString(s));
-    }
-    if (h->d_ring) hipFree(h->d_ring);
-    h->d_ring = ring;
-    if (applied) h->d_applied = applied;
-    if (bits) { h->d_touch = bits; h->d_count = cnt; }
-    h->lazy_window = window; h->lazy_base = 0;
+    if (!r && !h->lz.applied) r = dev_alloc(h, &applied, h->n);
+    hipError_t s = !r && applied ? hipMemsetAsync(applied, 0, (size_t)h->n * 4, h->st) : hipSuccess;
+    if (s != hipSuccess) { h->err = std::string("n2v: clearing the lazy state: ") + hipGetErrorString(s); r = NTF_EHIP; }
+    if (!r) r = rowlist_make(h, &made);                       // its wait is the wait for `applied` too
+    if (r) { hipFree(ring); hipFree(applied); return r; }
+    if (h->lz.ring) hipFree(h->lz.ring);
+    h->lz.ring = ring;
+    if (applied) h->lz.applied = applied;
+    if (made.bits) h->rl = made;
+    h->lz.window = window; h->lz.base = 0;
     return NTF_OK;
 }
 extern "C" int ntf_n2v_lazy_state(ntf_n2v* h, uint32_t* applied, int64_t* steps, int64_t* flushes) {
     if (!h) return NTF_EINVAL;
-    if (!h->lazy_window) FAIL(h, NTF_ESTATE, "n2v: not a lazy handle (ntf_n2v_set_lazy)");
+    if (!h->lz.window) FAIL(h, NTF_ESTATE, "n2v: not a lazy handle (ntf_n2v_set_lazy)");
     HIPCHK(h, hipSetDevice(h->device));
     if (applied) {
-        HIPCHK(h, hipMemcpyAsync(applied, h->d_applied, (size_t)h->n * 4, hipMemcpyDeviceToHost, h->st));
+        HIPCHK(h, hipMemcpyAsync(applied, h->lz.applied, (size_t)h->n * 4, hipMemcpyDeviceToHost, h->st));
         HIPCHK(h, hipStreamSynchronize(h->st));
     }
     if (steps) *steps = h->adam_t;
-    if (flushes) *flushes = h->lazy_flushes;
+    if (flushes) *flushes = h->lz.flushes;
     return NTF_OK;
 }
 
@@ -730,59 +746,47 @@ static void launch_dense_adam(ntf_n2v* h, float lr) {
     const int blocks = (int)std::min<int64_t>((np / 4 + 255) / 256, 256 * 8);
     hipLaunchKernelGGL(k_n2v_adam, dim3(blocks), dim3(256), 0, h->st, h->W, h->G, h->M1, h->V2, np, lr / (float)c.bc1, (float)c.b1, (float)c.b2, c.eps, (float)std::sqrt(c.bc2));
 }
-// the sparse step: marked rows -> list -> sparse_adam on the listed rows; the marks and the rows of G are clear afterwards
-static void launch_sparse_adam(ntf_n2v* h, float lr) {
+// the sparse step: marked rows -> list (at most `cap` rows) -> sparse_adam on the listed rows; the marks and the rows of G are clear afterwards
+static void launch_sparse_adam(ntf_n2v* h, float lr, int64_t cap) {
     const adam_consts c = adam_at(h->adam_t);
     const float step = (float)((double)lr * std::sqrt(c.bc2) / c.bc1);
-    const int64_t words = (h->n + 31) / 32, cap = std::min<int64_t>(h->n, h->pend_entries);
     if (cap <= 0) return;
-    hipMemsetAsync(h->d_count, 0, 8, h->st);
-    hipLaunchKernelGGL(k_n2v_compact, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, h->st, h->d_touch, words, h->d_list, h->d_count);
-    const dim3 grid((unsigned)std::min<int64_t>((cap + 3) / 4, 256 * 8)), block(256);
+    rowlist_list(h, false);
     with_nv(h->d / 64, [&](auto nv) {
-        hipLaunchKernelGGL(k_n2v_adam_rows<decltype(nv)::value>, grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_list, h->d_count, h->d, step,
+        hipLaunchKernelGGL(k_n2v_adam_rows<decltype(nv)::value>, rowlist_grid(cap), dim3(256), 0, h->st, h->W, h->G, h->M1, h->V2, h->rl.list, h->rl.count, h->d, step,
                            (float)(1.0 - c.b1), (float)(1.0 - c.b2), c.eps);
     });
 }
 
-// ---- lazy dense Adam, host side.  The marked rows as a list of at most `cap` rows (the caller has grown d_list to that); keep: the marks stay
-static void lazy_list(ntf_n2v* h, bool keep) {
-    const int64_t words = (h->n + 31) / 32;
-    hipMemsetAsync(h->d_count, 0, 8, h->st);
-    if (keep) hipLaunchKernelGGL(k_n2v_compact_keep, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, h->st, h->d_touch, words, h->d_list, h->d_count);
-    else hipLaunchKernelGGL(k_n2v_compact, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, h->st, h->d_touch, words, h->d_list, h->d_count);
-}
-// the listed rows brought to step adam_t
+// ---- lazy dense Adam, host side.  The listed rows (at most `cap`) brought to step adam_t
 static void lazy_catchup_rows(ntf_n2v* h, int64_t cap) {
     const adam_consts c = adam_at(1);                         // b1, b2 and eps alone: every step's own two constants come from the ring
-    const dim3 grid((unsigned)std::min<int64_t>((std::max<int64_t>(cap, 1) + 3) / 4, 256 * 8)), block(256);
     with_nv(h->d / 64, [&](auto nv) {
-        hipLaunchKernelGGL((k_n2v_catchup_rows<decltype(nv)::value, false>), grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_applied, h->d_ring, (float2*)nullptr,
-                           (uint32_t)h->lazy_window, h->d_list, h->d_count, h->d, (uint32_t)h->adam_t, 0.f, (float)c.b1, (float)c.b2, c.eps, 0.f);
+        hipLaunchKernelGGL((k_n2v_catchup_rows<decltype(nv)::value, false>), rowlist_grid(cap), dim3(256), 0, h->st, h->W, h->G, h->M1, h->V2, h->lz.applied, h->lz.ring,
+                           (float2*)nullptr, (uint32_t)h->lz.window, h->rl.list, h->rl.count, h->d, (uint32_t)h->adam_t, 0.f, (float)c.b1, (float)c.b2, c.eps, 0.f);
     });
 }
 // the full flush: every row to step adam_t, after which the ring is free again.  It reads no mark, so a pending gradient's marks survive it
 static void lazy_flush(ntf_n2v* h) {
-    if (h->adam_t == h->lazy_base) return;                   // every row is there already
+    if (h->adam_t == h->lz.base) return;                     // every row is there already
     const adam_consts c = adam_at(1);                         // b1, b2 and eps alone: every step's own two constants come from the ring
     const dim3 grid((unsigned)std::min<int64_t>((h->n + 3) / 4, 256 * 32)), block(256);
     with_nv(h->d / 64, [&](auto nv) {
-        hipLaunchKernelGGL(k_n2v_catchup_all<decltype(nv)::value>, grid, block, 0, h->st, h->W, h->M1, h->V2, h->d_applied, h->d_ring, (uint32_t)h->lazy_window, h->n, h->d,
+        hipLaunchKernelGGL(k_n2v_catchup_all<decltype(nv)::value>, grid, block, 0, h->st, h->W, h->M1, h->V2, h->lz.applied, h->lz.ring, (uint32_t)h->lz.window, h->n, h->d,
                            (uint32_t)h->adam_t, (float)c.b1, (float)c.b2, c.eps);
     });
-    h->lazy_base = h->adam_t; h->lazy_flushes += 1;
+    h->lz.base = h->adam_t; h->lz.flushes += 1;
 }
 // the step of the batch on the listed rows (already at adam_t - 1, the step before): k_n2v_adam's two constants, rounded as launch_dense_adam rounds them, go to
 // the kernel and from its first lane into the ring (the caller has made room in it).  G and the marks are clear afterwards
 static void launch_lazy_adam(ntf_n2v* h, float lr, int64_t cap) {
     const adam_consts c = adam_at(h->adam_t);
-    const dim3 grid((unsigned)std::min<int64_t>((std::max<int64_t>(cap, 1) + 3) / 4, 256 * 8)), block(256);
     with_nv(h->d / 64, [&](auto nv) {
-        hipLaunchKernelGGL((k_n2v_catchup_rows<decltype(nv)::value, true>), grid, block, 0, h->st, h->W, h->G, h->M1, h->V2, h->d_applied, h->d_ring,
-                           h->d_ring + h->adam_t % h->lazy_window, (uint32_t)h->lazy_window, h->d_list, h->d_count, h->d, (uint32_t)(h->adam_t - 1),
+        hipLaunchKernelGGL((k_n2v_catchup_rows<decltype(nv)::value, true>), rowlist_grid(cap), dim3(256), 0, h->st, h->W, h->G, h->M1, h->V2, h->lz.applied, h->lz.ring,
+                           h->lz.ring + h->adam_t % h->lz.window, (uint32_t)h->lz.window, h->rl.list, h->rl.count, h->d, (uint32_t)(h->adam_t - 1),
                            lr / (float)c.bc1, (float)c.b1, (float)c.b2, c.eps, (float)std::sqrt(c.bc2));
     });
-    hipMemsetAsync(h->d_touch, 0, (size_t)((h->n + 31) / 32) * 4, h->st);
+    hipMemsetAsync(h->rl.bits, 0, (size_t)rowlist_words(h) * 4, h->st);
 }
 
 static void launch_pairs(ntf_n2v* h, const int64_t* rows, int64_t n_rows, int ctx, int positive) {
@@ -795,6 +799,32 @@ static void launch_pairs(ntf_n2v* h, const int64_t* rows, int64_t n_rows, int ct
         if (h->dummy_pairs) hipLaunchKernelGGL((k_n2v_pairs<NV, true>), grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss);
         else hipLaunchKernelGGL((k_n2v_pairs<NV, false>), grid, block, 0, h->st, h->W, rows, n_rows, ctx, h->d, inv, positive, dummy, h->G, h->d_loss);
     });
+}
+
+// the window rows of a native batch: walks, negatives and both window launches into the scratch [pos walks | neg walks | pos windows | neg windows]; *win = the positive
+// windows, the negative ones right behind.  pairs_now (dense): each sign's pairs behind its window launch - behind both, n2v measured slower (profiles/n2v_step_paths_check.md)
+static int make_windows(ntf_n2v* h, int64_t B, int64_t pw, int64_t ng, int wl, int ctx, uint64_t step, bool pairs_now, const int64_t** win) {
+    const int nw = wl + 1 - ctx;
+    if (int r = need_rows(h, (pw + ng) * wl + (pw + ng) * nw * ctx)) return r;
+    int64_t *rw_p = h->d_rows, *rw_n = rw_p + pw * wl, *win_p = rw_n + ng * wl, *win_n = win_p + pw * nw * ctx;
+    launch_walks(h, B, pw, wl, step, rw_p);
+    hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((pw * nw * ctx + 255) / 256)), dim3(256), 0, h->st, rw_p, pw, wl, ctx, win_p);
+    if (pairs_now) launch_pairs(h, win_p, pw * nw, ctx, 1);
+    if (ng) {
+        launch_negs(h, B, ng, wl, step, rw_n);
+        hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((ng * nw * ctx + 255) / 256)), dim3(256), 0, h->st, rw_n, ng, wl, ctx, win_n);
+        if (pairs_now) launch_pairs(h, win_n, ng * nw, ctx, 0);
+    }
+    *win = win_p;
+    return NTF_OK;
+}
+// the window rows of an injected call (the parity tests give them): the two uploads into the scratch the caller has sized
+static int upload_windows(ntf_n2v* h, const int64_t* pos, int64_t n_pos, const int64_t* neg, int64_t n_neg, int ctx, const int64_t** win) {
+    if (n_pos) HIPCHK(h, hipMemcpyAsync(h->d_rows, pos, n_pos * ctx * 8, hipMemcpyHostToDevice, h->st));
+    if (n_neg) HIPCHK(h, hipMemcpyAsync(h->d_rows + n_pos * ctx, neg, n_neg * ctx * 8, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    *win = h->d_rows;
+    return NTF_OK;
 }
 
 extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, int32_t walk_length, int32_t context, int32_t walks_per_node, int32_t num_neg,
@@ -815,60 +845,29 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
         if (m2v_too_long(h, walk_length)) FAIL(h, NTF_EINVAL, "m2v: a walk longer than the metapath needs a metapath that ends on its start type");
         if ((r = stage_batch(h, batch, B))) return r;
     }
-    // the window entries of this call: what k_n2v_touch runs over, and with the pending ones the bound of the row list
-    const int64_t entries = injected ? (n_pos + n_neg) * context : (int64_t)B * walks_per_node * (1 + (int64_t)num_neg) * (walk_length + 1 - context) * context;
-    const bool lazy = h->lazy_window > 0;                    // the dense and the sparse path below are what they were; the lazy one defers the pairs
-    if (lazy && apply && h->adam_t >= 0xFFFFFFFFll) FAIL(h, NTF_ESTATE, "n2v: the step count of a lazy handle no longer fits its per-row counter (uint32)");
-    if ((h->opt == 1 || lazy) && (r = dev_grow(h, &h->d_list, &h->list_cap, std::min<int64_t>(h->n, h->pend_entries + entries)))) return r;
+    // the window rows of this call, positive and negative, and their entries: what k_n2v_touch runs over, and with the pending ones the bound of the row list
+    const int64_t pw = (int64_t)B * walks_per_node, ng = pw * num_neg;
+    const int64_t n_p = injected ? n_pos : pw * (walk_length + 1 - context), n_n = injected ? n_neg : ng * (walk_length + 1 - context), entries = (n_p + n_n) * context;
+    const n2v_mode m = mode(h);
+    if (m == N2V_LAZY && apply && h->adam_t >= 0xFFFFFFFFll) FAIL(h, NTF_ESTATE, "n2v: the step count of a lazy handle no longer fits its per-row counter (uint32)");
+    if (m != N2V_DENSE && (r = dev_grow(h, &h->rl.list, &h->rl.cap, std::min<int64_t>(h->n, h->pend_entries + entries)))) return r;
     HIPCHK(h, hipMemsetAsync(h->d_loss, 0, 8, h->st));
     const uint64_t step = h->step++;
-    if (injected) {
-        if (n_pos) HIPCHK(h, hipMemcpyAsync(h->d_rows, inj_pos, n_pos * context * 8, hipMemcpyHostToDevice, h->st));
-        if (n_neg) HIPCHK(h, hipMemcpyAsync(h->d_rows + n_pos * context, inj_neg, n_neg * context * 8, hipMemcpyHostToDevice, h->st));
-        HIPCHK(h, hipStreamSynchronize(h->st));
-        if (!lazy) {
-            launch_pairs(h, h->d_rows, n_pos, context, 1);
-            launch_pairs(h, h->d_rows + n_pos * context, n_neg, context, 0);
-        }
-        h->win_p = h->d_rows; h->win_n = h->d_rows + n_pos * context; h->n_win_p = n_pos; h->n_win_n = n_neg;
-    } else {
-        const int nw = walk_length + 1 - context;
-        const int64_t pw = (int64_t)B * walks_per_node, ng = pw * num_neg;
-        // scratch: [pos walks | neg walks | pos windows | neg windows]
-        if ((r = need_rows(h, (pw + ng) * walk_length + (pw + ng) * nw * context))) return r;
-        int64_t* rw_p = h->d_rows; int64_t* rw_n = rw_p + pw * walk_length;
-        int64_t* win_p = rw_n + ng * walk_length; int64_t* win_n = win_p + pw * nw * context;
-        launch_walks(h, B, pw, walk_length, step, rw_p);
-        hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((pw * nw * context + 255) / 256)), dim3(256), 0, h->st, rw_p, pw, walk_length, context, win_p);
-        if (!lazy) launch_pairs(h, win_p, pw * nw, context, 1);
-        if (ng) {
-            launch_negs(h, B, ng, walk_length, step, rw_n);
-            hipLaunchKernelGGL(k_n2v_windows, dim3((unsigned)((ng * nw * context + 255) / 256)), dim3(256), 0, h->st, rw_n, ng, walk_length, context, win_n);
-            if (!lazy) launch_pairs(h, win_n, ng * nw, context, 0);
-        }
-        h->win_p = win_p; h->win_n = win_n; h->n_win_p = pw * nw; h->n_win_n = ng * nw;
-    }
-    h->win_ctx = context;
+    const int64_t* win = nullptr;                            // windows: positive rows, then negative rows, back to back from `win` on
+    const bool pairs_now = !injected && m == N2V_DENSE;      // make_windows has launched the pairs already
+    if ((r = injected ? upload_windows(h, inj_pos, n_pos, inj_neg, n_neg, context, &win) : make_windows(h, B, pw, ng, walk_length, context, step, pairs_now, &win))) return r;
+    h->win_p = win; h->win_n = win + n_p * context; h->n_win_p = n_p; h->n_win_n = n_n; h->win_ctx = context;
+    // accumulate.  The pairs read W only at the rows the windows name, so a lazy handle first lists the marked rows - with those earlier apply = 0 calls marked
+    // (current already: an empty loop) - and brings them to adam_t
     h->pend_entries += entries;
-    const int64_t lazy_cap = std::min<int64_t>(h->n, h->pend_entries);
-    if (lazy) {
-        // the pairs read W only at the rows the windows name: mark them, list them with the rows earlier apply = 0 calls marked (current already: an empty loop),
-        // bring them to adam_t, and only then run the pairs - in the order the dense path launches them
-        if (entries > 0) hipLaunchKernelGGL(k_n2v_touch, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, h->st, h->win_p, entries,
-                                            h->m2v ? h->mp.total : (int64_t)-1, h->d_touch);
-        lazy_list(h, true);
-        lazy_catchup_rows(h, lazy_cap);
-        launch_pairs(h, h->win_p, h->n_win_p, context, 1);
-        launch_pairs(h, h->win_n, h->n_win_n, context, 0);
-    }
-    // sparse mode: the positive and the negative window rows lie back to back from win_p on, `entries` ids in all
-    if (h->opt == 1 && entries > 0) hipLaunchKernelGGL(k_n2v_touch, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, h->st, h->win_p, entries,
-                                                       h->m2v ? h->mp.total : (int64_t)-1, h->d_touch);
+    const int64_t cap = std::min<int64_t>(h->n, h->pend_entries);
+    if (m != N2V_DENSE) rowlist_mark(h, win, entries, h->m2v ? h->mp.total : (int64_t)-1);
+    if (m == N2V_LAZY) { rowlist_list(h, true); lazy_catchup_rows(h, cap); }
+    if (!pairs_now) { launch_pairs(h, h->win_p, n_p, context, 1); launch_pairs(h, h->win_n, n_n, context, 0); }
     if (apply) {
-        if (lazy && h->adam_t - h->lazy_base == h->lazy_window) lazy_flush(h);       // the ring is full: every row to adam_t, and its slots are free
+        if (m == N2V_LAZY && h->adam_t - h->lz.base == h->lz.window) lazy_flush(h);  // the ring is full: every row to adam_t, and its slots are free
         h->adam_t += 1;
-        if (lazy) launch_lazy_adam(h, lr, lazy_cap);
-        else if (h->opt == 1) launch_sparse_adam(h, lr); else launch_dense_adam(h, lr);
+        if (m == N2V_LAZY) launch_lazy_adam(h, lr, cap); else if (m == N2V_SPARSE) launch_sparse_adam(h, lr, cap); else launch_dense_adam(h, lr);
         h->pend_entries = 0;
     }
     if (loss_out) {
@@ -885,12 +884,12 @@ extern "C" int ntf_n2v_train_batch(ntf_n2v* h, const int64_t* batch, int32_t B, 
 extern "C" int ntf_n2v_get(ntf_n2v* h, int what, float* host) {   // what: 0 = embedding.weight, 1 = its gradient (as the last batch with apply = 0 left it)
     if (!h || !host || what < 0 || what > 1) return NTF_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->lazy_window && what == 0) lazy_flush(h);          // the table a reader sees is dense Adam's at step adam_t
+    if (h->lz.window && what == 0) lazy_flush(h);         // the table a reader sees is dense Adam's at step adam_t
     HIPCHK(h, hipStreamSynchronize(h->st));
     HIPCHK(h, hipMemcpy2D(host, (size_t)h->d_user * 4, what ? h->G : h->W, (size_t)h->d * 4, (size_t)h->d_user * 4, (size_t)h->n, hipMemcpyDeviceToHost));
     if (what) {   // reading the gradient consumes it, and with it the marks of the rows it named
         HIPCHK(h, hipMemsetAsync(h->G, 0, (size_t)h->n * h->d * 4, h->st));
-        if (h->d_touch) HIPCHK(h, hipMemsetAsync(h->d_touch, 0, (size_t)((h->n + 31) / 32) * 4, h->st));
+        if (h->rl.bits) HIPCHK(h, hipMemsetAsync(h->rl.bits, 0, (size_t)rowlist_words(h) * 4, h->st));
         h->pend_entries = 0;
     }
     return NTF_OK;
@@ -899,7 +898,7 @@ extern "C" int ntf_n2v_get(ntf_n2v* h, int what, float* host) {   // what: 0 = e
 extern "C" int ntf_n2v_moments(ntf_n2v* h, float* exp_avg, float* exp_avg_sq) {   // Adam's two moments [num_nodes, d], either may be NULL; reads only
     if (!h) return NTF_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->lazy_window) lazy_flush(h);
+    if (h->lz.window) lazy_flush(h);
     HIPCHK(h, hipStreamSynchronize(h->st));
     const size_t row = (size_t)h->d_user * 4;
     if (exp_avg) HIPCHK(h, hipMemcpy2D(exp_avg, row, h->M1, (size_t)h->d * 4, row, (size_t)h->n, hipMemcpyDeviceToHost));
@@ -923,15 +922,16 @@ extern "C" int ntf_n2v_edge_bce(ntf_n2v* h, const int64_t* src, const int64_t* d
     HIPCHK(h, hipSetDevice(h->device));
     for (int64_t i = 0; i < n; ++i) if (src[i] < 0 || src[i] >= h->n || dst[i] < 0 || dst[i] >= h->n) FAIL(h, NTF_EINVAL, "n2v: edge endpoint out of range");
     int r = need_rows(h, 2 * n); if (r) return r;
-    const bool lazy_rows = h->lazy_window > 0 && h->pend_entries == 0;     // no gradient pending: the bitmap is free for the endpoints
-    if (lazy_rows && (r = dev_grow(h, &h->d_list, &h->list_cap, std::min<int64_t>(h->n, 2 * n)))) return r;
+    const int64_t cap = std::min<int64_t>(h->n, 2 * n);
+    const bool lazy_rows = h->lz.window > 0 && h->pend_entries == 0;       // no gradient pending: the bitmap is free for the endpoints
+    if (lazy_rows && (r = dev_grow(h, &h->rl.list, &h->rl.cap, cap))) return r;
     HIPCHK(h, hipMemcpyAsync(h->d_rows, src, n * 8, hipMemcpyHostToDevice, h->st));
     HIPCHK(h, hipMemcpyAsync(h->d_rows + n, dst, n * 8, hipMemcpyHostToDevice, h->st));
     if (lazy_rows) {                                        // only the rows read are brought to adam_t
-        hipLaunchKernelGGL(k_n2v_touch, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, h->st, h->d_rows, 2 * n, (int64_t)-1, h->d_touch);
-        lazy_list(h, false);
-        lazy_catchup_rows(h, std::min<int64_t>(h->n, 2 * n));
-    } else if (h->lazy_window) lazy_flush(h);               // a gradient is pending and its marks must survive: the full flush reads none
+        rowlist_mark(h, h->d_rows, 2 * n, -1);
+        rowlist_list(h, false);
+        lazy_catchup_rows(h, cap);
+    } else if (h->lz.window) lazy_flush(h);                 // a gradient is pending and its marks must survive: the full flush reads none
     HIPCHK(h, hipMemsetAsync(h->d_loss + 1, 0, 8, h->st));
     hipLaunchKernelGGL(k_n2v_edge_bce, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->st, h->W, h->d_rows, h->d_rows + n, n, h->d, h->d_loss + 1);
     double l = 0;

@@ -726,11 +726,15 @@ class Node2Vec(_Handle):
         if len(self.rowptr) != self.num_nodes + 1:
             raise NtfError("rowptr must have num_nodes + 1 entries")
         self._create(int(device), self.num_nodes, self.d, _ptr(self.rowptr), _ptr(self.col), _ptr(w), int(seed) & (2**64 - 1))
-        self.sparse = False; self.lazy = 0
         self.p, self.q = 1.0, 1.0
+        self._choose_optimizer(sparse, lazy)
+        if float(p) != 1.0 or float(q) != 1.0: self.set_walk_bias(p, q)
+
+    def _choose_optimizer(self, sparse, lazy):
+        """the tail of both constructors: dense Adam unless one of the two opt-in modes is asked for"""
+        self.sparse = False; self.lazy = 0
         if sparse: self.set_optimizer(True)
         if lazy: self.set_lazy(lazy)
-        if float(p) != 1.0 or float(q) != 1.0: self.set_walk_bias(p, q)
 
     def set_walk_bias(self, p, q):
         """node2vec's p (return) and q (in-out), each in [1e-4, 1e4]; (1, 1) is the uniform walk again.  Any time: walks carry no state between calls.  Refused on a
@@ -826,9 +830,7 @@ class MetaPath2Vec(Node2Vec):
         rps = (C.c_void_p * max(len(hops), 1))(*[a.ctypes.data for a in self._rowptr])
         cls = (C.c_void_p * max(len(hops), 1))(*[a.ctypes.data if a.size else None for a in self._col])
         self._create(int(device), len(tc), _ptr(tc), len(hops), _ptr(hs), _ptr(hd), rps, cls, self.d, _ptr(w), int(seed) & (2**64 - 1))
-        self.sparse = False; self.lazy = 0
-        if sparse: self.set_optimizer(True)
-        if lazy: self.set_lazy(lazy)
+        self._choose_optimizer(sparse, lazy)
 
 
 class Doc2Vec(_Handle):

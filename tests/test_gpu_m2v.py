@@ -18,7 +18,7 @@ import torch
 
 import m2v_reference as R
 import test_gpu_n2v_parity as P
-from conftest import golden
+from n2v_reference import Cfg, toy_dblp
 from opentf_amd.synth import zipf_csr
 
 pytestmark = pytest.mark.gpu
@@ -300,19 +300,8 @@ def test_refusals_change_nothing():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the plugin
-class Cfg(dict):
-    def __getattr__(self, k):
-        if k.startswith("__"): raise AttributeError(k)
-        return self.get(k)
-
-
 def _toy():
-    toy = golden("toy_dblp")
-    n, S, M = [int(v) for v in toy["shape"]]
-    skill = scipy.sparse.csr_matrix((np.ones(len(toy["skill_indices"]), np.uint8), toy["skill_indices"], toy["skill_indptr"]), shape=(n, S)).tolil()
-    member = scipy.sparse.csr_matrix((np.ones(len(toy["member_indices"]), np.uint8), toy["member_indices"], toy["member_indptr"]), shape=(n, M)).tolil()
-    splits = {"test": toy["test"], "folds": {k: {"train": toy[f"train{k}"], "valid": toy[f"valid{k}"]} for k in range(3)}}
-    return {"skill": skill, "member": member, "loc": None}, splits, n, S, M
+    return toy_dblp()[1:]
 
 
 def test_gnn_m2v_plugin_on_toy_dblp(tmp_path):

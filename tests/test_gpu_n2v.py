@@ -10,24 +10,10 @@ import scipy.sparse
 import torch
 
 from conftest import golden
+from n2v_reference import Cfg, toy_dblp as _toy
 from oracle import n2v_oracle as N
 
 pytestmark = pytest.mark.gpu
-
-
-class Cfg(dict):
-    def __getattr__(self, k):
-        if k.startswith("__"): raise AttributeError(k)
-        return self.get(k)
-
-
-def _toy():
-    toy = golden("toy_dblp")
-    n, S, M = [int(v) for v in toy["shape"]]
-    skill = scipy.sparse.csr_matrix((np.ones(len(toy["skill_indices"]), np.uint8), toy["skill_indices"], toy["skill_indptr"]), shape=(n, S)).tolil()
-    member = scipy.sparse.csr_matrix((np.ones(len(toy["member_indices"]), np.uint8), toy["member_indices"], toy["member_indptr"]), shape=(n, M)).tolil()
-    splits = {"test": toy["test"], "folds": {k: {"train": toy[f"train{k}"], "valid": toy[f"valid{k}"]} for k in range(3)}}
-    return toy, {"skill": skill, "member": member, "loc": None}, splits, n, S, M
 
 
 @pytest.mark.parametrize("d", [9, 64, 100, 128, 256])      # 9, 100 (round 6): sizes that are not a multiple of a wave's 64 lanes - device rows are padded, the pad stays zero

@@ -1,4 +1,4 @@
-"""Lazy dense Adam of the node2vec / metapath2vec producers (ntf_n2v_set_lazy: k_n2v_touch -> k_n2v_compact_keep -> k_n2v_catchup_rows before the pairs,
+"""Lazy dense Adam of the node2vec / metapath2vec producers (ntf_n2v_set_lazy: k_n2v_touch -> k_n2v_compact<false> -> k_n2v_catchup_rows before the pairs,
 k_n2v_catchup_rows<.., true> after them, k_n2v_catchup_all for a full flush; opentf_amd/csrc/ntf_n2v.hip).
 
 The claim: the table of dense Adam, bit for bit given bit-identical gradients, while a step writes only the rows its windows name.  So the tests hold a lazy
@@ -16,7 +16,9 @@ import numpy as np
 import pytest
 import torch
 
+import n2v_reference
 import test_gpu_n2v_parity as P
+from n2v_reference import bits, net as _net
 
 pytestmark = pytest.mark.gpu
 
@@ -24,10 +26,7 @@ LR = 0.01
 SIZES = [1, 65, 192, 193]            # NV 1 to 4; a pad column at three of them (256 leaves out 1.06e-3 of the elements, over the cap)
 BIT_SIZES = [65, 193]
 DEFAULT_WINDOW = 4096
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+within_bar = functools.partial(n2v_reference.within_bar, "lazy")
 
 
 # ---------------------------------------------------------------------------------------------------------------- the two-term sequence
@@ -105,13 +104,6 @@ def five_steps(d):
     return out
 
 
-def within_bar(Wd, Wref, compare, tag):
-    err = np.abs(Wd.astype(np.float64) - Wref); tol = 2e-5 + 1e-4 * np.abs(Wref)
-    worst = float((err / tol)[compare].max()) if compare.any() else 0.0
-    print(f"n2v lazy adam {tag}: max |W - ref| / tol over the compared elements {worst:.3f}, left out {int((~compare).sum())} of {compare.size}")
-    assert (err <= tol)[compare].all(), (tag, worst)
-
-
 def native_sets_replayed():
     """three native batches of (97, 9, 4, 3, 2) of a handle of seed NATIVE_SEED, replayed on the host"""
     rp, col, nn, _ = P.graph()
@@ -138,12 +130,6 @@ def bce64(W, src, dst):
 
 
 # ================================================================================================================ the GPU tests
-def _net(W, lazy=False, seed=0):
-    from opentf_amd.libntf import Node2Vec
-    rp, col, nn, _ = P.graph()
-    return Node2Vec(rp, col, W, seed=seed, lazy=lazy)
-
-
 def _same_bits(lazy, dense, tag):
     Wl, Wd = lazy.weight(), dense.weight()
     (ml, vl), (md, vd) = lazy.moments(), dense.moments()

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import n2v_reference as R
 from opentf_amd.synth import zipf_csr
 from oracle import n2v_oracle as N
 from oracle.d2v_oracle import philox4x32
@@ -294,6 +295,20 @@ def contract_case():
     return b, (wl, ctx, wpn, nneg), (p0, n0), (pos[:301], neg[:602])
 
 
+CORNER_D, CORNER_START_SEED = 65, 0
+
+
+@functools.lru_cache(None)
+def corner_cases():
+    """the corners of the one step that every optimiser runs: (a) a native batch without negatives - the hub and two drawn start nodes, walk length 4,
+    context 3, two walks per node - replayed as step 0 of a handle of seed NATIVE_SEED; (b) injected rows without positives: two negative rows of (a) above.
+    -> start nodes, (walk length, context, walks per node), the replayed positive windows, the two negative rows"""
+    rp, col, nn, _ = graph()
+    b, (wl, ctx, wpn) = start_nodes(8, CORNER_START_SEED)[5:], (4, 3, 2)
+    pos = N.windows(torch.from_numpy(replay_walks(rp, col, b, len(b) * wpn, wl, NATIVE_SEED, 0)), ctx).numpy()
+    return b, (wl, ctx, wpn), pos, injected_case()[1][:2]
+
+
 # ---------------------------------------------------------------------------------------------------------------- edge BCE
 def edge_case(d, n):
     """table of the regime above with three hand-built rows (dots of exactly +30 and -30), n pairs: the two hand-built ones, a self-pair, then drawn"""
@@ -310,12 +325,6 @@ def edge_case(d, n):
 
 
 # ================================================================================================================ the GPU tests
-def _net(W, seed=0):
-    from opentf_amd.libntf import Node2Vec
-    rp, col, nn, _ = graph()
-    return Node2Vec(rp, col, W, seed=seed)
-
-
 def _step(net, W, pos, neg, tag):
     ref = ref_batch(W, pos, neg)
     assert conditions_hold(ref)
@@ -326,7 +335,7 @@ def _step(net, W, pos, neg, tag):
 @pytest.mark.parametrize("d", SIZES)
 def test_injected_windows_match_float64_element_by_element(d):
     W = table(d)
-    net = _net(W)
+    net = R.net(W)
     _step(net, W, *injected_case(), f"d={d} injected")
     for k, (pos, neg) in enumerate(single_row_cases()):
         _step(net, W, pos, neg, f"d={d} {'one positive row' if k == 0 else 'one negative row'}")
@@ -393,7 +402,7 @@ def test_native_batches_replay_from_the_philox_counters(d):
     from opentf_amd.libntf import NTF_EINVAL, NtfError
     rp, col, nn, _ = graph()
     W = table(d)
-    net = _net(W, seed=NATIVE_SEED)
+    net = R.net(W, seed=NATIVE_SEED)
     for t, (B, wl, ctx, wpn, nneg) in enumerate(NATIVE_STEPS):
         batch, rw, pos, neg = replay_step(t)
         ref = ref_batch(W, pos, neg)
@@ -409,6 +418,25 @@ def test_native_batches_replay_from_the_philox_counters(d):
     assert np.array_equal(net.weight(), W)
 
 
+@pytest.mark.parametrize("mode", ["dense", "sparse", "lazy"])
+def test_a_batch_without_negatives_and_injected_rows_without_positives(mode):
+    """the step's stages are shared by the three optimisers: an empty side must launch nothing and mark nothing in each of them, with the bars of (a)"""
+    W = table(CORNER_D)
+    batch, (wl, ctx, wpn), pos, neg = corner_cases()
+    ra, rb = ref_batch(W, pos, np.zeros((0, ctx), np.int64)), ref_batch(W, neg[:0], neg)
+    assert conditions_hold(ra) and conditions_hold(rb) and len(batch) == 3 and len(neg) == 2
+    net = R.net(W, seed=NATIVE_SEED, **{"dense": {}, "sparse": {"sparse": True}, "lazy": {"lazy": True}}[mode])
+    loss = net.train_batch(batch, wl, ctx, wpn, 0, 0.0, apply=False)
+    got_pos, got_neg = net.last_windows()
+    assert np.array_equal(got_pos, pos) and got_neg.shape == (0, ctx)
+    parity(loss, net.grad(), ra, f"d={CORNER_D} {mode} native batch without negatives")
+    loss = net.loss_on(neg[:0], neg, apply=False)
+    got_pos, got_neg = net.last_windows()
+    assert got_pos.shape == (0, neg.shape[1]) and np.array_equal(got_neg, neg)
+    parity(loss, net.grad(), rb, f"d={CORNER_D} {mode} injected rows without positives")
+    assert np.array_equal(net.weight(), W)
+
+
 @pytest.mark.parametrize("d", ADAM_SIZES)
 def test_adam_over_steps_that_name_different_rows(d):
     W0 = table(d)
@@ -416,7 +444,7 @@ def test_adam_over_steps_that_name_different_rows(d):
     Wref, refs, compare, named = adam_reference(W0, sets)
     assert (~compare).mean() <= 1e-3 and all(conditions_hold(r) for r in refs)
     assert (~named).sum() >= 5 and all(((r["K"] > 0) != named).any() for r in refs)
-    net = _net(W0)
+    net = R.net(W0)
     for pos, neg in sets: net.loss_on(pos, neg, lr=0.01, apply=True)
     Wd = net.weight()
     assert np.array_equal(Wd[~named].view(np.uint32), W0[~named].view(np.uint32))           # rows no window ever names: bit for bit
@@ -431,7 +459,7 @@ def test_adam_over_steps_that_name_different_rows(d):
 @pytest.mark.parametrize("n", [1, 5, 1001])
 def test_edge_bce_matches_float64(d, n):
     W, src, dst, ref = edge_case(d, n)
-    got = _net(W).edge_bce(src, dst)
+    got = R.net(W).edge_bce(src, dst)
     print(f"n2v edge_bce d={d} n={n}: {got:.8f} ref {ref:.8f} rel {abs(got - ref) / ref:.2e}")
     assert abs(got - ref) <= 1e-6 * ref
 
@@ -445,7 +473,7 @@ def test_refusals_change_nothing_and_gradients_of_unread_calls_add():
     for kw in ({"W": np.zeros((nn, 0), np.float32)}, {"W": np.zeros((nn, 257), np.float32)}, {"rp": down},
                {"col": np.where(np.arange(len(col)) == 5, nn, col).astype(np.int32)}):
         with pytest.raises(NtfError, match=rf"failed \({NTF_EINVAL}\)"): Node2Vec(kw.get("rp", rp), kw.get("col", col), kw.get("W", W))
-    net = _net(W, seed=CONTRACT_SEED)
+    net = R.net(W, seed=CONTRACT_SEED)
     pos, neg = injected_case()
     batch = start_nodes(33)
     bad = batch.copy(); bad[3] = -1

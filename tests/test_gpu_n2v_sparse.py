@@ -18,9 +18,12 @@ import pytest
 import scipy.sparse
 import torch
 
+import n2v_reference
 import test_gpu_n2v_parity as P
+from n2v_reference import bits, net
 
 pytestmark = pytest.mark.gpu
+within_bar = functools.partial(n2v_reference.within_bar, "sparse")
 
 U = P.U
 B1, B2, EPS = 0.9, 0.999, 1e-8
@@ -58,19 +61,6 @@ def five_steps(d):
     out = sparse_adam_reference(P.table(d), P.adam_window_sets())
     for a in out[:3] + out[4:]: a.setflags(write=False)
     return out
-
-
-def within_bar(Wd, Wref, compare, tag):
-    """the bar of test_adam_over_steps_that_name_different_rows on the compared elements; prints the largest err / tol"""
-    err = np.abs(Wd.astype(np.float64) - Wref); tol = 2e-5 + 1e-4 * np.abs(Wref)
-    worst = float((err / tol)[compare].max()) if compare.any() else 0.0
-    print(f"n2v sparse adam {tag}: max |W - ref| / tol over the compared elements {worst:.3f}, left out {int((~compare).sum())} of {compare.size}")
-    assert (err <= tol)[compare].all(), (tag, worst)
-    return worst
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @functools.lru_cache(None)
@@ -120,10 +110,7 @@ def boundary_case():
 
 
 # ================================================================================================================ the GPU tests
-def _net(W, seed=0, sparse=True):
-    from opentf_amd.libntf import Node2Vec
-    rp, col, nn, _ = P.graph()
-    return Node2Vec(rp, col, W, seed=seed, sparse=sparse)
+_net = functools.partial(net, sparse=True)
 
 
 @pytest.mark.parametrize("d", SIZES)

@@ -7,6 +7,7 @@ import pytest
 from scipy.stats import chi2
 
 import n2v_bias_reference as R
+from n2v_reference import plugin_cfg as _cfg
 
 
 def test_thresholds():
@@ -64,19 +65,6 @@ def test_p_q_one_is_the_uniform_distribution_over_entries():
     for x1 in col[rp[0]:rp[1]]:
         row = col[rp[x1]:rp[x1 + 1]]
         assert np.allclose(P[x1, row], 1.0 / 14 / len(row))
-
-
-class Cfg(dict):
-    def __getattr__(self, k):
-        if k.startswith("__"): raise AttributeError(k)
-        return self.get(k)
-
-
-def _cfg(method, **kw):
-    sec = Cfg(d=16, w=3, e=4, b=16, lr=0.01, es=5, ns=2, spe=2, wl=5, wn=3, **kw)
-    if method == "m2v":
-        sec["metapath_name"] = [[["member", "to", "team"], ["team", "rev_to", "skill"], ["skill", "to", "team"], ["team", "rev_to", "member"]], "mtstm"]
-    return Cfg(graph=Cfg(structure=[[["skill", "to", "team"], ["member", "to", "team"]], "stm"], dup_edge="add", pre=None), **{method: sec})
 
 
 def test_the_directory_name_takes_the_bias_only_when_it_is_not_one(tmp_path):

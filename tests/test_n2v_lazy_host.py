@@ -9,14 +9,7 @@ import torch
 
 import test_gpu_n2v_lazy as L
 import test_gpu_n2v_parity as P
-
-
-@pytest.fixture(autouse=True)
-def _global_generators_left_as_found():
-    import random
-    t, n, r = torch.get_rng_state(), np.random.get_state(), random.getstate()
-    yield
-    torch.set_rng_state(t); np.random.set_state(n); random.setstate(r)
+from n2v_reference import global_generators_left_as_found, plugin_cfg as _cfg      # the fixture: autouse
 
 
 def test_the_two_entries_are_declared_and_bound():
@@ -28,19 +21,6 @@ def test_the_two_entries_are_declared_and_bound():
         assert inspect.signature(cls.__init__).parameters["lazy"].default is False
         assert callable(cls.set_lazy) and callable(cls.lazy_state)
     assert libntf.Node2Vec.LAZY_WINDOW == L.DEFAULT_WINDOW == 4096
-
-
-class Cfg(dict):
-    def __getattr__(self, k):
-        if k.startswith("__"): raise AttributeError(k)
-        return self.get(k)
-
-
-def _cfg(method, **kw):
-    sec = Cfg(d=16, w=3, e=4, b=16, lr=0.01, es=5, ns=2, spe=2, wl=5, wn=3, **kw)
-    if method == "m2v":
-        sec["metapath_name"] = [[["member", "to", "team"], ["team", "rev_to", "skill"], ["skill", "to", "team"], ["team", "rev_to", "member"]], "mtstm"]
-    return Cfg(graph=Cfg(structure=[[["skill", "to", "team"], ["member", "to", "team"]], "stm"], dup_edge="add", pre=None), **{method: sec})
 
 
 @pytest.mark.parametrize("method", ["n2v", "m2v"])

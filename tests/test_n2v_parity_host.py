@@ -5,15 +5,8 @@ import pytest
 import torch
 
 import test_gpu_n2v_parity as P
+from n2v_reference import global_generators_left_as_found      # the fixture: autouse
 from oracle import n2v_oracle as N
-
-
-@pytest.fixture(autouse=True)
-def _global_generators_left_as_found():
-    import random
-    t, n, r = torch.get_rng_state(), np.random.get_state(), random.getstate()
-    yield
-    torch.set_rng_state(t); np.random.set_state(n); random.setstate(r)
 
 
 def _autograd(W, pos, neg, dtype):
@@ -115,6 +108,14 @@ def test_the_adam_case_stays_under_its_cap(d):
     for pos, neg in P.adam_window_sets():
         opt.zero_grad(); N.loss(emb, torch.from_numpy(np.array(pos)), torch.from_numpy(np.array(neg))).backward(); opt.step()
     assert np.abs(emb.detach().numpy() - W).max() <= 1e-9
+
+
+def test_the_corner_cases_meet_their_conditions():
+    batch, (wl, ctx, wpn), pos, neg = P.corner_cases()
+    rp, col, nn, sp = P.graph()
+    assert len(batch) == len(set(batch.tolist())) == 3 and batch[0] == sp["hub"] and pos.shape == (len(batch) * wpn * (wl + 1 - ctx), ctx) and neg.shape == (2, 4)
+    W = P.table(P.CORNER_D)
+    assert P.conditions_hold(P.ref_batch(W, pos, np.zeros((0, ctx), np.int64))) and P.conditions_hold(P.ref_batch(W, neg[:0], neg))
 
 
 def test_the_saturation_table_keeps_clear_of_the_undefined_band():

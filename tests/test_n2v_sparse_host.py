@@ -6,14 +6,7 @@ import torch
 
 import test_gpu_n2v_parity as P
 import test_gpu_n2v_sparse as S
-
-
-@pytest.fixture(autouse=True)
-def _global_generators_left_as_found():
-    import random
-    t, n, r = torch.get_rng_state(), np.random.get_state(), random.getstate()
-    yield
-    torch.set_rng_state(t); np.random.set_state(n); random.setstate(r)
+from n2v_reference import global_generators_left_as_found, plugin_cfg as _cfg      # the fixture: autouse
 
 
 def test_the_reference_is_torch_sparse_adam_in_float64():
@@ -88,19 +81,6 @@ def test_the_metapath_case_names_the_dummy_row_and_meets_its_conditions():
     W, m, v, refs, compare, named = S.sparse_adam_reference(M.table(M.NATIVE_PATH, 129), sets)
     assert (~compare).mean() <= 1e-3 and all(P.conditions_hold(r) for r in refs) and all(r["K"][p.total] > 0 for r in refs)
     assert (~named).sum() >= 5 and compare[p.total].mean() > 0.9
-
-
-class Cfg(dict):
-    def __getattr__(self, k):
-        if k.startswith("__"): raise AttributeError(k)
-        return self.get(k)
-
-
-def _cfg(method, **kw):
-    sec = Cfg(d=16, w=3, e=4, b=16, lr=0.01, es=5, ns=2, spe=2, wl=5, wn=3, **kw)
-    if method == "m2v":
-        sec["metapath_name"] = [[["member", "to", "team"], ["team", "rev_to", "skill"], ["skill", "to", "team"], ["team", "rev_to", "member"]], "mtstm"]
-    return Cfg(graph=Cfg(structure=[[["skill", "to", "team"], ["member", "to", "team"]], "stm"], dup_edge="add", pre=None), **{method: sec})
 
 
 @pytest.mark.parametrize("method", ["n2v", "m2v"])
