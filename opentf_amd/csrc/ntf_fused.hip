@@ -86,6 +86,7 @@ __global__ void k_prep_h(SignSpec si, int bayes, const float* __restrict__ h, in
 // PAD: the weight rows are p.Hr < H floats wide (fused_tmpl).  They are fetched at stride p.Hr; the 16-byte chunks of a stage whose hidden units lie at or past p.Hr
 // are sourced from zeros (the padding columns of row 0 of p.h) - never from the next row, which need not exist and may hold anything.  p.h has H columns, the last
 // H - p.Hr zero; the s_in words are p.Hr / 32 a row.  The swizzle, the LDS image and the MFMA sequence are the template width's.
+constexpr size_t fwd_f32_lds(int H, bool bayes) { return 2 * ((size_t)(bayes ? 2 : 1) * BN * 4 * (H > 128 ? 128 : H) + 512); }   // two stages of out_fwd_f32_body<H>
 template <int H, bool BAYES, bool TRAIN, bool DH, bool INJ, bool PROBS = false, bool PAD = false>
 __device__ __forceinline__ void out_fwd_f32_body(const OutFwdArgs& p, char* smem) {
     static_assert(!PROBS || (!TRAIN && !DH), "the probability epilogue replaces the loss: forward only");
@@ -419,6 +420,7 @@ __global__ __launch_bounds__(256, H <= 64 ? 2 : 1) void k_out_probs(OutFwdArgs p
 // 32-byte read per row and matrix for all eight column tiles); its accumulators hold 8 consecutive hidden units of the rows rowmap(r, half).
 // ------------------------------------------------------------------------------------------------
 // PAD (160, 192, 224 hidden units): rows of p.Hr floats, the chunks past them staged from zeros as in the forward kernel; the slabs keep 256 columns.
+constexpr size_t out_dh_lds(bool bayes) { return 2 * (size_t)(bayes ? 2 : 1) * 32 * 4 * 256; }   // two stages of k_out_dh
 template <bool BAYES, bool INJ, bool PAD = false>
 __global__ __launch_bounds__(256, 1) void k_out_dh(OutFwdArgs p) {
     constexpr int H = 256, NJT = H / 32;
@@ -545,7 +547,6 @@ __global__ __launch_bounds__(256, 1) void k_out_dh(OutFwdArgs p) {
 // element e of lane half h  <->  expert 16s + 8(e>>2) + 4h + (e&3).
 // ------------------------------------------------------------------------------------------------
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-constexpr int BN6 = 32;   // experts per tile of k_out_fwd_b6
 
 // planes[tile][plane][row][H] (fp16 of W * scale) of a row-major f32 matrix W [M, H]; rows past M are zero
 __global__ void k_split_planes(const float* __restrict__ W, int M, int H, float scale, uint16_t* __restrict__ out, int* __restrict__ rflag) {
@@ -886,6 +887,8 @@ __global__ __launch_bounds__(256, 1) void k_out_fwd_b6(OutFwd6Args pp) {
 #ifndef H3P_BPRIO
 #define H3P_BPRIO 0
 #endif
+// the ring of three stages of k_out_fwd_h3p / k_out_fwd_h3e; producer: + k_out_fwd_h3p's two hand-over slots of 16 KiB
+constexpr size_t fwd_h3_lds(bool bayes, bool producer) { return 3 * ((size_t)(bayes ? 2 : 1) * 2 * 32 * 128 * 2 + 512) + (producer ? 2 * 16384 : 0); }
 template <bool BAYES, bool INJ, bool STAMP = false>      // STAMP (-DNTF_DIAG builds, NTF_FWD_ABL=9): cycle sums per wave and step segment into pp.stamps
 __global__ __launch_bounds__(512) void k_out_fwd_h3p(OutFwd6Args pp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1453,41 +1456,121 @@ __global__ __launch_bounds__(512) void k_out_fwd_h3e(OutFwd6Args pp) {
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int H, bool BAYES, bool PAD = false>
-static void fwd_dispatch(hipStream_t st, const FusedOut& f, const OutFwdArgs& a, const SpecialArgs& s, int grid, int phases) {
-    constexpr int HS = H > 128 ? 128 : H;                                   // hidden units per LDS stage (out_fwd_f32_body)
-    constexpr int STAGE = (BAYES ? 2 : 1) * BN * 4 * HS + 512;
-    const size_t lds = 2 * STAGE;
-    const bool dh = f.dh != nullptr;
-    const bool inj = BAYES && (f.s_out.inj != nullptr || f.s_in.inj != nullptr);  // packed images instead of the hash
-    // H = 256: the forward kernel without its dh products, then k_out_dh on the dz it stored (before the sparse fix-up of phase 4 patches dzT)
-#define NTF_LAUNCH_FWD(TR, DHF)                                                                                           \
-    do {                                                                                                                  \
-        constexpr bool DHK = (DHF) && H <= 128;                                                                           \
-        auto kf = inj ? k_out_fwd<H, BAYES, TR, DHK, BAYES, PAD> : k_out_fwd<H, BAYES, TR, DHK, false, PAD>;              \
-        if (phases & 2) {                                                                                                 \
-            set_max_lds(reinterpret_cast<const void*>(kf), (int)lds); \
-            hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, st, a);                                                    \
-            if ((DHF) && H == 256) {                                                                                      \
-                auto kd = inj ? k_out_dh<BAYES, BAYES, PAD> : k_out_dh<BAYES, false, PAD>;                                \
-                const size_t ldsd = 2 * (size_t)(BAYES ? 2 : 1) * 32 * 4 * 256;                                           \
-                set_max_lds(reinterpret_cast<const void*>(kd), (int)ldsd);                                                \
-                hipLaunchKernelGGL(kd, dim3(grid), dim3(256), ldsd, st, a);                                               \
-            }                                                                                                             \
-        }                                                                                                                 \
-        if (phases & 4) launch_out_special(st, f.H, BAYES, TR, DHF, s);                                                   \
-    } while (0)
-    if (f.probs) {      // inference: probabilities / logits to the transposed buffer, entropy partials to the workspace; no fix-up
-        if (phases & 2) {
-            auto kf = inj ? k_out_probs<H, BAYES, BAYES, PAD> : k_out_probs<H, BAYES, false, PAD>;
-            set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);
-            hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, st, a);
-        }
+// launch_fused_out_fwd: the launch arguments, phase 1, one function per kernel family, the choice between them
+static OutFwdArgs fwd_args(const FusedOut& f, const Geom& g, char* ws, const WsLayout& w) {
+    OutFwdArgs a;
+    a.B = f.B; a.M = f.M; a.Bpad = g.Bpad; a.NRB = g.NRB; a.NCG = g.NCG; a.T = g.T; a.nCB = g.nCB;
+    a.h = reinterpret_cast<float*>(ws + w.hz); a.hs = reinterpret_cast<float*>(ws + w.hs); a.mu = f.mu; a.mu_b = f.mu_b; a.wp = f.wp; a.bp = f.bp;
+    a.sbits = reinterpret_cast<uint32_t*>(ws + w.sbits); a.sinbits = reinterpret_cast<uint32_t*>(ws + w.sinbits);
+    a.tnw = f.tnw; a.inv_B = f.inv_B; a.dzT = f.dzT; a.slab = f.dh_slab; a.lossp = reinterpret_cast<float*>(ws + w.lossp);
+    a.so_k0 = f.s_out.k0; a.so_k1 = f.s_out.k1; a.si_k0 = f.s_in.k0; a.si_k1 = f.s_in.k1; a.so_inj = f.s_out.inj != nullptr; a.si_inj = f.s_in.inj != nullptr;
+    a.rflag = f.rflag; a.rmode = 0;
+    a.pscale = f.pscale; a.pacc = f.pacc; a.plogit = f.plogit; a.Hr = f.H;
+    a.t_lo = 0; a.t_hi = g.T; a.cg_off = 0; a.ncg_tot = g.NCG;
+    return a;
+}
+static SpecialArgs special_args(const FusedOut& f, const Geom& g, const OutFwdArgs& a, bool inj) {
+    const bool ranged = f.chunk_ncg_tot > 0;      // the split-product forward of this step runs (ran) as launches over ranges of the experts (FusedOut.chunk_*)
+    SpecialArgs s;
+    s.B = f.B; s.M = f.M; s.Bpad = g.Bpad; s.NCG = ranged ? f.chunk_ncg_tot : g.NCG; s.nCB = g.nCB; s.ns = f.ns;
+    s.nslab = s.NCG; s.fb_ncg = ranged ? g.NCG : 0;
+    s.h = f.h; s.hs = a.hs; s.mu = f.mu; s.mu_b = f.mu_b; s.wp = f.wp; s.bp = f.bp; s.slab = f.dh_slab; s.lossp = a.lossp; s.h_mask = f.h_mask;
+    s.sbits = a.sbits; s.sinbits = a.sinbits; s.rows = f.rows; s.m_indptr = f.m_indptr; s.neg = f.neg; s.m_indices = f.m_indices;
+    s.tpw = f.tpw; s.tnw = f.tnw; s.inv_B = f.inv_B; s.dzT = f.dzT; s.dh = f.dh; s.row_fix = f.row_fix;
+    s.so_k0 = f.s_out.k0; s.so_k1 = f.s_out.k1; s.so_inj = inj;
+    s.dz_pack_scale = (f.train && f.split && f.H == 128) ? f.dz_scale : 0.f; s.rflag = f.rflag; s.c_lo = f.c_lo;
+    s.wp_pl = (f.bayes && f.split && f.H == 128 && f.wp_pl) ? f.wp_pl : nullptr; s.wp_inv_scale = 1.f / f.w_scale;
+    return s;
+}
+// phase 1: the operand images of the step - injected s_out signs, hz / hs / the s_in words, the fp16 planes of mu and Wp (fp16x3, H = 128)
+static void launch_fwd_prep(hipStream_t st, const FusedOut& f, const Geom& g, char* ws, const WsLayout& w, bool inj, bool guard) {
+    const int Ht = fused_tmpl(f.H);
+    if (inj) hipLaunchKernelGGL(k_sign_bits, dim3((g.nCB + 63) / 64, g.Bpad), dim3(64), 0, st, f.s_out, f.B, f.M, g.nCB, reinterpret_cast<uint32_t*>(ws + w.sbits));
+    if (!f.h_ready) {
+        const int n = g.Bpad * (Ht / 32);
+        hipLaunchKernelGGL(k_prep_h, dim3((n + 63) / 64), dim3(64), 0, st, f.s_in, f.bayes, f.h, f.B, f.H, Ht, g.Bpad, reinterpret_cast<uint32_t*>(ws + w.sinbits),
+                           reinterpret_cast<float*>(ws + w.hs), reinterpret_cast<float*>(ws + w.hz), guard ? 65504.f / f.h_scale : 0.f, guard ? f.rflag : nullptr);
     }
-    else if (!f.train) NTF_LAUNCH_FWD(false, false);
-    else if (dh) NTF_LAUNCH_FWD(true, true);
-    else NTF_LAUNCH_FWD(true, false);
-#undef NTF_LAUNCH_FWD
+    if (f.split && f.H == 128 && !f.planes_ready) {
+        const int64_t Mp = ((int64_t)f.M + BN6 - 1) / BN6 * BN6, n = Mp * (f.H / 2);
+        hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f.mu, f.M, f.H, f.w_scale, f.mu_pl, guard ? f.rflag : nullptr);
+        if (f.bayes) hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f.wp, f.M, f.H, f.w_scale, f.wp_pl, guard ? f.rflag : nullptr);
+    }
+}
+// the exact-f32 kernels of template width H: phase 2 (k_out_probs, or k_out_fwd and at 256 k_out_dh behind it) and phase 4 (the sparse fix-up)
+template <int H, bool BAYES, bool PAD>
+static void launch_fwd_f32(hipStream_t st, const FusedOut& f, const OutFwdArgs& a, const SpecialArgs& s, int grid, int phases, bool inj) {
+    const size_t lds = fwd_f32_lds(H, BAYES);
+    const bool dhf = f.train && f.dh != nullptr;
+    if (phases & 2) with_flag(inj, [&](auto ij) {
+        constexpr bool IJ = BAYES && decltype(ij)::value;      // packed images instead of the hash: Flipout only (without it the INJ forms are not built)
+        // inference: probabilities / logits to the transposed buffer, entropy partials to the workspace; no fix-up
+        if (f.probs) { launch_lds(k_out_probs<H, BAYES, IJ, PAD>, dim3(grid), dim3(256), lds, st, a); return; }
+        with_flag(f.train, [&](auto tr) { with_flag(dhf, [&](auto dh) {
+            constexpr bool TR = decltype(tr)::value, DHF = TR && decltype(dh)::value, DHK = DHF && H <= 128;
+            launch_lds(k_out_fwd<H, BAYES, TR, DHK, IJ, PAD>, dim3(grid), dim3(256), lds, st, a);
+            // H = 256: the forward kernel without its dh products, then k_out_dh on the dz it stored (before the sparse fix-up of phase 4 patches dzT)
+            if constexpr (DHF && H == 256) launch_lds(k_out_dh<BAYES, IJ, PAD>, dim3(grid), dim3(256), out_dh_lds(BAYES), st, a);
+        }); });
+    });
+    if ((phases & 4) && !f.probs) launch_out_special(st, f.H, BAYES, f.train != 0, dhf, s);
+}
+// the same pass on the exact-f32 kernel behind a split-product launch: it runs only when an operand left the fp16 window
+static void launch_fwd_fallback(hipStream_t st, const FusedOut& f, OutFwdArgs a, const SpecialArgs& s, int grid, bool inj) {
+    a.rmode = 2;
+    with_flag(f.bayes, [&](auto by) { launch_fwd_f32<128, decltype(by)::value, false>(st, f, a, s, grid, 2, inj); });
+}
+#ifdef NTF_DIAG
+// NTF_FWD_ABL=9: k_out_fwd_h3p<true, false, STAMP> in place of the step's kernel, the 30th launch's cycle sums per wave role and step segment to stderr.  True: it launched
+static bool launch_fwd_h3p_stamped(hipStream_t st, const FusedOut& f, OutFwd6Args a6, int grid, bool inj) {
+    static const int fwd_abl5 = getenv("NTF_FWD_ABL") ? atoi(getenv("NTF_FWD_ABL")) : 0;
+    if (fwd_abl5 != 9 || !f.bayes || inj) return false;
+    static unsigned long long* d_st = nullptr; static int n_launch = 0;
+    if (!d_st) hipMalloc(&d_st, (size_t)grid * 8 * 10 * 8);
+    a6.stamps = d_st;
+    launch_lds(k_out_fwd_h3p<true, false, true>, dim3(grid), dim3(512), fwd_h3_lds(true, true), st, a6);
+    if (++n_launch != 30) return true;
+    std::vector<unsigned long long> hst((size_t)grid * 80);
+    hipStreamSynchronize(st); hipMemcpy(hst.data(), d_st, hst.size() * 8, hipMemcpyDeviceToHost);
+    double cyc = 0, wall = 0;
+    for (size_t w = 0; w < (size_t)grid * 8; ++w) { cyc += (double)hst[w * 10 + 7]; wall += (double)hst[w * 10 + 8]; }
+    fprintf(stderr, "[pair stamps] per wave, kernel entry to the end of its loop: %.0f shader-clock cycles in %.0f ticks of 100 MHz = %.3f GHz, %.3f ms\n",
+            cyc / (grid * 8.0), wall / (grid * 8.0), cyc / (wall * 10.0), wall / (grid * 8.0) / 1e5);
+    for (int role = 0; role < 2; ++role) {
+        double sum[7] = {0};
+        for (int wg = 0; wg < grid; ++wg) for (int w = 4 * role; w < 4 * role + 4; ++w) for (int q = 0; q < 7; ++q) sum[q] += (double)hst[((size_t)wg * 8 + w) * 10 + q];
+        if (role == 0) fprintf(stderr, "[pair stamps] waves 0-3, cycles per step: top+first reads %.0f | MFMAs+DMA %.0f | dz stores %.0f | logits %.0f | wait %.0f | barrier %.0f  (steps/wave %.1f)\n",
+                sum[4] / sum[6], sum[0] / sum[6], sum[5] / sum[6], sum[1] / sum[6], sum[2] / sum[6], sum[3] / sum[6], sum[6] / (grid * 4.0));
+        else fprintf(stderr, "[pair stamps] waves 4-7, cycles per step: top+reads %.0f | dz %.0f | dh MFMAs %.0f | wait %.0f | barrier %.0f\n",
+                sum[4] / sum[6], sum[0] / sum[6], sum[1] / sum[6], sum[2] / sum[6], sum[3] / sum[6]);
+    }
+    return true;
+}
+#endif
+// fp16x3 at H = 128, phase 2: the evaluation kernel (evalp: nrbe 256-row blocks x ncg column groups), the training step's wave pairs, or k_out_fwd_b6
+static void launch_fwd_split(hipStream_t st, const FusedOut& f, const OutFwdArgs& a, int grid, bool evalp, int nrbe, int ncg, bool inj, bool guard) {
+    OutFwd6Args a6; a6.stamps = nullptr; a6.a = a; a6.mu_pl = f.mu_pl; a6.wp_pl = f.wp_pl;
+    a6.a.rmode = guard ? 1 : 0;
+    a6.h_scale = f.h_scale; a6.dz_scale = f.dz_scale;
+    a6.u_z = 1.f / (f.w_scale * f.h_scale); a6.u_dh = 1.f / (f.dz_scale * f.w_scale);
+    const bool dh = f.dh != nullptr;
+    with_flag(f.bayes, [&](auto by) { with_flag(inj, [&](auto ij) {
+        constexpr bool BY = decltype(by)::value, IJ = BY && decltype(ij)::value;      // (INJ forms: Flipout only)
+        const dim3 g6(grid), b6(256);
+        if (evalp) {
+            OutFwd6Args ae = a6; ae.a.NRB = nrbe;
+            launch_lds(k_out_fwd_h3e<BY, IJ>, dim3(nrbe * ncg), dim3(512), fwd_h3_lds(BY, false), st, ae);
+        } else if (f.train && dh && f.wide == 5) {    // the fp16x3 training step: producer / consumer wave pairs, two waves per SIMD (a.T counts 64-expert tiles)
+#ifdef NTF_DIAG
+            if (launch_fwd_h3p_stamped(st, f, a6, grid, inj)) return;
+#endif
+            launch_lds(k_out_fwd_h3p<BY, IJ>, dim3(grid), dim3(512), fwd_h3_lds(BY, true), st, a6);
+        }
+        else if (f.probs) launch_lds(k_out_fwd_b6<BY, false, false, IJ, true>, g6, b6, fwd_b6_lds(BY), st, a6);
+        else if (!f.train) launch_lds(k_out_fwd_b6<BY, false, false, IJ, false>, g6, b6, fwd_b6_lds(BY), st, a6);
+        else if (dh) launch_lds(k_out_fwd_b6<BY, true, true, IJ, false>, g6, b6, fwd_b6_lds(BY), st, a6);
+        else launch_lds(k_out_fwd_b6<BY, true, false, IJ, false>, g6, b6, fwd_b6_lds(BY), st, a6);
+    }); });
 }
 
 void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
@@ -1501,124 +1584,28 @@ void launch_fused_out_fwd(hipStream_t st, const FusedOut& f, int phases) {
     if (evalp) g.NCG = std::max(1, std::min({NCG_MAX / nrbe, g.T, NCG_MAX}));
     const WsLayout w = ws_layout(f.B, f.H, f.M);
     char* ws = static_cast<char*>(f.ws);
-    uint32_t* sbits = reinterpret_cast<uint32_t*>(ws + w.sbits);
-    uint32_t* sinbits = reinterpret_cast<uint32_t*>(ws + w.sinbits);
-    float* hs = reinterpret_cast<float*>(ws + w.hs);
-    float* hz = reinterpret_cast<float*>(ws + w.hz);
-    float* lossp = reinterpret_cast<float*>(ws + w.lossp);
-    const bool inj = f.bayes && (f.s_out.inj != nullptr || f.s_in.inj != nullptr);
+    const bool inj = f.bayes && (f.s_out.inj != nullptr || f.s_in.inj != nullptr);  // packed images instead of the hash
     const bool guard = f.rflag != nullptr;   // fp16x3 arithmetic somewhere in this step (forward and / or dW): range-checked operands
-    if (inj && (phases & 1)) hipLaunchKernelGGL(k_sign_bits, dim3((g.nCB + 63) / 64, g.Bpad), dim3(64), 0, st, f.s_out, f.B, f.M, g.nCB, sbits);
-    if ((phases & 1) && !f.h_ready) {
-        const int n = g.Bpad * (Ht / 32);
-        hipLaunchKernelGGL(k_prep_h, dim3((n + 63) / 64), dim3(64), 0, st, f.s_in, f.bayes, f.h, f.B, f.H, Ht, g.Bpad, sinbits, hs, hz,
-                           guard ? 65504.f / f.h_scale : 0.f, guard ? f.rflag : nullptr);
-    }
-    OutFwdArgs a;
-    a.B = f.B; a.M = f.M; a.Bpad = g.Bpad; a.NRB = g.NRB; a.NCG = g.NCG; a.T = g.T; a.nCB = g.nCB;
-    a.h = hz; a.hs = hs; a.mu = f.mu; a.mu_b = f.mu_b; a.wp = f.wp; a.bp = f.bp; a.sbits = sbits; a.sinbits = sinbits;
-    a.tnw = f.tnw; a.inv_B = f.inv_B; a.dzT = f.dzT; a.slab = f.dh_slab; a.lossp = lossp;
-    a.so_k0 = f.s_out.k0; a.so_k1 = f.s_out.k1; a.si_k0 = f.s_in.k0; a.si_k1 = f.s_in.k1; a.so_inj = f.s_out.inj != nullptr; a.si_inj = f.s_in.inj != nullptr;
-    a.rflag = f.rflag; a.rmode = 0;
-    a.pscale = f.pscale; a.pacc = f.pacc; a.plogit = f.plogit; a.Hr = f.H;
-    a.t_lo = 0; a.t_hi = g.T; a.cg_off = 0; a.ncg_tot = g.NCG;
-    const bool ranged = f.chunk_ncg_tot > 0;      // the split-product forward of this step runs (ran) as launches over ranges of the experts (FusedOut.chunk_*)
-    SpecialArgs s;
-    s.B = f.B; s.M = f.M; s.Bpad = g.Bpad; s.NCG = ranged ? f.chunk_ncg_tot : g.NCG; s.nCB = g.nCB; s.ns = f.ns;
-    s.nslab = s.NCG; s.fb_ncg = ranged ? g.NCG : 0;
-    s.h = f.h; s.hs = hs; s.mu = f.mu; s.mu_b = f.mu_b; s.wp = f.wp; s.bp = f.bp; s.slab = f.dh_slab; s.lossp = lossp; s.h_mask = f.h_mask;
-    s.sbits = sbits; s.sinbits = sinbits; s.rows = f.rows; s.m_indptr = f.m_indptr; s.neg = f.neg; s.m_indices = f.m_indices;
-    s.tpw = f.tpw; s.tnw = f.tnw; s.inv_B = f.inv_B; s.dzT = f.dzT; s.dh = f.dh; s.row_fix = f.row_fix;
-    s.so_k0 = f.s_out.k0; s.so_k1 = f.s_out.k1; s.so_inj = inj;
-    s.dz_pack_scale = (f.train && f.split && f.H == 128) ? f.dz_scale : 0.f; s.rflag = f.rflag; s.c_lo = f.c_lo;
-    s.wp_pl = (f.bayes && f.split && f.H == 128 && f.wp_pl) ? f.wp_pl : nullptr; s.wp_inv_scale = 1.f / f.w_scale;
+    if (phases & 1) launch_fwd_prep(st, f, g, ws, w, inj, guard);
+    OutFwdArgs a = fwd_args(f, g, ws, w);
+    const SpecialArgs s = special_args(f, g, a, inj);
     int grid = g.NRB * g.NCG;
-    const bool range_launch = ranged && f.chunk_ncg > 0 && (phases & 2);      // THIS call launches one range
+    const bool range_launch = f.chunk_ncg_tot > 0 && f.chunk_ncg > 0 && (phases & 2);      // THIS call launches one range of a ranged step
     if (range_launch) { a.t_lo = f.chunk_t_lo; a.t_hi = f.chunk_t_hi; a.cg_off = f.chunk_cg_off; a.ncg_tot = f.chunk_ncg_tot; a.NCG = f.chunk_ncg; grid = g.NRB * f.chunk_ncg; }
     if (f.split && f.H == 128) {
-        if ((phases & 1) && !f.planes_ready) {
-            const int64_t Mp = ((int64_t)f.M + BN6 - 1) / BN6 * BN6, n = Mp * (f.H / 2);
-            hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f.mu, f.M, f.H, f.w_scale, f.mu_pl, guard ? f.rflag : nullptr);
-            if (f.bayes) hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f.wp, f.M, f.H, f.w_scale, f.wp_pl, guard ? f.rflag : nullptr);
-        }
         if (phases & 2) {
-            OutFwd6Args a6; a6.stamps = nullptr; a6.a = a; a6.mu_pl = f.mu_pl; a6.wp_pl = f.wp_pl;
-            a6.a.rmode = guard ? 1 : 0;
-            a6.h_scale = f.h_scale; a6.dz_scale = f.dz_scale;
-            a6.u_z = 1.f / (f.w_scale * f.h_scale); a6.u_dh = 1.f / (f.dz_scale * f.w_scale);
-            const bool dh = f.dh != nullptr;
-            const size_t lds = (size_t)2 * ((size_t)(f.bayes ? 2 : 1) * 2 * BN6 * 128 * 2 + 512);
-#define NTF_L6(BY, TR, DHF, IJ, PR) do { auto kf = k_out_fwd_b6<BY, TR, DHF, IJ, PR>;                                     \
-            set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);       \
-            hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, st, a6); } while (0)
-#define NTF_L6B(BY, IJ) do { if (f.probs) NTF_L6(BY, false, false, IJ, true); else if (!f.train) NTF_L6(BY, false, false, IJ, false);  \
-                             else if (dh) NTF_L6(BY, true, true, IJ, false); else NTF_L6(BY, true, false, IJ, false); } while (0)
-            if (evalp) {
-                const size_t ldse = 3 * ((size_t)(f.bayes ? 2 : 1) * 2 * 32 * 128 * 2 + 512);
-                OutFwd6Args ae = a6; ae.a.NRB = nrbe;
-#define NTF_LE(BY, IJ) do { auto kf = k_out_fwd_h3e<BY, IJ>;                                                                    \
-                set_max_lds(reinterpret_cast<const void*>(kf), (int)ldse);  \
-                hipLaunchKernelGGL(kf, dim3(nrbe * g.NCG), dim3(512), ldse, st, ae); } while (0)
-                if (f.bayes) { if (inj) NTF_LE(true, true); else NTF_LE(true, false); } else NTF_LE(false, false);
-#undef NTF_LE
-            } else
-            if (f.train && dh && f.wide == 5) {    // the fp16x3 training step: producer / consumer wave pairs, two waves per SIMD (a.T counts 64-expert tiles)
-                {
-                    const size_t ldsp = 3 * ((size_t)(f.bayes ? 2 : 1) * 2 * 32 * 128 * 2 + 512) + 2 * 16384;
-#define NTF_LP(BY, IJ) do { auto kf = k_out_fwd_h3p<BY, IJ>;                                                                    \
-                set_max_lds(reinterpret_cast<const void*>(kf), (int)ldsp);  \
-                hipLaunchKernelGGL(kf, dim3(grid), dim3(512), ldsp, st, a6); } while (0)
-#ifdef NTF_DIAG
-                    static const int fwd_abl5 = getenv("NTF_FWD_ABL") ? atoi(getenv("NTF_FWD_ABL")) : 0;
-                    if (fwd_abl5 == 9 && f.bayes && !inj) {
-                        static unsigned long long* d_st = nullptr; static int n_launch = 0;
-                        if (!d_st) hipMalloc(&d_st, (size_t)grid * 8 * 10 * 8);
-                        a6.stamps = d_st;
-                        auto kf = k_out_fwd_h3p<true, false, true>;
-                        set_max_lds(reinterpret_cast<const void*>(kf), (int)ldsp);
-                        hipLaunchKernelGGL(kf, dim3(grid), dim3(512), ldsp, st, a6);
-                        if (++n_launch == 30) {
-                            std::vector<unsigned long long> hst((size_t)grid * 80);
-                            hipStreamSynchronize(st); hipMemcpy(hst.data(), d_st, hst.size() * 8, hipMemcpyDeviceToHost);
-                            double cyc = 0, wall = 0;
-                            for (size_t w = 0; w < (size_t)grid * 8; ++w) { cyc += (double)hst[w * 10 + 7]; wall += (double)hst[w * 10 + 8]; }
-                            fprintf(stderr, "[pair stamps] per wave, kernel entry to the end of its loop: %.0f shader-clock cycles in %.0f ticks of 100 MHz = %.3f GHz, %.3f ms\n",
-                                    cyc / (grid * 8.0), wall / (grid * 8.0), cyc / (wall * 10.0), wall / (grid * 8.0) / 1e5);
-                            for (int role = 0; role < 2; ++role) {
-                                double sum[7] = {0};
-                                for (int wg = 0; wg < grid; ++wg) for (int w = 4 * role; w < 4 * role + 4; ++w) for (int q = 0; q < 7; ++q) sum[q] += (double)hst[((size_t)wg * 8 + w) * 10 + q];
-                                if (role == 0) fprintf(stderr, "[pair stamps] waves 0-3, cycles per step: top+first reads %.0f | MFMAs+DMA %.0f | dz stores %.0f | logits %.0f | wait %.0f | barrier %.0f  (steps/wave %.1f)\n",
-                                        sum[4] / sum[6], sum[0] / sum[6], sum[5] / sum[6], sum[1] / sum[6], sum[2] / sum[6], sum[3] / sum[6], sum[6] / (grid * 4.0));
-                                else fprintf(stderr, "[pair stamps] waves 4-7, cycles per step: top+reads %.0f | dz %.0f | dh MFMAs %.0f | wait %.0f | barrier %.0f\n",
-                                        sum[4] / sum[6], sum[0] / sum[6], sum[1] / sum[6], sum[2] / sum[6], sum[3] / sum[6]);
-                            }
-                        }
-                    } else
-#endif
-                    if (f.bayes) { if (inj) NTF_LP(true, true); else NTF_LP(true, false); } else NTF_LP(false, false);
-#undef NTF_LP
-                }
-            } else if (f.bayes) { if (inj) NTF_L6B(true, true); else NTF_L6B(true, false); } else NTF_L6B(false, false);
-#undef NTF_L6B
-#undef NTF_L6
-            if (guard && !f.probs && !f.split_fallback && !range_launch) {   // the same pass on the exact-f32 kernel, run only when an operand left the fp16 window
-                OutFwdArgs af = a; af.rmode = 2;
-                if (f.bayes) fwd_dispatch<128, true>(st, f, af, s, grid, 2); else fwd_dispatch<128, false>(st, f, af, s, grid, 2);
-            }
+            launch_fwd_split(st, f, a, grid, evalp, nrbe, g.NCG, inj, guard);
+            if (guard && !f.probs && !f.split_fallback && !range_launch) launch_fwd_fallback(st, f, a, s, grid, inj);
         }
-        if ((phases & 8) && f.split_fallback && guard && !f.probs) {   // ... as a launch of its own: behind the last range of a ranged (data-parallel) step, once over the whole layer
-            OutFwdArgs af = a; af.rmode = 2;
-            if (f.bayes) fwd_dispatch<128, true>(st, f, af, s, grid, 2); else fwd_dispatch<128, false>(st, f, af, s, grid, 2);
-        }
-        if ((phases & 4) && !f.probs) {
-            launch_out_special(st, 128, f.bayes != 0, f.train != 0, f.dh != nullptr, s);
-        }
+        // ... as a launch of its own: behind the last range of a ranged (data-parallel) step, once over the whole layer
+        if ((phases & 8) && f.split_fallback && guard && !f.probs) launch_fwd_fallback(st, f, a, s, grid, inj);
+        if ((phases & 4) && !f.probs) launch_out_special(st, 128, f.bayes != 0, f.train != 0, f.dh != nullptr, s);
         return;
     }
-#define NTF_H(HH, PD) do { if (f.bayes) fwd_dispatch<HH, true, PD>(st, f, a, s, grid, phases); else fwd_dispatch<HH, false, PD>(st, f, a, s, grid, phases); } while (0)
-    if (Ht != f.H) { if (Ht == 256) NTF_H(256, true); else NTF_H(128, true); }
-    else if (f.H == 256) NTF_H(256, false); else if (f.H == 128) NTF_H(128, false); else if (f.H == 64) NTF_H(64, false); else NTF_H(32, false);
-#undef NTF_H
+    with_value<256, 128, 64, 32>(Ht, [&](auto h) { with_flag(Ht != f.H, [&](auto pd) { with_flag(f.bayes, [&](auto by) {
+        constexpr int H = decltype(h)::value; constexpr bool PD = H >= 128 && decltype(pd)::value;      // (PAD forms: 96 on 128; 160, 192, 224 on 256)
+        launch_fwd_f32<H, decltype(by)::value, PD>(st, f, a, s, grid, phases, inj);
+    }); }); });
 }
 
 // inference helpers: ent[i] += sum over the column groups of the per-row entropy partials; P[i][c] = PT[c][i] (tiled transpose through LDS)

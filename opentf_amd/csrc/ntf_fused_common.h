@@ -3,6 +3,7 @@
 #pragma once
 #include "ntf_fused.h"
 #include "ntf_device.h"
+#include "ntf_host.h"
 #include <algorithm>
 #include <vector>
 #include <cstdio>
@@ -21,6 +22,8 @@ constexpr int NCG_MAX = 256;  // column groups (one workgroup per CU when the ba
 #endif
 constexpr int DW_WAVES = 8;               // waves per workgroup of the dW kernel: two per SIMD
 constexpr int DW_TC = 32 * DW_WAVES;      // experts per workgroup of the dW kernel
+constexpr int BN6 = 32;                   // experts per tile of k_out_fwd_b6 and k_out_probs_mc, whose two LDS stages hold the fp16 planes of the tile (+ 512 B of bias tiles)
+constexpr size_t fwd_b6_lds(bool bayes) { return (size_t)2 * ((size_t)(bayes ? 2 : 1) * 2 * BN6 * 128 * 2 + 512); }
 
 static inline int rup(int a, int b) { return (a + b - 1) / b * b; }
 // Hidden widths 96, 160, 192 and 224 run the kernels of the next fused width up (96 -> 128; the others -> 256), which take the real row width as a run-time
@@ -37,6 +40,11 @@ inline void set_max_lds(const void* fn, int bytes) {
     if (it != done.end() && it->second >= bytes) return;
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     done[key] = bytes;
+}
+// the launch of a kernel with `lds` bytes of dynamic LDS (the only caller of set_max_lds)
+template <class K, class... A> void launch_lds(K kf, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);
+    hipLaunchKernelGGL(kf, grid, block, lds, st, args...);
 }
 // Layout of dzT (d loss / d z of the output layer, the only dense [experts x batch] tensor of a step): tiles of DW_TC = 256 experts x 32 batch
 // rows, [expert tile][32-row K block][expert in tile][row in block].  The dW kernel consumes one K block of its expert tile per stage: one

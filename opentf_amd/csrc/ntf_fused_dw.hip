@@ -110,6 +110,7 @@ __device__ __forceinline__ void dw_produce_finish(const DwArgs& p, float kl, flo
 // PAD: the layer's rows are p.Hr < HG floats wide (96 on H = 128's shape; 160, 192, 224 on the two-workgroup shape of 256): the h tiles keep HG columns, zero past
 // p.Hr; the epilogue addresses rows of p.Hr floats, and a lane whose NJT hidden units lie past p.Hr loads and stores nothing - no parameter, moment or gradient outside
 // its row is touched, and Flipout's KL / rho terms are taken over real elements only.
+constexpr size_t dw_f32_lds(int H, bool bayes) { return 2 * ((size_t)DW_TC * 32 * 4 + (size_t)(bayes ? 2 : 1) * 32 * 4 * H); }   // two stages of out_dw_f32_body<H>
 template <int H, bool BAYES, bool ADAM, int HG = H, bool PAD = false>
 __device__ __forceinline__ void out_dw_f32_body(const DwArgs& p, char* smem, int jh = 0) {  // ADAM: see DwArgs
     constexpr int NJT = H / 32;
@@ -313,6 +314,7 @@ __global__ void k_prep_planes_T(const float* __restrict__ hz, const float* __res
 //   B: the fp16 planes of h / h*s_in for the K block ([plane][j][32 rows], chunks swizzled with (j>>2)&3): one ds_read_b128 per fragment.
 // No compiler-visible global load sits in the loop: hipcc would wait for it with a vmcnt that, in the real in-order queue, also waits
 // for the DMA issued just before.
+constexpr size_t dw_b6_lds(int H, bool bayes) { return 2 * ((size_t)DW_TC * 128 + (size_t)(bayes ? 2 : 1) * 2 * H * 64); }   // two stages of k_out_dw_b6<H>
 template <int H, bool BAYES, bool ADAM>
 __global__ __launch_bounds__(64 * DW_WAVES, 2) void k_out_dw_b6(DwArgs p) {   // ADAM: update mu / rho and their moments in the epilogue (see DwArgs)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -624,6 +626,7 @@ constexpr int QW = 4;            // waves per workgroup
 constexpr int QTC = 32 * QW;     // experts per workgroup
 // SPLIT (round 5): the split-K form for few expert tiles - a narrow expert shard under a wide minibatch: workgroup = (tile, K range), raw partial sums into the slabs
 // k_out_dw_finish adds up (the layout k_out_dw_p2's split launch writes: an accumulator's element is addressed by its expert row and hidden unit, not by the kernel).
+constexpr size_t dw_q_lds(bool bayes) { return 2 * ((size_t)QTC * 128 + 2 * 128 * 64 + (bayes ? 1024 : 0)) + 64; }   // two stages of k_out_dw_q + dw_produce_finish's scratch
 template <bool BAYES, bool ADAM, bool STAMP = false, bool SPLIT = false>
 __global__ __launch_bounds__(64 * QW, 2) void k_out_dw_q(DwArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -838,8 +841,8 @@ __global__ __launch_bounds__(64 * QW, 2) void k_out_dw_q(DwArgs p) {
     if (ADAM && p.produce) dw_produce_finish<BAYES>(p, nx_kl, nx_amax, reinterpret_cast<double*>(smem + 2 * STAGE), QW);   // (scratch behind the stages)
 }
 
-void launch_fused_out_dw(hipStream_t st, const FusedDw& f) {
-    const Geom g = geom(f.B, f.M);
+// ---- launch_fused_out_dw: the launch arguments, one function per kernel family, the choice between them
+static DwArgs dw_args(const FusedDw& f, const Geom& g) {
     const WsLayout w = ws_layout(f.B, f.H, f.M);
     char* ws = static_cast<char*>(f.ws);
     DwArgs a;
@@ -849,130 +852,121 @@ void launch_fused_out_dw(hipStream_t st, const FusedDw& f) {
     a.g_mu = f.g_mu; a.g_rho = f.g_rho; a.g_b = f.g_b; a.g_bp = f.g_bp; a.klw = f.klw;
     a.w_mu = f.w_mu; a.w_rho = f.w_rho; a.m_mu = f.m_mu; a.v_mu = f.v_mu; a.m_rho = f.m_rho; a.v_rho = f.v_rho;
     a.lr_over_bc1 = f.lr_over_bc1; a.b1 = f.b1; a.b2 = f.b2; a.eps = f.eps; a.bc2_sqrt = f.bc2_sqrt;
-    const int total = (f.M + DW_TC - 1) / DW_TC;
-    const int grid = f.wg_count > 0 ? std::min(f.wg_count, total - f.wg_begin) : total;
     a.wg_begin = f.wg_count > 0 ? f.wg_begin : 0;
-    if (grid <= 0) return;
     a.hb = reinterpret_cast<const uint16_t*>(ws + w.hb);
     a.rflag = f.rflag; a.rmode = 0;
     a.produce = (f.produce && f.adam && f.H == 128) ? 1 : 0;      // (Fnn: the planes of the updated mu and the range flag only)
     a.cur_eps = f.cur_eps; a.lean = (a.produce && f.lean) ? 1 : 0;
     a.nx_eps = f.nx_eps; a.nx_wp = f.nx_wp; a.nx_pl_wp = f.nx_pl_wp; a.nx_pl_mu = f.nx_pl_mu; a.nx_pscale = f.nx_pscale; a.nx_klw = f.nx_klw; a.nx_kl = f.nx_kl; a.nx_rflag = f.nx_rflag;
     a.ntile = 0; a.stagger = 0; a.stamps = nullptr;
-    const bool guard = f.split && f.rflag != nullptr;
-    a.sT = reinterpret_cast<const uint32_t*>(ws + w.sbitsT);
+    a.sT = reinterpret_cast<const uint32_t*>(ws + w.sbitsT); a.sinT = reinterpret_cast<const uint32_t*>(ws + w.sinT);
     a.ksplit = 1; a.part = nullptr; a.slab = 0; a.part_row0 = 0;
+    a.Hr = f.H;
+    a.a_scale = f.split ? f.a_scale : 0.f; a.unscale = f.split ? 1.f / (f.a_scale * f.h_scale) : 0.f;   // (fp16x3 only)
+    return a;
+}
+// width 256 (and 160, 192, 224 on it): exact-f32 only (no split-product kernels at this width), each 256-expert tile as two hidden-half workgroups
+static void launch_dw_h2(hipStream_t st, const FusedDw& f, const DwArgs& a, int grid, bool pad) {
+    with_flag(f.bayes, [&](auto by) { with_flag(f.adam, [&](auto ad) { with_flag(pad, [&](auto pd) {
+        constexpr bool BY = decltype(by)::value, AD = decltype(ad)::value, PD = decltype(pd)::value;
+        launch_lds(k_out_dw_h2<BY, AD, PD>, dim3(grid, 2), dim3(64 * DW_WAVES), dw_f32_lds(128, BY), st, a);
+    }); }); });
+}
+// 96 on H = 128's exact-f32 kernel
+static void launch_dw_pad128(hipStream_t st, const FusedDw& f, const DwArgs& a, int grid) {
+    with_flag(f.bayes, [&](auto by) { with_flag(f.adam, [&](auto ad) {
+        constexpr bool BY = decltype(by)::value, AD = decltype(ad)::value;
+        launch_lds(k_out_dw<128, BY, AD, true>, dim3(grid), dim3(64 * DW_WAVES), dw_f32_lds(128, BY), st, a);
+    }); });
+}
+#ifdef NTF_DIAG
+// NTF_DW_STAMP_FILE: the 30th launch's per-wave stamps of k_out_dw_q<true, true>, raw (10 x u64 per wave), to this file (profiles/dw_stamps.py).  True: it launched
+static bool launch_dw_q_stamped(hipStream_t st, const FusedDw& f, DwArgs& a, int qgrid) {
+    static const char* stamp_file = getenv("NTF_DW_STAMP_FILE");
+    if (!stamp_file || !f.bayes || !f.adam) return false;
+    static unsigned long long* d_st = nullptr; static int n_launch = 0;
+    if (!d_st) hipMalloc(&d_st, (size_t)qgrid * QW * 10 * 8);
+    a.stamps = d_st;
+    launch_lds(k_out_dw_q<true, true, true>, dim3(qgrid), dim3(64 * QW), dw_q_lds(true), st, a);
+    if (++n_launch == 30) {
+        std::vector<unsigned long long> hst((size_t)qgrid * QW * 10);
+        hipStreamSynchronize(st); hipMemcpy(hst.data(), d_st, hst.size() * 8, hipMemcpyDeviceToHost);
+        if (FILE* fp = fopen(stamp_file, "wb")) { fwrite(hst.data(), 8, hst.size(), fp); fclose(fp); }
+    }
+    return true;
+}
+#endif
+// fp16x3 step, H = 128: the forward kernel left packed plane pairs in dzT.  Quarter-grid arithmetic: a 256-expert tile of the caller's range is two QTC-expert workgroups
+// (a: left as the exact-f32 launch behind this one takes it - the 256-expert tile range again, no split, no stagger)
+static void launch_dw_q(hipStream_t st, const FusedDw& f, DwArgs& a, const Geom& g) {
+    const int total_q = (f.M + QTC - 1) / QTC, qb = f.wg_count > 0 ? 2 * f.wg_begin : 0;
+    const int qgrid = f.wg_count > 0 ? std::min(2 * f.wg_count, total_q - qb) : total_q;
+    const int wg256 = a.wg_begin;
+    a.wg_begin = qb;
+    const int ks = (f.ksplit > 1 && f.part) ? std::min(f.ksplit, std::max(1, g.Bpad / 32)) : 1;
+    if (ks > 1) {   // few expert tiles (a narrow expert shard under a wide minibatch): every half-tile's K range split over ks workgroups (k_out_dw_q<.., SPLIT>), k_out_dw_finish adds the parts and runs the epilogue
+        a.ksplit = ks; a.part = f.part; a.slab = (int64_t)qgrid * QTC * 128; a.part_row0 = qb * QTC;
+        const int64_t nq = (int64_t)qgrid * QTC * 128 / 4;
+        with_flag(f.bayes, [&](auto by) {
+            constexpr bool BY = decltype(by)::value;      // (the Adam flag is k_out_dw_finish's: the SPLIT form has no epilogue)
+            launch_lds(k_out_dw_q<BY, false, false, true>, dim3(qgrid * ks), dim3(64 * QW), dw_q_lds(BY), st, a);
+            with_flag(f.adam, [&](auto ad) { hipLaunchKernelGGL((k_out_dw_finish<BY, decltype(ad)::value>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, a); });
+        });
+        a.ksplit = 1; a.wg_begin = wg256; a.part_row0 = 0;
+        return;
+    }
+    // two half-tile workgroups per CU, the epilogue of one beside the main loop of the other (k_out_dw_q)
+    static int n_cu = 0;
+    if (!n_cu) { int dev = 0; hipGetDevice(&dev); hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu <= 0) n_cu = 256; }
+    static const int stagger_q = getenv("NTF_DW_STAGGER") ? atoi(getenv("NTF_DW_STAGGER")) : -1;   // 10 ns ticks; default: half of a tile's main loop + epilogue
+    const int nib = g.Bpad / 32;
+    a.ntile = 2 * n_cu;
+    a.stagger = (f.adam && qgrid > n_cu) ? (stagger_q >= 0 ? stagger_q : (nib * 140 + 4500) / 2) : 0;
+    bool stamped = false;
+#ifdef NTF_DIAG
+    stamped = launch_dw_q_stamped(st, f, a, qgrid);
+#endif
+    if (!stamped) with_flag(f.bayes, [&](auto by) { with_flag(f.adam, [&](auto ad) {
+        constexpr bool BY = decltype(by)::value, AD = decltype(ad)::value;
+        launch_lds(k_out_dw_q<BY, AD>, dim3(qgrid), dim3(64 * QW), dw_q_lds(BY), st, a);
+    }); });
+    a.wg_begin = wg256; a.ntile = 0; a.stagger = 0;
+}
+// fp16x3 on f32 dz: H = 32, 64; H = 128 without the packed forward kernel
+static void launch_dw_b6(hipStream_t st, const FusedDw& f, const DwArgs& a, int grid) {
+    with_value<128, 64, 32>(f.H, [&](auto h) { with_flag(f.bayes, [&](auto by) { with_flag(f.adam, [&](auto ad) {
+        constexpr int H = decltype(h)::value; constexpr bool BY = decltype(by)::value, AD = decltype(ad)::value;
+        launch_lds(k_out_dw_b6<H, BY, AD>, dim3(grid), dim3(64 * DW_WAVES), dw_b6_lds(H, BY), st, a);
+    }); }); });
+}
+// exact f32: the step's kernel (rmode 0), or the fallback behind a split-product launch (rmode 2: it runs only when the range flag is raised) on one round of workgroups
+static void launch_dw_f32(hipStream_t st, const FusedDw& f, DwArgs a, int grid) {
+    a.ntile = grid;
+    const bool fb = a.rmode == 2;
+    with_value<128, 64, 32>(f.H, [&](auto h) { with_flag(f.bayes, [&](auto by) { with_flag(f.adam, [&](auto ad) {
+        constexpr int H = decltype(h)::value; constexpr bool BY = decltype(by)::value, AD = decltype(ad)::value;
+        launch_lds(fb ? k_out_dw_fallback<H, BY, AD> : k_out_dw<H, BY, AD>, dim3(fb ? std::min(grid, 256) : grid), dim3(64 * DW_WAVES), dw_f32_lds(H, BY), st, a);
+    }); }); });
+}
+
+void launch_fused_out_dw(hipStream_t st, const FusedDw& f) {
+    const Geom g = geom(f.B, f.M);
+    const int total = (f.M + DW_TC - 1) / DW_TC;
+    const int grid = f.wg_count > 0 ? std::min(f.wg_count, total - f.wg_begin) : total;
+    if (grid <= 0) return;
+    DwArgs a = dw_args(f, g);
+    const bool guard = f.split && f.rflag != nullptr;
     const int Ht = fused_tmpl(f.H);
     const bool pad = Ht != f.H;       // 96, 160, 192, 224: the PAD forms of the exact-f32 kernels, in every arithmetic mode (no split-product form at these widths)
-    a.Hr = f.H;
-    if (Ht == 256) {   // exact-f32 only (no split-product kernels at this width): each 256-expert tile as two hidden-half workgroups
-        const size_t lds = 2 * ((size_t)DW_TC * 32 * 4 + (size_t)(f.bayes ? 2 : 1) * 32 * 4 * 128);
-#define NTF_DWH(BY, AD) do { auto kf = k_out_dw_h2<BY, AD>; set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);              \
-        hipLaunchKernelGGL(kf, dim3(grid, 2), dim3(64 * DW_WAVES), lds, st, a); } while (0)
-#define NTF_DWHP(BY, AD) do { auto kf = k_out_dw_h2<BY, AD, true>; set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);       \
-        hipLaunchKernelGGL(kf, dim3(grid, 2), dim3(64 * DW_WAVES), lds, st, a); } while (0)
-        if (pad) { if (f.bayes) { if (f.adam) NTF_DWHP(true, true); else NTF_DWHP(true, false); } else { if (f.adam) NTF_DWHP(false, true); else NTF_DWHP(false, false); } }
-        else
-        if (f.bayes) { if (f.adam) NTF_DWH(true, true); else NTF_DWH(true, false); } else { if (f.adam) NTF_DWH(false, true); else NTF_DWH(false, false); }
-#undef NTF_DWHP
-#undef NTF_DWH
-        return;
-    }
-    if (pad) {      // 96 on H = 128's exact-f32 kernel
-        const size_t lds = 2 * ((size_t)DW_TC * 32 * 4 + (size_t)(f.bayes ? 2 : 1) * 32 * 4 * 128);
-#define NTF_DWP(BY, AD) do { auto kf = k_out_dw<128, BY, AD, true>; set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);      \
-        hipLaunchKernelGGL(kf, dim3(grid), dim3(64 * DW_WAVES), lds, st, a); } while (0)
-        if (f.bayes) { if (f.adam) NTF_DWP(true, true); else NTF_DWP(true, false); } else { if (f.adam) NTF_DWP(false, true); else NTF_DWP(false, false); }
-#undef NTF_DWP
-        return;
-    }
-    if (f.split && f.dz_packed) {   // fp16x3 step, H = 128: the forward kernel left packed plane pairs in dzT
-        a.a_scale = f.a_scale; a.unscale = 1.f / (f.a_scale * f.h_scale); a.rmode = guard ? 1 : 0;
-        const int ks = (f.ksplit > 1 && f.part) ? std::min(f.ksplit, std::max(1, g.Bpad / 32)) : 1;
-        if (ks > 1) {   // few expert tiles (a narrow expert shard under a wide minibatch): every half-tile's K range split over ks workgroups (k_out_dw_q<.., SPLIT>), k_out_dw_finish adds the parts and runs the epilogue
-            a.sinT = reinterpret_cast<const uint32_t*>(ws + w.sinT);
-            const int total_q = (f.M + QTC - 1) / QTC, qb = f.wg_count > 0 ? 2 * f.wg_begin : 0;
-            const int qgrid = f.wg_count > 0 ? std::min(2 * f.wg_count, total_q - qb) : total_q;
-            const int wg256 = a.wg_begin;
-            a.wg_begin = qb;
-            a.ksplit = ks; a.part = f.part; a.slab = (int64_t)qgrid * QTC * 128; a.part_row0 = qb * QTC;
-            const size_t ldsq = 2 * ((size_t)QTC * 128 + 2 * 128 * 64 + (f.bayes ? 1024 : 0)) + 64;
-            const int64_t nq = (int64_t)qgrid * QTC * 128 / 4;
-#define NTF_DWQS(BY, AD) do { auto kf = k_out_dw_q<BY, false, false, true>;                                                    \
-            set_max_lds(reinterpret_cast<const void*>(kf), (int)ldsq);     \
-            hipLaunchKernelGGL(kf, dim3(qgrid * ks), dim3(64 * QW), ldsq, st, a);                                              \
-            hipLaunchKernelGGL((k_out_dw_finish<BY, AD>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, a); } while (0)
-            if (f.bayes) { if (f.adam) NTF_DWQS(true, true); else NTF_DWQS(true, false); } else { if (f.adam) NTF_DWQS(false, true); else NTF_DWQS(false, false); }
-#undef NTF_DWQS
-            if (!guard) return;
-            a.rmode = 2; a.ksplit = 1; a.wg_begin = wg256; a.part_row0 = 0;
-            goto exact_f32;
-        }
-        {   // two half-tile workgroups per CU, the epilogue of one beside the main loop of the other (k_out_dw_q)
-            a.sinT = reinterpret_cast<const uint32_t*>(ws + w.sinT);
-            const int total_q = (f.M + QTC - 1) / QTC, qb = f.wg_count > 0 ? 2 * f.wg_begin : 0;
-            const int qgrid = f.wg_count > 0 ? std::min(2 * f.wg_count, total_q - qb) : total_q;
-            const int wg256 = a.wg_begin;
-            a.wg_begin = qb;
-            static int n_cu = 0;
-            if (!n_cu) { int dev = 0; hipGetDevice(&dev); hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu <= 0) n_cu = 256; }
-            static const int stagger_q = getenv("NTF_DW_STAGGER") ? atoi(getenv("NTF_DW_STAGGER")) : -1;   // 10 ns ticks; default: half of a tile's main loop + epilogue
-            const int nib = g.Bpad / 32;
-            a.ntile = 2 * n_cu;
-            a.stagger = (f.adam && qgrid > n_cu) ? (stagger_q >= 0 ? stagger_q : (nib * 140 + 4500) / 2) : 0;
-            const size_t ldsq = 2 * ((size_t)QTC * 128 + 2 * 128 * 64 + (f.bayes ? 1024 : 0)) + 64;
-#define NTF_DWQ(BY, AD) do { auto kf = k_out_dw_q<BY, AD>;                                                                     \
-            set_max_lds(reinterpret_cast<const void*>(kf), (int)ldsq);     \
-            hipLaunchKernelGGL(kf, dim3(qgrid), dim3(64 * QW), ldsq, st, a); } while (0)
-#ifdef NTF_DIAG
-            static const char* stamp_file = getenv("NTF_DW_STAMP_FILE");   // -DNTF_DIAG builds: the 30th launch's per-wave stamps, raw (10 x u64 per wave), to this file (profiles/dw_stamps.py)
-#else
-            static const char* stamp_file = nullptr;
-#endif
-            if (stamp_file && f.bayes && f.adam) {
-                static unsigned long long* d_st = nullptr; static int n_launch = 0;
-                if (!d_st) hipMalloc(&d_st, (size_t)qgrid * QW * 10 * 8);
-                a.stamps = d_st;
-                auto kf = k_out_dw_q<true, true, true>;
-                set_max_lds(reinterpret_cast<const void*>(kf), (int)ldsq);
-                hipLaunchKernelGGL(kf, dim3(qgrid), dim3(64 * QW), ldsq, st, a);
-                if (++n_launch == 30) {
-                    std::vector<unsigned long long> hst((size_t)qgrid * QW * 10);
-                    hipStreamSynchronize(st); hipMemcpy(hst.data(), d_st, hst.size() * 8, hipMemcpyDeviceToHost);
-                    if (FILE* fp = fopen(stamp_file, "wb")) { fwrite(hst.data(), 8, hst.size(), fp); fclose(fp); }
-                }
-            }
-            else if (f.bayes) { if (f.adam) NTF_DWQ(true, true); else NTF_DWQ(true, false); } else { if (f.adam) NTF_DWQ(false, true); else NTF_DWQ(false, false); }
-#undef NTF_DWQ
-            if (!guard) return;
-            a.rmode = 2; a.wg_begin = wg256; a.ntile = 0; a.stagger = 0;   // the exact-f32 kernel behind it runs only when the range flag is raised
-            goto exact_f32;
-        }
-    }
+    if (Ht == 256) return launch_dw_h2(st, f, a, grid, pad);
+    if (pad) return launch_dw_pad128(st, f, a, grid);
     if (f.split) {
         a.rmode = guard ? 1 : 0;
-        a.a_scale = f.a_scale; a.unscale = 1.f / (f.a_scale * f.h_scale);
-#define NTF_DWB1(HH, BY, AD) do { auto kf = k_out_dw_b6<HH, BY, AD>; const size_t lds = 2 * ((size_t)DW_TC * 128 + (size_t)(BY ? 2 : 1) * 2 * HH * 64); \
-        set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);                                      \
-        hipLaunchKernelGGL(kf, dim3(grid), dim3(64 * DW_WAVES), lds, st, a); } while (0)
-#define NTF_DWB(HH) do { if (f.bayes) { if (f.adam) NTF_DWB1(HH, true, true); else NTF_DWB1(HH, true, false); }                                            \
-                         else { if (f.adam) NTF_DWB1(HH, false, true); else NTF_DWB1(HH, false, false); } } while (0)
-        if (f.H == 128) NTF_DWB(128); else if (f.H == 64) NTF_DWB(64); else NTF_DWB(32);
-#undef NTF_DWB
-#undef NTF_DWB1
+        if (f.dz_packed) launch_dw_q(st, f, a, g); else launch_dw_b6(st, f, a, grid);
         if (!guard) return;
-        a.rmode = 2;   // fall through: the exact-f32 kernel, which runs only when the range flag is raised
+        a.rmode = 2;   // the exact-f32 kernel behind it
     }
-exact_f32:
-    a.ntile = grid;
-#define NTF_DW1(HH, BY) do { const bool fb = a.rmode == 2;                                                                                    \
-        auto kf = fb ? (f.adam ? k_out_dw_fallback<HH, BY, true> : k_out_dw_fallback<HH, BY, false>) : (f.adam ? k_out_dw<HH, BY, true> : k_out_dw<HH, BY, false>);   \
-        const size_t lds = 2 * (DW_TC * 32 * 4 + (BY ? 2 : 1) * 32 * 4 * HH);                                                                \
-        set_max_lds(reinterpret_cast<const void*>(kf), (int)lds);                      \
-        hipLaunchKernelGGL(kf, dim3(fb ? std::min(grid, 256) : grid), dim3(64 * DW_WAVES), lds, st, a); } while (0)
-#define NTF_DW(HH) do { if (f.bayes) NTF_DW1(HH, true); else NTF_DW1(HH, false); } while (0)
-    if (f.H == 128) NTF_DW(128); else if (f.H == 64) NTF_DW(64); else NTF_DW(32);
-#undef NTF_DW
+    launch_dw_f32(st, f, a, grid);
 }
 
 // fp16 split planes of the hidden activations for the dW kernel (once per step, after launch_fused_out_fwd's phase 1)

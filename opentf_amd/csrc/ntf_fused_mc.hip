@@ -4,8 +4,6 @@
 
 namespace ntf {
 
-constexpr int BN6 = 32;   // experts per tile, as k_out_fwd_b6 (ntf_fused.hip)
-
 // ------------------------------------------------------------------------------------------------
 // k_out_probs_mc (NTF_INFER_MC=1): the Flipout inference form of k_out_fwd_b6 (<true, false, false, false, PROBS>) with the Monte-Carlo passes INSIDE the kernel.
 // k_out_fwd_b6 reads and rewrites every running sum of the transposed [experts x batch] buffer once per pass (pold: 0.93 GB each way at config 2, B = 1000); here a
@@ -199,9 +197,7 @@ void launch_fused_probs_mc(hipStream_t st, const FusedProbsMc& f) {
         const FusedMcPass& s = f.pass[k];
         a.ps[k] = McPassArgs{s.hz, s.wp_pl, s.bp, s.s_out.k0, s.s_out.k1, s.s_in.k0, s.s_in.k1};
     }
-    const size_t lds = (size_t)2 * (2 * 2 * BN6 * 128 * 2 + 512);
-    set_max_lds(reinterpret_cast<const void*>(k_out_probs_mc), (int)lds);
-    hipLaunchKernelGGL(k_out_probs_mc, dim3(g.NRB * o.NCG), dim3(256), lds, st, a);
+    launch_lds(k_out_probs_mc, dim3(g.NRB * o.NCG), dim3(256), fwd_b6_lds(true), st, a);
 }
 
 }  // namespace ntf

@@ -11,6 +11,7 @@
 // Workgroup 0 adds the hidden layer's KL; extra workgroups behind the row blocks are the operand producer of the output layer's BIAS (rho_b -> sigma eps, KL).
 #include "ntf_head.h"
 #include "ntf_device.h"
+#include "ntf_host.h"
 #include <algorithm>
 
 namespace ntf {
@@ -249,10 +250,9 @@ void launch_head(hipStream_t st, const HeadArgs& a) {
     p.nrb = p.Bpad / 32;
     const int nbias = (p.bayes && p.M > 0) ? (int)std::min<int64_t>(((p.M + 3) / 4 + 255) / 256, 512) : 0;
     const size_t lds = (size_t)(32 * (p.D + 1) + 32 * HS_LD) * 4 + 32 * 4 * 4;
-#define NTF_HEAD_D(DD) do { if (p.bayes) hipLaunchKernelGGL((k_head<true, DD>), dim3(p.nrb + nbias), dim3(256), lds, st, p);   \
-                            else hipLaunchKernelGGL((k_head<false, DD>), dim3(p.nrb), dim3(256), lds, st, p); } while (0)
-    if (p.D == 64) NTF_HEAD_D(64); else if (p.D == 128) NTF_HEAD_D(128); else NTF_HEAD_D(256);
-#undef NTF_HEAD_D
+    with_value<64, 128, 256>(p.D, [&](auto d) { with_flag(p.bayes != 0, [&](auto by) {   // (Flipout: the bias workgroups behind the row blocks)
+        hipLaunchKernelGGL((k_head<decltype(by)::value, decltype(d)::value>), dim3(p.nrb + (decltype(by)::value ? nbias : 0)), dim3(256), lds, st, p);
+    }); });
 }
 
 }  // namespace ntf

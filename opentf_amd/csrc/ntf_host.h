@@ -1,5 +1,5 @@
 // The host scaffold of every entry of the library, once: the check macros and allocators of a handle with an `err` string (ntf_engine, ntf_n2v, ntf_d2v,
-// ntf_knn), the RAII device buffer of the handle-less entries (ntf_metrics, ntf_auc, ntf_cooc), the upload of a host table into padded device rows and the dispatch of a row width onto the kernels' NV template argument.
+// ntf_knn), the RAII device buffer of the handle-less entries (ntf_metrics, ntf_auc, ntf_cooc), the upload of a host table into padded device rows and the dispatch of run-time widths and flags onto the kernels' template arguments.
 #pragma once
 #include "../../include/opentf_amd.h"
 #include <hip/hip_runtime.h>
@@ -68,5 +68,9 @@ template <int LO = 1, class F> bool with_nv(int nv, F&& f) {
     if (nv == 4) f(std::integral_constant<int, 4>());
     return true;
 }
+// a run-time flag as a compile-time one: f(std::true_type()) or f(std::false_type())
+template <class F> void with_flag(bool b, F&& f) { if (b) f(std::true_type()); else f(std::false_type()); }
+// a run-time v out of the set VS (the widths a launcher has kernels for) as f(std::integral_constant<int, v>()) and true; any other v calls nothing and gives false
+template <int... VS, class F> bool with_value(int v, F&& f) { return ((v == VS && (f(std::integral_constant<int, VS>()), true)) || ...); }
 
 }  // namespace ntf

@@ -292,11 +292,7 @@ extern "C" int ntf_knn_query(ntf_knn* h, const float* queries, int64_t n, int32_
             KnnSimArgs a;
             a.T = h->table; a.rinv_t = h->rinv; a.Q = h->q + g0 * dp; a.rinv_q = h->q_rinv + g0; a.S = h->ws; a.r0 = r0; a.ld = R; a.rr = rr; a.nq = ng; a.dp = (int)dp;
             const dim3 grid((unsigned)std::min<int64_t>((rr + KNN_RB - 1) / KNN_RB, (int64_t)h->n_cu * per_cu), (unsigned)((ng + nqt * 32 - 1) / (nqt * 32)));
-            switch (nqt) {
-                case 1: set_max_lds(reinterpret_cast<const void*>(k_knn_sims<1>), (int)lds); hipLaunchKernelGGL(k_knn_sims<1>, grid, dim3(KNN_WAVES * 64), lds, h->st, a); break;
-                case 2: set_max_lds(reinterpret_cast<const void*>(k_knn_sims<2>), (int)lds); hipLaunchKernelGGL(k_knn_sims<2>, grid, dim3(KNN_WAVES * 64), lds, h->st, a); break;
-                default: set_max_lds(reinterpret_cast<const void*>(k_knn_sims<4>), (int)lds); hipLaunchKernelGGL(k_knn_sims<4>, grid, dim3(KNN_WAVES * 64), lds, h->st, a); break;
-            }
+            with_value<1, 2, 4>(nqt, [&](auto q) { launch_lds(k_knn_sims<decltype(q)::value>, grid, dim3(KNN_WAVES * 64), lds, h->st, a); });
             hipLaunchKernelGGL(k_knn_select, dim3((unsigned)ng), dim3(1024), 0, h->st, h->ws, R, rr, r0, (int)topn, exclude ? h->q_excl + g0 : nullptr, h->run, r0 == 0 ? 1 : 0);
         }
         const int64_t ne = (int64_t)ng * topn;

@@ -120,14 +120,12 @@ __global__ __launch_bounds__(64) void k_out_special(SpecialArgs p) {
 }
 
 void launch_out_special(hipStream_t st, int H, bool bayes, bool train, bool dh, const SpecialArgs& s) {
-#define NTF_SPK(HH, BY) do { if (!train) hipLaunchKernelGGL((k_out_special<HH, BY, false, false>), dim3(s.B), dim3(64), 0, st, s);         \
-        else if (dh) hipLaunchKernelGGL((k_out_special<HH, BY, true, true>), dim3(s.B), dim3(64), 0, st, s);                                  \
-        else hipLaunchKernelGGL((k_out_special<HH, BY, true, false>), dim3(s.B), dim3(64), 0, st, s); } while (0)
-#define NTF_SPH(HH) do { if (bayes) NTF_SPK(HH, true); else NTF_SPK(HH, false); } while (0)
-    if (H == 256) NTF_SPH(256); else if (H == 128) NTF_SPH(128); else if (H == 64) NTF_SPH(64); else if (H == 32) NTF_SPH(32);
-    else if (H == 96) NTF_SPH(96); else if (H == 160) NTF_SPH(160); else if (H == 192) NTF_SPH(192); else NTF_SPH(224);
-#undef NTF_SPH
-#undef NTF_SPK
+    with_value<256, 128, 64, 32, 96, 160, 192, 224>(H, [&](auto hh) { with_flag(bayes, [&](auto by) {
+        constexpr int HH = decltype(hh)::value; constexpr bool BY = decltype(by)::value;
+        if (!train) hipLaunchKernelGGL((k_out_special<HH, BY, false, false>), dim3(s.B), dim3(64), 0, st, s);
+        else if (dh) hipLaunchKernelGGL((k_out_special<HH, BY, true, true>), dim3(s.B), dim3(64), 0, st, s);
+        else hipLaunchKernelGGL((k_out_special<HH, BY, true, false>), dim3(s.B), dim3(64), 0, st, s);
+    }); });
 }
 
 }  // namespace ntf

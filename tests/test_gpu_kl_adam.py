@@ -345,6 +345,7 @@ RHO_CASES = {     # name: dims, B, multihot
     "h128": ([64, 128, 20000], 160, False),
     "h128_split": ([64, 128, 3000], 600, False),      # max_batch >= 258 ks: room for the split-K partial slabs (ntf_engine.hip)
     "h128_high": ([64, 128, 3000], 150, False),
+    "h128_small": ([64, 128, 300], 40, False),        # just over one 256-expert tile and no multiple of 64, just over one 32-row block
     "h64": ([48, 64, 3000], 150, False),
     "h32": ([40, 32, 2000], 140, False),
     "h256": ([64, 256, 3000], 150, False),
@@ -354,7 +355,8 @@ RHO_CASES = {     # name: dims, B, multihot
 RHO_RUNS = [   # case, mode, fuse_adam, env
     ("h128", "default", 0, {}), ("h128", "default", 1, {}), ("h128", "default", 2, {}), ("h128_split", "default", 1, {"NTF_DW_KSPLIT": "2"}),
     ("h128", "f32", 1, {}), ("h64", "f32", 1, {}), ("h64", "default", 1, {}), ("h32", "f32", 1, {}), ("h32", "default", 0, {}),
-    ("h256", "default", 1, {}), ("h100_generic", "generic", 0, {}), ("two_hidden", "default", 1, {})
+    ("h256", "default", 1, {}), ("h100_generic", "generic", 0, {}), ("two_hidden", "default", 1, {}),
+    ("h128_small", "default", 1, {"NTF_FWD_KERNEL": "0"})      # k_out_fwd_b6's training form with d(hidden): the one launch branch of the fused output layer no other test runs
 ]
 _CACHE = {}
 
