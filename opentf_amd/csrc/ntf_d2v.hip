@@ -465,8 +465,10 @@ extern "C" int ntf_d2v_create(int device, int64_t n_docs, int64_t n_vocab, int32
 
 extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32_t negative, double alpha_start, double alpha_end, uint64_t epoch, int32_t serial,
                                    const int64_t* order, const double* progress, double* mean_loss, double* device_ms) {
-    if (!h || window < 1 || window > 255 || negative < 0 || negative > 8 || (dm != 0 && dm != 1)) return NTF_EINVAL;
-    if (!dm && 2 * window > 254) return NTF_EINVAL;
+    if (!h) { g_d2v_create_error = "d2v train: the handle is NULL"; return NTF_EINVAL; }
+    if (window < 1 || window > 255 || (!dm && 2 * window > 254)) FAIL(h, NTF_EINVAL, "d2v train: window outside 1..255 (dm = 0: 1..127: the unit index 1 + u of a window word is 8 bits of the Philox counter)");
+    if (negative < 0 || negative > 8) FAIL(h, NTF_EINVAL, "d2v train: negative outside 0..8");
+    if (dm != 0 && dm != 1) FAIL(h, NTF_EINVAL, "d2v train: dm is 0 or 1");
     HIPCHK(h, hipSetDevice(h->device));
     if (order) {
         std::vector<char> seen((size_t)h->n_docs, 0);
@@ -489,8 +491,9 @@ extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32
     const int64_t want = (h->n_docs + 3) / 4;
     const dim3 grid(serial ? 1u : (unsigned)std::min<int64_t>(want, 256 * 16)), block(serial ? 64 : 256);
     if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
-    // PV-DM at the reference's window (src/mdl/emb/__config__.yaml: w = 5): word-vector additions deferred to one per kept position (k_d2v_epoch<.., 5>); NTF_D2V_DEFER=0: the plain kernel
-    static const bool defer_ok = !(getenv("NTF_D2V_DEFER") && atoi(getenv("NTF_D2V_DEFER")) == 0);
+    // PV-DM at the reference's window (src/mdl/emb/__config__.yaml: w = 5): word-vector additions deferred to one per kept position (k_d2v_epoch<.., 5>); NTF_D2V_DEFER=0 (read per call): the plain kernel
+    const char* defer_env = getenv("NTF_D2V_DEFER");
+    const bool defer_ok = !(defer_env && atoi(defer_env) == 0);
     if (dm && window == 5 && defer_ok && h->dp >= 128) {     // (d = 64: the rows are 256 B and the plain kernel's shorter chain wins - 45.7 against 49.4 ms; d = 128 / 192 / 256: 55 / 78 / 98 against 66 / 102 / 133)
         with_nv<2>(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL((k_d2v_epoch<decltype(nv)::value, 5>), grid, block, 0, h->st, a, dm); });   // <1, 5> is never launched, so never built
     } else

@@ -1,6 +1,6 @@
 """Batched doc2vec infer_vector on the MI355X (opentf_amd/csrc/ntf_d2v.hip k_d2v_infer, ntf_d2v_infer; opentf_amd/mdl/emb/d2v.py D2v.infer_vecs): gensim 4.3.3's
-infer_vector as src/mdl/emb/d2v.py:96-98 calls it, with this build's Philox streams, against a sequential reference written out below (oracle/d2v_oracle.py has the
-draws, the key and the sigmoid table, but no inference pass)."""
+infer_vector as src/mdl/emb/d2v.py:96-98 calls it, with this build's Philox streams, against the sequential reference of tests/d2v_reference.py (oracle/d2v_oracle.py
+has the draws, the key and the sigmoid table, but no inference pass)."""
 import ctypes as C
 import functools
 
@@ -12,91 +12,11 @@ pytestmark = pytest.mark.gpu
 from oracle import d2v_oracle as D                      # noqa: E402
 from opentf_amd import libntf                           # noqa: E402
 from opentf_amd.mdl.emb import d2v as P                 # noqa: E402
+from d2v_reference import _query_words, _vocab60, reference_infer      # noqa: E402
 from test_d2v import _clustered, _toy_teamsvecs         # noqa: E402
 
 ALPHA, MIN_ALPHA, SEED = 0.025, 0.001, 11
 SIGMA = {9: 1.6, 64: 0.8, 100: 0.8, 128: 0.7, 256: 0.6}
-EPS = 2.0 ** -24
-
-
-def _bin(f):
-    """what the unit does with f: below / above the table, or its bin (the f32 arithmetic of D.sigmoid_table)"""
-    f = np.float32(f)
-    if f <= -D.MAX_EXP: return -1
-    if f >= D.MAX_EXP: return D.EXP_TABLE_SIZE
-    return int((f + np.float32(D.MAX_EXP)) * np.float32(D.EXP_TABLE_SIZE / D.MAX_EXP / 2))
-
-
-def reference_infer(q_ptr, q_words, ids, init, wv, s1, sample_int, cum, dm, window, negative, epochs, alpha, min_alpha, seed):
-    """the issue's / the header's semantics, one query after the other: f32 vectors, f in f64 rounded once.  -> (out [n, d], flagged units per query, units, units
-    skipped for |f| >= 6).  A unit is flagged when f lies within 16 * 2^-24 * sum |l1_q syn1neg_q| of a bin edge or of +-6: the device sums f in another order (at
-    most 4 sequential adds, 6 tree levels, 1 product rounding; headroom for the drift of v), and another bin is a discrete jump, not rounding."""
-    n = len(q_ptr) - 1
-    out = np.array(init, dtype=np.float32, copy=True)
-    flagged = np.zeros(n, dtype=np.int64)
-    units = skipped = 0
-    delta = (alpha - min_alpha) / max(epochs - 1, 1)
-    si = [int(x) for x in sample_int]
-    for i in range(n):
-        v = out[i].copy()
-        doc = int(ids[i]) if ids is not None else i
-        w = [int(x) for x in q_words[q_ptr[i]:q_ptr[i + 1]]]
-        a = alpha
-        for e in range(epochs):
-            key = D.epoch_key(seed, e)
-            af = np.float32(a)
-            kept = [x for p, x in enumerate(w) if si[x] >= D.draw(key, doc, p, 0, D.SLOT_KEEP)[0]][:D.MAX_DOCUMENT_LEN]
-            K = len(kept)
-            for pos in range(K):
-                b = D.draw(key, doc, pos, 0, D.SLOT_WINDOW)[0] % window
-                lo, hi = max(0, pos - window + b), min(K, pos + window + 1 - b)
-                if dm:
-                    l1 = v.copy()
-                    for m in range(lo, hi):
-                        if m != pos: l1 += wv[kept[m]]
-                    l1 *= np.float32(1.0) / np.float32(hi - lo)
-                else:
-                    l1 = v
-                work = np.zeros_like(v)
-                r = D.draw(key, doc, pos, 0, D.SLOT_NEG0) + D.draw(key, doc, pos, 0, D.SLOT_NEG1)
-                for k in range(negative + 1):
-                    if k == 0: t, label = kept[pos], np.float32(1)
-                    else:
-                        t = int(np.searchsorted(cum, np.uint32(r[k - 1] % int(cum[-1])), side="left"))
-                        if t == kept[pos]: continue
-                        label = np.float32(0)
-                    prod = l1.astype(np.float64) * s1[t].astype(np.float64)
-                    f64 = float(prod.sum())
-                    margin = 16 * EPS * float(np.abs(prod).sum())
-                    units += 1
-                    if _bin(f64 - margin) != _bin(f64 + margin): flagged[i] += 1
-                    f = np.float32(f64)
-                    if f <= -D.MAX_EXP or f >= D.MAX_EXP:
-                        skipped += 1
-                        continue
-                    g = np.float32((label - D.sigmoid_table(f)) * af)
-                    work += g * s1[t]
-                v = v + work
-            a -= delta
-        out[i] = v
-    return out, flagged, units, skipped
-
-
-POP = 1.0 / (np.arange(60) + 1.0) ** 1.5
-POP /= POP.sum()
-
-
-def _vocab60():
-    """sample_int / cum_table of a 60-word Zipf corpus at sample = 0.05: the two most frequent words (vocabulary indices 0 and 1) are dropped 54 % and 9 % of the time"""
-    words = np.random.default_rng(0).choice(60, 20000, replace=True, p=POP).astype(np.int64)
-    keys, count, si, cum, wi = P.build_vocab(words, sample=0.05)
-    assert len(keys) == 60 and si[0] < 0.6 * 2 ** 32 and si[1] < 2 ** 32 - 1
-    return si, cum
-
-
-def _query_words(rng, n):
-    """vocabulary indices drawn by the corpus' own frequencies (index = frequency rank): the subsampled words are the common ones"""
-    return rng.choice(60, n, replace=True, p=POP).astype(np.int32)
 
 
 @functools.lru_cache(maxsize=None)
