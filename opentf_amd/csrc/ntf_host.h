@@ -1,5 +1,5 @@
 // The host scaffold of every entry of the library, once: the check macros and allocators of a handle with an `err` string (ntf_engine, ntf_n2v, ntf_d2v,
-// ntf_knn), the RAII device buffer of the handle-less entries (ntf_metrics, ntf_auc, ntf_cooc), the upload of a host table into padded device rows and the dispatch of run-time widths and flags onto the kernels' template arguments.
+// ntf_knn, ntf_link), the RAII device buffer of the handle-less entries (ntf_metrics, ntf_auc, ntf_cooc), the upload of a host table into padded device rows and the dispatch of run-time widths and flags onto the kernels' template arguments.
 #pragma once
 #include "../../include/opentf_amd.h"
 #include <hip/hip_runtime.h>

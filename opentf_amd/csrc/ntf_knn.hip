@@ -1,8 +1,7 @@
 // Batched cosine nearest-neighbour search over a resident [n_rows, d] f32 table on the MI355X (include/opentf_amd.h ntf_knn_*): what
 // KeyedVectors.most_similar (opentf_amd/mdl/emb/d2v.py, the second half of the reference's infer_d2v, src/mdl/emb/d2v.py:96-98) does one query at a time on the host.
 //   k_knn_norms   reciprocal row norms (once per table at create, once per call for the queries)
-//   k_knn_sims    sims of a query group against a row range into the workspace, exact-f32 MFMA (v_mfma_f32_32x32x2_f32): the query chunk resident in LDS,
-//                 the table streamed with 16-byte loads through a wave-private LDS stage that gives the MFMA operand its [row][k] -> lane transpose
+//   k_sims        (ntf_sims.h, shared with the link decode; the cosine epilogue) sims of a query group against a row range into the workspace, exact-f32 MFMA
 //   k_knn_select  per (query, range): the topn largest of the range by (sim desc, id asc), merged into the query's running list by the same 64-bit composite
 //   k_knn_finish  running lists -> ids and sims
 // [n, n_rows] is never formed: the workspace holds [query group, row range] and is sized by the caller's budget alone.
@@ -11,6 +10,7 @@
 #include "ntf_fused_common.h"
 #include "ntf_host.h"
 #include "ntf_select.h"
+#include "ntf_sims.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -36,126 +36,30 @@ static thread_local std::string g_knn_create_error;
 extern "C" const char* ntf_knn_last_error(const ntf_knn* h) { return h ? h->err.c_str() : g_knn_create_error.c_str(); }
 
 namespace {
-constexpr int KNN_KC = 32;               // k-chunk: floats of a row staged at a time (one 128-B line a row); rows are padded to a multiple of it
-constexpr int KNN_SLD = KNN_KC + 1;      // odd LDS row stride: the fragment reads (32 lanes = 32 rows, same k) hit 32 different banks
-constexpr int KNN_WAVES = 8;             // waves a workgroup, 32 table rows each
-constexpr int KNN_RB = KNN_WAVES * 32;   // table rows a workgroup takes at a time (the row unit of the workspace plan)
-constexpr int KNN_QUNIT = 32;            // the query unit of the workspace plan
-constexpr int KNN_MAX_GROUP = 1024;      // queries a group holds at most
-constexpr int64_t KNN_MAX_RANGE = 262144;   // rows a range holds at most: a selection workgroup walks one (query, range) row of sims
-
 // ---- reciprocal norms: n2 = one k-ordered fmaf chain from 0, rinv = 1 / sqrt(n2) (IEEE sqrt, IEEE divide), 0 when n2 < FLT_MIN.  flag |= 1: a non-finite value, |= 2: n2 overflows.
 // One thread a row keeps the chain sequential; the rows come through LDS in 32-float chunks so that the global reads are whole 128-B lines (8 lanes a row, 16 bytes each)
 // and the chain's reads - 256 rows at the same k, odd stride - hit different banks.  The pad columns are zeros: fmaf(0, 0, n2) = n2.
 __global__ __launch_bounds__(256) void k_knn_norms(const float* __restrict__ T, int64_t n, int d, int dp, float* __restrict__ rinv, int* __restrict__ flag) {
-    __shared__ float tile[256 * KNN_SLD];
+    __shared__ float tile[256 * SIM_SLD];
     const int tid = threadIdx.x;
     const int64_t i0 = (int64_t)blockIdx.x * 256, i = i0 + tid;
     float n2 = 0.f; bool bad = false;
-    for (int k0 = 0; k0 < dp; k0 += KNN_KC) {
+    for (int k0 = 0; k0 < dp; k0 += SIM_KC) {
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int r = j * 32 + (tid >> 3), k = (tid & 7) * 4;
             const float4 v = (i0 + r < n) ? *reinterpret_cast<const float4*>(T + (i0 + r) * dp + k0 + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-            float* s = tile + r * KNN_SLD + k;
+            float* s = tile + r * SIM_SLD + k;
             s[0] = v.x; s[1] = v.y; s[2] = v.z; s[3] = v.w;
         }
         __syncthreads();
-        for (int k = 0; k < KNN_KC; ++k) { const float v = tile[tid * KNN_SLD + k]; bad |= !(fabsf(v) <= FLT_MAX); n2 = fmaf(v, v, n2); }
+        for (int k = 0; k < SIM_KC; ++k) { const float v = tile[tid * SIM_SLD + k]; bad |= !(fabsf(v) <= FLT_MAX); n2 = fmaf(v, v, n2); }
     }
     if (i >= n) return;
     if (bad) atomicOr(flag, 1);
     else if (!(n2 <= FLT_MAX)) atomicOr(flag, 2);
     rinv[i] = n2 < FLT_MIN ? 0.f : 1.f / sqrtf(n2);
-}
-
-struct KnnSimArgs {
-    const float *T, *rinv_t, *Q, *rinv_q;   // Q / rinv_q: the group's first query
-    float* S;                               // [group, ld] sims of the range
-    int64_t r0, ld; int rr, nq, dp;         // the range [r0, r0 + rr), queries in the group, row stride
-};
-
-// NQT 32-query tiles resident a workgroup (blockIdx.y picks the chunk of the group); blockIdx.x strides over the range's 256-row blocks.
-// MFMA operands: A = queries (lane: query lane & 31, k = 2 s + (lane >> 5)), B = table rows (lane: row lane & 31, same k) - so the accumulator's lane axis is the
-// table row and a store of one accumulator register is two 128-B runs of a query's sims row.  Step s of the chain takes k = 2 s then 2 s + 1: k-ordered from 0.
-template <int NQT>
-__global__ __launch_bounds__(KNN_WAVES * 64) void k_knn_sims(KnnSimArgs a) {
-    extern __shared__ float smem[];
-    const int qld = a.dp + 1;
-    float* Qs = smem;                                         // [NQT * 32][dp + 1]
-    float* rqs = Qs + NQT * 32 * qld;                         // [NQT * 32]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* stage = rqs + NQT * 32 + wave * (32 * KNN_SLD);    // [32][33], private to the wave
-    const int q0 = blockIdx.y * (NQT * 32);
-    for (int e = tid; e < NQT * 32 * a.dp; e += blockDim.x) {
-        const int q = e / a.dp, k = e - q * a.dp;
-        Qs[q * qld + k] = (q0 + q < a.nq) ? a.Q[(int64_t)(q0 + q) * a.dp + k] : 0.f;
-    }
-    for (int q = tid; q < NQT * 32; q += blockDim.x) rqs[q] = (q0 + q < a.nq) ? a.rinv_q[q0 + q] : 0.f;
-    __syncthreads();
-    const int nkc = a.dp / KNN_KC, nrb = (a.rr + KNN_RB - 1) / KNN_RB;
-    const int lrow = lane >> 3, lk = (lane & 7) * 4;          // staging: 8 lanes a row of the chunk, 8 rows an instruction
-    const float* aq = Qs + (lane & 31) * qld + (lane >> 5);
-    const float* bs = stage + (lane & 31) * KNN_SLD + (lane >> 5);
-    for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
-        const int w0 = rb * KNN_RB + wave * 32;               // the wave's first row inside the range
-        if (w0 >= a.rr) continue;                             // (no workgroup barrier below)
-        const float* Tw = a.T + (a.r0 + w0) * a.dp;
-        float4 pre[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = j * 8 + lrow;
-            pre[j] = (w0 + r < a.rr) ? *reinterpret_cast<const float4*>(Tw + (int64_t)r * a.dp + lk) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        f32x16 acc[NQT];
-#pragma unroll
-        for (int t = 0; t < NQT; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-        for (int kc = 0; kc < nkc; ++kc) {
-            __builtin_amdgcn_wave_barrier();                  // the previous chunk's fragment reads are issued before the stage is overwritten
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float* s = stage + (j * 8 + lrow) * KNN_SLD + lk;
-                s[0] = pre[j].x; s[1] = pre[j].y; s[2] = pre[j].z; s[3] = pre[j].w;
-            }
-            __builtin_amdgcn_wave_barrier();
-            if (kc + 1 < nkc) {                               // the next chunk's loads fly under this chunk's MFMAs
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int r = j * 8 + lrow;
-                    pre[j] = (w0 + r < a.rr) ? *reinterpret_cast<const float4*>(Tw + (int64_t)r * a.dp + (kc + 1) * KNN_KC + lk) : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            }
-            const float* ak = aq + kc * KNN_KC;
-#pragma unroll 4
-            for (int s = 0; s < KNN_KC / 2; ++s) {
-                const float b = bs[2 * s];
-#pragma unroll
-                for (int t = 0; t < NQT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[t * 32 * qld + 2 * s], b, acc[t], 0, 0, 0);
-            }
-        }
-        const int row = w0 + (lane & 31);
-        if (row < a.rr) {
-            const float rt = a.rinv_t[a.r0 + row];
-            // register r of tile t is query 32 t + 8 (r >> 2) + 4 (lane >> 5) + (r & 3); group x range <= 2^28 floats, so the offsets are 32-bit
-            int ldi = (int)a.ld;
-            asm volatile("" : "+v"(ldi));       // kept in a vector register: 64 scalar multiples of it, one per store, do not fit the scalar file
-            int ql = 4 * (lane >> 5), off = (q0 + ql) * ldi + row;
-#pragma unroll
-            for (int t = 0; t < NQT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float rq = rqs[ql];                 // (a query past the group's last has rq = 0: its row of the workspace exists, the workspace holds whole chunks)
-                    float sim = (acc[t][r] * rq) * rt;
-                    if (rq == 0.f || rt == 0.f || sim == 0.f) sim = 0.f;           // a norm below FLT_MIN scores 0 with everything; -0 is returned as +0
-                    a.S[off] = sim;
-                    const int step = (r & 3) == 3 ? 5 : 1;
-                    ql += step; off += step * ldi;
-                }
-        }
-    }
 }
 
 // One workgroup per query of the group: the K largest of its sims row S[q, 0 .. M) by the composite (key << 32) | (0x7fffffff - id), id = r0 + column, the
@@ -164,21 +68,10 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void k_knn_sims(KnnSimArgs a) {
 __global__ __launch_bounds__(1024) void k_knn_select(const float* __restrict__ S, int64_t ld, int M, int64_t r0, int K, const int32_t* __restrict__ excl,
                                                      unsigned long long* __restrict__ run, int first) {
     __shared__ SelShared sh;
-    unsigned long long* keys = sh.keys;
     const int64_t i = blockIdx.x;
-    const int tid = threadIdx.x, NT = blockDim.x;
     const int64_t ex = excl ? (int64_t)excl[i] - r0 : -1;     // the excluded column of this range, if it lies in it
     const int n2 = select_topk_row<SignedKey, true>(sh, S + i * ld, M, K, r0, ex);
-    // keys[0 .. K): the range's candidates, sorted.  Merge with the running list: 2 n2 <= 4096 composites, sorted again
-    unsigned long long* mine = run + i * K;
-    if (!first) {
-        __syncthreads();
-        for (int k = tid; k < n2; k += NT) keys[n2 + k] = k < K ? mine[k] : 0ull;
-        for (int k = K + tid; k < n2; k += NT) keys[k] = 0ull;
-        __syncthreads();
-        bitonic_desc(keys, 2 * n2, tid, NT);
-    }
-    for (int k = tid; k < K; k += NT) mine[k] = keys[k];
+    merge_running(sh, n2, K, run + i * K, first);
 }
 
 __global__ void k_knn_finish(const unsigned long long* __restrict__ run, int64_t n, int32_t* __restrict__ idx, float* __restrict__ sims) {
@@ -189,7 +82,6 @@ __global__ void k_knn_finish(const unsigned long long* __restrict__ run, int64_t
     sims[e] = c ? SignedKey::value((unsigned)(c >> 32)) : -INFINITY;
 }
 
-size_t knn_sims_lds(int nqt, int dp) { return ((size_t)nqt * 32 * (dp + 1) + (size_t)nqt * 32 + (size_t)KNN_WAVES * 32 * KNN_SLD) * sizeof(float); }
 }  // namespace
 
 extern "C" void ntf_knn_destroy(ntf_knn* h) {
@@ -213,7 +105,7 @@ extern "C" int ntf_knn_create(int device, const float* table, int64_t n_rows, in
     if (device < 0 || device >= ndev) { g_knn_create_error = "no such HIP device (there is no CPU fallback)"; return NTF_EHIP; }
     hipSetDevice(device);
     ntf_knn* h = new ntf_knn();
-    h->device = device; h->n_rows = n_rows; h->d = d; h->dp = (d + KNN_KC - 1) / KNN_KC * KNN_KC;
+    h->device = device; h->n_rows = n_rows; h->d = d; h->dp = (d + SIM_KC - 1) / SIM_KC * SIM_KC;
     const int64_t dp = h->dp;
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->n_cu < 1) h->n_cu = 256;
     if (hipStreamCreate(&h->st) != hipSuccess) { g_knn_create_error = "hipStreamCreate failed"; delete h; return NTF_EHIP; }
@@ -247,7 +139,7 @@ extern "C" int ntf_knn_query(ntf_knn* h, const float* queries, int64_t n, int32_
     if (topn < 1 || topn > SEL_MAX) FAIL(h, NTF_EINVAL, "knn query: topn outside 1..2048");
     if (workspace_bytes < 0) FAIL(h, NTF_EINVAL, "knn query: workspace_bytes < 0");
     const int64_t wsb = workspace_bytes ? workspace_bytes : NTF_KNN_WORKSPACE_BYTES;
-    const int64_t unit = (int64_t)KNN_QUNIT * KNN_RB * 4;
+    const int64_t unit = (int64_t)SIM_QUNIT * SIM_RB * 4;
     if (wsb < unit) FAIL(h, NTF_EINVAL, "knn query: workspace_bytes below one unit of work (32 queries x 256 rows of f32 sims = 32 KiB)");
     const int d = h->d; const int64_t dp = h->dp, N = h->n_rows;
     for (int64_t e = 0; e < n * d; ++e) if (!std::isfinite(queries[e])) FAIL(h, NTF_EINVAL, "knn query: a query value is not finite");
@@ -257,13 +149,8 @@ extern "C" int ntf_knn_query(ntf_knn* h, const float* queries, int64_t n, int32_
         for (int64_t i = 0; i < n; ++i) { if (exclude[i] < -1 || exclude[i] >= N) FAIL(h, NTF_EINVAL, "knn query: an exclude value outside [-1, n_rows)"); excl[(size_t)i] = (int32_t)exclude[i]; }
     }
     // the plan (header): a group of 32 g queries, a range of 256 r rows, group x range x 4 bytes <= the budget
-    const int64_t g = std::min<int64_t>(std::max<int64_t>(wsb / ((int64_t)8 << 20), 1), std::min<int64_t>(KNN_MAX_GROUP / KNN_QUNIT, (n + KNN_QUNIT - 1) / KNN_QUNIT));
-    const int64_t G = g * KNN_QUNIT;
-    // query tiles resident a workgroup of the sims kernel: 4 (dp <= 128: a 4-tile image of wider rows does not fit LDS beside the stages), 2 or 1, as many as a full group
-    // fills.  The workspace holds whole chunks of 32 nqt rows (gw = g rounded up to a multiple of nqt), so every query slot a workgroup stores to has its row there
-    const int nqt_max = (std::min(G, n) > 64 && dp <= 128) ? 4 : (std::min(G, n) > 32) ? 2 : 1;
-    const int64_t Gw = (g + nqt_max - 1) / nqt_max * nqt_max * KNN_QUNIT;
-    const int64_t R = std::min<int64_t>(std::min<int64_t>(wsb / (Gw * KNN_RB * 4), KNN_MAX_RANGE / KNN_RB), (N + KNN_RB - 1) / KNN_RB) * KNN_RB;
+    const SimsPlan plan(wsb, n, N, dp);
+    const int64_t G = plan.G, Gw = plan.Gw, R = plan.R;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->st));
     {
@@ -284,15 +171,9 @@ extern "C" int ntf_knn_query(ntf_knn* h, const float* queries, int64_t n, int32_
     if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
     for (int64_t g0 = 0; g0 < n; g0 += G) {
         const int ng = (int)std::min<int64_t>(G, n - g0);
-        const int nqt = std::min(nqt_max, ng > 64 ? 4 : ng > 32 ? 2 : 1);      // a shorter last group takes a shorter chunk (1, 2 and 4 divide nqt_max)
-        const size_t lds = knn_sims_lds(nqt, (int)dp);
-        const int per_cu = std::max<int>(1, (int)((160u << 10) / lds));
         for (int64_t r0 = 0; r0 < N; r0 += R) {
             const int rr = (int)std::min<int64_t>(R, N - r0);
-            KnnSimArgs a;
-            a.T = h->table; a.rinv_t = h->rinv; a.Q = h->q + g0 * dp; a.rinv_q = h->q_rinv + g0; a.S = h->ws; a.r0 = r0; a.ld = R; a.rr = rr; a.nq = ng; a.dp = (int)dp;
-            const dim3 grid((unsigned)std::min<int64_t>((rr + KNN_RB - 1) / KNN_RB, (int64_t)h->n_cu * per_cu), (unsigned)((ng + nqt * 32 - 1) / (nqt * 32)));
-            with_value<1, 2, 4>(nqt, [&](auto q) { launch_lds(k_knn_sims<decltype(q)::value>, grid, dim3(KNN_WAVES * 64), lds, h->st, a); });
+            launch_sims<SimCosine>(h->st, h->n_cu, plan.nqt_max, h->table, h->rinv, h->q + g0 * dp, h->q_rinv + g0, h->ws, r0, R, rr, ng, (int)dp);
             hipLaunchKernelGGL(k_knn_select, dim3((unsigned)ng), dim3(1024), 0, h->st, h->ws, R, rr, r0, (int)topn, exclude ? h->q_excl + g0 : nullptr, h->run, r0 == 0 ? 1 : 0);
         }
         const int64_t ne = (int64_t)ng * topn;

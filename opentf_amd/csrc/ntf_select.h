@@ -1,5 +1,6 @@
-// The row-wise top-K selection, once: k_topk_rows (ntf_kernels.hip, the probabilities of ntf_forward_topk / ntf_score_rows) and k_knn_select
-// (ntf_knn.hip, the sims of a (query, range)) are this function plus what each does with the sorted candidates.
+// The row-wise top-K selection, once: k_topk_rows (ntf_kernels.hip, the probabilities of ntf_forward_topk / ntf_score_rows), k_knn_select (ntf_knn.hip, the sims
+// of a (query, range)) and k_link_select (ntf_link.hip, the logits of one) are this function plus what each does with the sorted candidates; the last two merge them
+// into a running list, merge_running below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -135,6 +136,22 @@ __device__ __forceinline__ int select_topk_row(SelShared& sh, const float* __res
         bitonic_desc(keys, n2, tid, NT);
     }
     return n2;
+}
+
+// A row walked range by range (k_knn_select, k_link_select): the sorted candidates select_topk_row left in sh.keys[0 .. K) (n2: its return value) are merged with
+// the row's running list `mine` [K] (first: there is none yet) by the same composite - a total order, so the merge is exact and the order of the ranges free - and
+// the list is written back.  2 n2 <= 4096 composites, sorted again; a composite of 0 is an empty slot.
+__device__ __forceinline__ void merge_running(SelShared& sh, int n2, int K, unsigned long long* __restrict__ mine, int first) {
+    unsigned long long* keys = sh.keys;
+    const int tid = threadIdx.x, NT = blockDim.x;
+    if (!first) {
+        __syncthreads();
+        for (int k = tid; k < n2; k += NT) keys[n2 + k] = k < K ? mine[k] : 0ull;
+        for (int k = K + tid; k < n2; k += NT) keys[k] = 0ull;
+        __syncthreads();
+        bitonic_desc(keys, 2 * n2, tid, NT);
+    }
+    for (int k = tid; k < K; k += NT) mine[k] = keys[k];
 }
 
 }  // namespace ntf

@@ -147,6 +147,15 @@ FAIR_SYMBOLS = {
     "ntf_fair_metrics": (C.c_int, [C.c_int, _P, _I64, _I32, _P, _I64, _I32, _P, _I64, _P, _I32, _P, _P]),
 }
 
+# every symbol declared in include/opentf_amd_link.h (the link decode of a Gnn table: the second side header, NTF_ABI_VERSION unchanged)
+LINK_SYMBOLS = {
+    "ntf_link_create": (C.c_int, [C.c_int, _P, _I64, _I32, _I64, _I64, C.POINTER(_P)]),
+    "ntf_link_destroy": (None, [_P]),
+    "ntf_link_last_error": (C.c_char_p, [_P]),
+    "ntf_link_topk": (C.c_int, [_P, _I64, _P, _P, _P, _I32, _I64, _P, _P, _P, _P]),
+    "ntf_link_dense": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -161,9 +170,10 @@ def lib():
         for name, (res, args) in SYMBOLS.items():
             fn = getattr(l, name)  # AttributeError if the library does not export a declared symbol
             fn.restype, fn.argtypes = res, args
-        for name, (res, args) in FAIR_SYMBOLS.items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = res, args
+        for table in (FAIR_SYMBOLS, LINK_SYMBOLS):
+            for name, (res, args) in table.items():
+                fn = getattr(l, name)
+                fn.restype, fn.argtypes = res, args
         if l.ntf_abi_version() != NTF_ABI_VERSION:
             raise NtfError("libopentf_amd.so ABI version mismatch")
         _lib = l
@@ -929,3 +939,60 @@ class Knn(_Handle):
         idx = np.empty((n, max(int(topn), 0)), dtype=np.int32); sims = np.empty((n, max(int(topn), 0)), dtype=np.float32); ms = C.c_double()
         self._ck(lib().ntf_knn_query(self._h, _ptr(q), n, int(topn), _ptr(ex), int(workspace_bytes), _ptr(idx), _ptr(sims), C.byref(ms) if want_ms else None))
         return (idx, sims, ms.value) if want_ms else (idx, sims)
+
+
+class Link(_Handle):
+    """Link decode over a [rows, d] float32 node-embedding table resident on one MI355X (include/opentf_amd_link.h ntf_link_*): logit <E[query], E[candidate]> and
+    its sigmoid for every row of the candidate block [cand_lo, cand_hi), ranked by the logit.  Candidate id j is table row cand_lo + j.  Queries are table rows
+    (`rows` [n]) or mean pools of table rows (`pooled` = (ptr [n + 1], items) or a scipy sparse [n, rows] whose column ids are table rows), gathered on the device."""
+
+    _CREATE, _DESTROY, _LAST_ERROR, _TAG = "ntf_link_create", "ntf_link_destroy", "ntf_link_last_error", " link"
+    WORKSPACE_BYTES = Knn.WORKSPACE_BYTES
+    UNIT_BYTES = Knn.UNIT_BYTES
+    MAX_K = 2048
+
+    def __init__(self, table, cand_lo, cand_hi, device=0):
+        t = _f32(table)
+        if t.ndim != 2:
+            raise NtfError(f"table must be [rows, d], got {t.shape}")
+        self.n_rows, self.d = int(t.shape[0]), int(t.shape[1])
+        self.cand_lo, self.cand_hi = int(cand_lo), int(cand_hi)
+        self.n_cand = self.cand_hi - self.cand_lo
+        self._create(int(device), _ptr(t), self.n_rows, self.d, self.cand_lo, self.cand_hi)
+
+    def _queries(self, rows, pooled):
+        """-> (n, q_rows, q_ptr, q_items): int64 arrays or None, as the C entries take them (which refuse both or neither)"""
+        if not getattr(self, "_h", None):
+            raise NtfError("the Link handle is closed")
+        r = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+        ptr = items = None
+        if pooled is not None:
+            if hasattr(pooled, "tocsr"):
+                m = pooled.tocsr(); m.sort_indices()
+                pooled = (m.indptr, m.indices)
+            ptr = np.ascontiguousarray(np.asarray(pooled[0], dtype=np.int64).reshape(-1))
+            items = np.ascontiguousarray(np.asarray(pooled[1], dtype=np.int64).reshape(-1))
+            if len(ptr) < 1 or (len(ptr) > 1 and int(ptr[-1]) > len(items)):
+                raise NtfError("pooled queries: ptr must hold n + 1 offsets into items")
+        n = len(r) if r is not None else (len(ptr) - 1 if ptr is not None else 0)
+        return n, r, ptr, items
+
+    def topk(self, rows=None, pooled=None, K=10, workspace_bytes=0, want_ms=False):
+        """the K best candidates of every query, largest logit first, equal logits by ascending candidate id -> (idx [n, K] int32, logit [n, K] f32, prob [n, K] f32
+        [, device ms]); slots past the C candidates hold id -1, logit -inf and probability 0"""
+        n, r, ptr, items = self._queries(rows, pooled)
+        shape = (max(n, 0), max(int(K), 0))
+        idx = np.empty(shape, dtype=np.int32); logit = np.empty(shape, dtype=np.float32); prob = np.empty(shape, dtype=np.float32); ms = C.c_double()
+        self._ck(lib().ntf_link_topk(self._h, n, _ptr(r), _ptr(ptr), _ptr(items), int(K), int(workspace_bytes), _ptr(idx), _ptr(logit), _ptr(prob),
+                                     C.byref(ms) if want_ms else None))
+        return (idx, logit, prob, ms.value) if want_ms else (idx, logit, prob)
+
+    def dense(self, rows=None, pooled=None, workspace_bytes=0, want_ms=False, logit=True, prob=True):
+        """every candidate of every query -> (logit [n, C] f32 or None, prob [n, C] f32 or None[, device ms])"""
+        n, r, ptr, items = self._queries(rows, pooled)
+        shape = (max(n, 0), self.n_cand)
+        lo = np.empty(shape, dtype=np.float32) if logit else None
+        pr = np.empty(shape, dtype=np.float32) if prob else None
+        ms = C.c_double()
+        self._ck(lib().ntf_link_dense(self._h, n, _ptr(r), _ptr(ptr), _ptr(items), int(workspace_bytes), _ptr(lo), _ptr(pr), C.byref(ms) if want_ms else None))
+        return (lo, pr, ms.value) if want_ms else (lo, pr)

@@ -18,6 +18,11 @@ What the caller (src/main.py:100-153) does and what it gets here:
       package (opentf_amd/mdl/fnn.py) finds the table and runs the gather INSIDE every training step from `original_skill`
       (which main.py:152 stores itself) instead of reading pre-pooled rows.
 
+  * `t2v.test(teamsvecs, splits, testcfg)`; `t2v.evaluate(...)`; `t2v.adila(...)`            (the reference's CI matrix lists Gnn under cmd=[train,test,eval]; gnn.py:512-545)
+      the table as a recommender: every member scored for a team by the link decode sigmoid(<E[team], E[member]>) - the logit of v_loss, over the very member-team edges
+      learn() held out - on the device (`opentf_amd/csrc/ntf_link.hip`, `libntf.Link`), `.pred` files in this package's Fnn.test's format, then Ntf's evaluate / adila on
+      them.  `recommend(skill_rows)` does the same for teams outside the graph from the mean pool of their skills' rows.
+
 Node ids of the homogeneous graph: [skills | members | teams].  (PyG's HeteroData orders the three blocks by Python set iteration, i.e.
 arbitrarily per process; consumers select by type, gnn.py:505-509, so the order is not part of the contract.)
 
@@ -37,7 +42,7 @@ import scipy.sparse
 
 from ..earlystopping import EarlyStopping, PlateauLR
 from ..fnn import index_order, parse_devices
-from ..ntf import cfg_get, dist_rank, summary_writer
+from ..ntf import Ntf, cfg_get, coo_from_topk, dist_rank, summary_writer, topk_sparse
 from .t2v import T2v, gather_meanpool
 
 log = logging.getLogger(__name__)
@@ -189,6 +194,8 @@ class Gnn(T2v):
         self.writer = summary_writer()
         self.offsets = None
         self.blocks = None      # {node type: (first row, end row)} of the loaded table
+        self.n_nodes = None     # rows of the table learn() trained or loaded
+        self._link = self._link_table = None      # the libntf.Link test() / recommend() keep, and the table it holds
 
     def _mcfg(self):
         return cfg_get(self.cfg, self.name)
@@ -247,7 +254,7 @@ class Gnn(T2v):
             else:
                 rowptr, col, off, n = stm_graph(skill, member, drop)
                 n_start = n
-            self.offsets = off
+            self.offsets, self.n_nodes = off, n
             init = torch.nn.Embedding(n, d).weight.detach().numpy()       # the draw Node2Vec's / MetaPath2Vec's constructor makes (gnn.py:153-160): Embedding(count + 1, d) for m2v
             if self.name == "m2v": make_net = lambda: libntf.MetaPath2Vec(counts, hops, init, seed=seed, device=parse_devices(self.device)[0], sparse=self._sparse(), lazy=self._lazy())
             else:
@@ -371,3 +378,82 @@ class Gnn(T2v):
         if vectype == "skill":
             teamsvecs["skill_table"] = table
         return dense
+
+    # ---- the table as a recommender (src/mdl/emb/gnn.py:512-545): every member scored for a team by the link decode sigmoid(<E[team], E[member]>), the logit of
+    # v_loss over exactly the member-team edges learn() held out (include/opentf_amd_link.h; INTEGRATION.md §2b: PyG's dot-product decode restated, not pinned)
+    is_bayesian = False
+    evaluate = Ntf.evaluate      # both need `output`, `cfg` and `seed` only; they read the .pred files test() writes
+    adila = Ntf.adila
+    _eval_engine = Ntf._eval_engine      # NTF_EVAL_ENGINE=1: "Gnn owns no engine", the files are read
+
+    def _link_for(self, table):
+        """the Link over `table` with the member block as candidates; one handle is kept, a new table replaces it"""
+        from ... import libntf
+        if self._link is None or self._link_table is not table:
+            self.close()
+            lo, hi = self.blocks["member"]
+            self._link, self._link_table = libntf.Link(table, lo, hi, device=parse_devices(self.device)[0]), table
+        return self._link
+
+    def close(self):
+        """frees the device handle test() / recommend() keep"""
+        if self._link is not None:
+            self._link.close()
+        self._link = self._link_table = None
+
+    def test(self, teamsvecs, splits, testcfg):
+        """The flow of this package's Fnn.test: per fold `f{k}.pt` (+ `f{k}.e{e}.pt` with per_epoch) through _load_fold, the teams of the pred set as QUERY ROWS of
+        the table (team block start + team id: no vector crosses the host), the member block as candidates (member id = row - member block start), and
+        `f{k}.{set}.[e{e}.]pred` = {'y_pred': sparse COO of the topK probabilities (topK < M) or the dense [n, M] probabilities, 'uncertainty': None}."""
+        import torch
+        from ... import libntf
+        self._node_emb(teamsvecs, "member")      # RuntimeError before learn()
+        assert os.path.isdir(self.output), f"No folder for {self.output} exist!"
+        if dist_rank() != 0:                     # one writer, as Fnn.test: the others wait so that evaluate() finds complete files
+            _barrier(); return
+        learned = self.model
+        (m_lo, m_hi), t_lo = self.blocks["member"], self.blocks["team"][0]
+        M = m_hi - m_lo
+        topK = cfg_get(testcfg, "topK")
+        sparse_out = bool(topK) and topK < M
+        on_gpu_topk = sparse_out and topK <= libntf.Link.MAX_K
+        for foldidx in splits["folds"].keys():
+            modelfiles = [f"{self.output}/f{foldidx}.pt"]
+            if cfg_get(testcfg, "per_epoch"):
+                modelfiles += [f"{self.output}/{_}" for _ in os.listdir(self.output) if re.match(rf"f{foldidx}.e\d+.pt", _)]
+            for modelfile in sorted(sorted(modelfiles), key=len):
+                link = self._link_for(self._load_fold(modelfile, self.offsets, self.n_nodes))
+                for pred_set in (["test", "train", "valid"] if cfg_get(testcfg, "on_train") else ["test"]):
+                    teams = np.asarray(splits["test"] if pred_set == "test" else splits["folds"][foldidx][pred_set], dtype=np.int64)
+                    rows = teams + t_lo
+                    if len(rows) == 0:
+                        y_pred = torch.empty(0, M)
+                    elif on_gpu_topk:
+                        idx, _, prob = link.topk(rows=rows, K=int(topK))
+                        y_pred = coo_from_topk(prob, idx, (len(rows), M))
+                    else:
+                        y_pred = torch.from_numpy(link.dense(rows=rows, logit=False)[1])
+                        if sparse_out:
+                            y_pred = topk_sparse(y_pred, int(topK))
+                    match = re.search(r"(e\d+)\.pt$", os.path.basename(modelfile))
+                    epoch = (match.group(1) + ".") if match else ""
+                    torch.save({"y_pred": y_pred, "uncertainty": None}, f"{self.output}/f{foldidx}.{pred_set}.{epoch}pred", pickle_protocol=4)
+                    log.info(f"{self.name} model predictions for fold{foldidx}.{pred_set}.{epoch} has saved at {self.output}/f{foldidx}.{pred_set}.{epoch}pred")
+        self.model = learned                     # get_dense_vecs keeps reading the table learn() left
+        _barrier()
+
+    def recommend(self, skill_rows, topn=10):
+        """Teams that are not in the graph: each row of `skill_rows` (scipy sparse [n, S], or a list of skill-id lists) is the mean pool of its skills' rows of the
+        table - get_dense_vecs' pool, on the device - scored against every member.  -> (idx [n, topn] int32 member ids, prob [n, topn] f32), best first."""
+        self._node_emb(None, "member")           # RuntimeError before learn()
+        s_lo, s_hi = self.blocks["skill"]
+        if hasattr(skill_rows, "tocsr"):
+            ptr, items = _csr(skill_rows)
+        else:
+            lists = [np.asarray(r, dtype=np.int64).reshape(-1) for r in skill_rows]
+            ptr = np.concatenate([[0], np.cumsum([len(r) for r in lists])]).astype(np.int64)
+            items = np.concatenate(lists).astype(np.int64) if lists else np.zeros(0, dtype=np.int64)
+        if len(items) and (items.min() < 0 or items.max() >= s_hi - s_lo):
+            raise ValueError(f"recommend: a skill id outside [0, {s_hi - s_lo})")
+        idx, _, prob = self._link_for(self.model).topk(pooled=(ptr, items + s_lo), K=int(topn))
+        return idx, prob

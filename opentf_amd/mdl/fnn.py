@@ -21,7 +21,7 @@ import numpy as np
 import scipy.sparse
 
 from .earlystopping import EarlyStopping, PlateauLR
-from .ntf import Ntf, cfg2str, cfg_get, dist_rank
+from .ntf import Ntf, cfg2str, cfg_get, coo_from_topk, dist_rank, topk_sparse
 
 log = logging.getLogger(__name__)
 
@@ -408,24 +408,8 @@ def make_fnn(base):
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
             return t.cpu().numpy()
 
-        @staticmethod
-        def _topk_sparse(probs, k):
-            """src/pkgmgr.py:125-134"""
-            import torch
-            v, i = torch.topk(probs, k, dim=1)
-            rows = torch.arange(probs.shape[0]).unsqueeze(1).expand(-1, k)
-            return torch.sparse_coo_tensor(torch.stack([rows, i], dim=0).reshape(2, -1), v.reshape(-1), size=probs.shape).coalesce()
-
-        @staticmethod
-        def _coo_from_topk(vals, idx, shape):
-            """The coalesced COO tensor topk_sparse() returns (indices sorted by row, then column), from the GPU top-K."""
-            import torch
-            order = np.argsort(idx, axis=1, kind="stable")
-            idx_s = np.take_along_axis(idx, order, axis=1).astype(np.int64)
-            val_s = np.take_along_axis(vals, order, axis=1)
-            rows = np.repeat(np.arange(shape[0], dtype=np.int64), idx.shape[1])
-            ind = torch.from_numpy(np.stack([rows, idx_s.reshape(-1)]))
-            return torch.sparse_coo_tensor(ind, torch.from_numpy(val_s.reshape(-1)), size=shape, is_coalesced=True)
+        _topk_sparse = staticmethod(topk_sparse)          # (mdl/ntf.py: Gnn.test writes the same two forms)
+        _coo_from_topk = staticmethod(coo_from_topk)
 
     Fnn.__qualname__ = "Fnn"
     return Fnn

@@ -126,6 +126,25 @@ def _read_pred(path):
     return scipy.sparse.csr_matrix((y.values().numpy(), (ij[0], ij[1])), shape=tuple(y.size()))
 
 
+def topk_sparse(probs, k):
+    """src/pkgmgr.py:125-134"""
+    import torch
+    v, i = torch.topk(probs, k, dim=1)
+    rows = torch.arange(probs.shape[0]).unsqueeze(1).expand(-1, k)
+    return torch.sparse_coo_tensor(torch.stack([rows, i], dim=0).reshape(2, -1), v.reshape(-1), size=probs.shape).coalesce()
+
+
+def coo_from_topk(vals, idx, shape):
+    """The coalesced COO tensor topk_sparse() returns (indices sorted by row, then column), from the GPU top-K (Fnn.test, Gnn.test)."""
+    import torch
+    order = np.argsort(idx, axis=1, kind="stable")
+    idx_s = np.take_along_axis(idx, order, axis=1).astype(np.int64)
+    val_s = np.take_along_axis(vals, order, axis=1)
+    rows = np.repeat(np.arange(shape[0], dtype=np.int64), idx.shape[1])
+    ind = torch.from_numpy(np.stack([rows, idx_s.reshape(-1)]))
+    return torch.sparse_coo_tensor(ind, torch.from_numpy(val_s.reshape(-1)), size=shape, is_coalesced=True)
+
+
 class _FoldTable:
     """what the set-level files need of the folds' final files: one column of means per fold, and the running sum of the per-instance tables"""
     def __init__(self): self.means, self.inst_sum = [], None
