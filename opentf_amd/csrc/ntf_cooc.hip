@@ -25,6 +25,16 @@ constexpr int SORT_MAX = 2048;     // entries a single wave sorts in LDS (2 x 8 
 constexpr int HIST_WGS = 512;      // persistent workgroups of the histogram path, one scratch row each
 constexpr int SCAN_BLOCK = 1024;   // elements per block of the scan (256 threads x 4)
 
+// a HIP event that lives as long as its owner (DevBuf's shape): every return of the entry destroys it
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    DevEvent(const DevEvent&) = delete;
+    DevEvent& operator=(const DevEvent&) = delete;
+    ~DevEvent() { if (e) hipEventDestroy(e); }
+    bool create() { if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return false; } return true; }
+};
+
 // ---------------------------------------------------------------- scan (exclusive, u32 in -> int64 out, out[n] = total)
 __global__ __launch_bounds__(256) void k_scan_block_sums(const uint32_t* __restrict__ in, int64_t n, int64_t* __restrict__ block_sums) {
     __shared__ int64_t red[4];
@@ -238,9 +248,9 @@ extern "C" int ntf_skill_cooccurrence(int device, int64_t n_teams, int32_t n_mem
         !six.put(s_indices, (size_t)s_nnz * 4) || (n_skip && !dskip.put(skip.data(), (size_t)n_teams)) || !work.alloc((size_t)n_members * 4, true) ||
         !cursor.alloc((size_t)n_members * 4, true) || !wstart.alloc((size_t)(n_members + 1) * 8) || !rlen.alloc((size_t)n_members * 4, true) ||
         !biglist.alloc((size_t)n_members * 4) || !bigcount.alloc(4, true)) return NTF_ENOMEM;
-    hipEvent_t ev0, ev1;
-    hipEventCreate(&ev0); hipEventCreate(&ev1);
-    hipEventRecord(ev0, 0);
+    DevEvent ev0, ev1;
+    if (!ev0.create() || !ev1.create()) return NTF_EHIP;
+    hipEventRecord(ev0.e, 0);
     const unsigned tb = (unsigned)((n_teams + 255) / 256);
     hipLaunchKernelGGL(k_cooc_work, dim3(tb), dim3(256), 0, 0, n_teams, mip.as<int64_t>(), mix.as<int32_t>(), sip.as<int64_t>(),
                        n_skip ? dskip.as<uint8_t>() : nullptr, work.as<uint32_t>());
@@ -268,10 +278,9 @@ extern "C" int ntf_skill_cooccurrence(int device, int64_t n_teams, int32_t n_mem
     if (!r->indices.alloc((size_t)std::max<int64_t>(r->nnz, 4) * 4) || !r->data.alloc((size_t)std::max<int64_t>(r->nnz, 16))) { delete r; return NTF_ENOMEM; }
     hipLaunchKernelGGL(k_cooc_compact, dim3((unsigned)((n_members + 3) / 4)), dim3(256), 0, 0, n_members, rlen.as<uint32_t>(), wstart.as<int64_t>(),
                        r->indptr.as<int64_t>(), tix.as<int32_t>(), tval.as<uint8_t>(), r->indices.as<int32_t>(), r->data.as<uint8_t>());
-    hipEventRecord(ev1, 0);
+    hipEventRecord(ev1.e, 0);
     const hipError_t s = hipDeviceSynchronize();
-    float ms = 0; hipEventElapsedTime(&ms, ev0, ev1); r->ms = ms;
-    hipEventDestroy(ev0); hipEventDestroy(ev1);
+    float ms = 0; hipEventElapsedTime(&ms, ev0.e, ev1.e); r->ms = ms;
     if (s != hipSuccess || hipGetLastError() != hipSuccess) { ntf_csr_result_free(r); return NTF_EHIP; }
     if (nnz_out) *nnz_out = r->nnz;
     *out = r;
