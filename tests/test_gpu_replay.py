@@ -26,7 +26,7 @@ def _dataset(rng, N, S, D, M, mean_s, mean_m):
     return (s_ip, s_ix), table, (m_ip, m_ix)
 
 
-def _replay(D, H, M, B, S, mean_s, mean_m, seed, t0, nsteps=3, bad_frac=5e-4, nsd="uniform", multihot=False, bayesian=True, pipelined=True, ns=5, tpw=10.0, tnw=1.0):
+def _replay(D, H, M, B, S, mean_s, mean_m, seed, t0, nsteps=3, bad_frac=5e-4, nsd="uniform", multihot=False, bayesian=True, pipelined=True, ns=5, tpw=10.0, tnw=1.0, dense=False):
     import torch
     from oracle import ntf_oracle as O
     from opentf_amd import libntf
@@ -51,9 +51,13 @@ def _replay(D, H, M, B, S, mean_s, mean_m, seed, t0, nsteps=3, bad_frac=5e-4, ns
     def as_torch(noise):
         return [{k: torch.from_numpy(v) for k, v in n.items()} for n in noise] if noise is not None else None
 
-    e = libntf.Engine([D, H, M], bayesian=bayesian, input_mode=libntf.INPUT_MULTIHOT if multihot else libntf.INPUT_MEANPOOL, max_batch=B, ns=ns, nsd=nsd, tpw=tpw, tnw=tnw, lr=1e-3, seed=seed, fuse_adam=1)     # what bench.py and the plugin create: Adam in the dW epilogue, operands / head prefetched
-    if not multihot: e.set_skill_table(table)
-    e.set_skill_csr(skill); e.set_member(member); e.load_state_dict(sd)
+    assert not (dense and multihot)
+    e = libntf.Engine([D, H, M], bayesian=bayesian, input_mode=libntf.INPUT_MULTIHOT if multihot else libntf.INPUT_DENSE if dense else libntf.INPUT_MEANPOOL, max_batch=B, ns=ns, nsd=nsd, tpw=tpw, tnw=tnw, lr=1e-3, seed=seed, fuse_adam=1)     # what bench.py and the plugin create: Adam in the dW epilogue, operands / head prefetched
+    if dense: e.set_dense_input(Xall.numpy())      # the engine reads the mean-pooled rows themselves: no table, no skill CSR
+    else:
+        if not multihot: e.set_skill_table(table)
+        e.set_skill_csr(skill)
+    e.set_member(member); e.load_state_dict(sd)
     if nsd == "unigram": e.set_unigram(np.bincount(member[1], minlength=M) / N)      # src/mdl/fnn.py:82
     e.stage_order(order)
 
