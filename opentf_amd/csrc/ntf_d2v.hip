@@ -59,54 +59,117 @@ struct D2vArgs {
 __device__ __forceinline__ uint4 d2v_draw(uint32_t k0, uint32_t k1, int64_t doc, int pos, int unit, int slot) {
     return philox4x32(make_uint4((uint32_t)doc, (uint32_t)((uint64_t)doc >> 32), ((uint32_t)pos << 8) | (uint32_t)unit, (uint32_t)slot), make_uint2(k0, k1));
 }
-__device__ __forceinline__ uint4 d2v_draw(const D2vArgs& a, int64_t doc, int pos, int unit, int slot) { return d2v_draw(a.k0, a.k1, doc, pos, unit, slot); }
 // EXP_TABLE lookup of doc2vec_inner.pyx (the table is built in float32: entry i = sigmoid((i / 1000 * 2 - 1) * 6))
 __device__ __forceinline__ float d2v_sigmoid_table(float f) {
     const int i = (int)((f + D2V_MAX_EXP) * (1000.f / D2V_MAX_EXP / 2.f));
     const float e = expf(((float)i / 1000.f * 2.f - 1.f) * D2V_MAX_EXP);
     return e / (e + 1.f);
 }
-// rows other waves add to: read past the CU's vector cache
-__device__ __forceinline__ float d2v_ld(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// one value of a table row.  The trainer: rows other waves add to, read past the CU's vector cache; FROZEN (inference): tables nobody writes, a plain cached load
+template <bool FROZEN = false>
+__device__ __forceinline__ float d2v_ld(const float* p) {
+    if constexpr (FROZEN) return *p; else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the row of `table` that belongs to the word at kept position m (wave-uniform: the row address in scalar registers)
+template <class T>
+__device__ __forceinline__ T* d2v_row(T* table, int d, const int* kept, int m) { return table + (int64_t)__builtin_amdgcn_readfirstlane(kept[m & (D2V_RING - 1)]) * d; }
+// row += v: one coalesced f32 atomic row add
+template <int NV>
+__device__ __forceinline__ void d2v_row_add(float* row, int lane, const float (&v)[NV]) {
+#pragma unroll
+    for (int q = 0; q < NV; ++q) unsafeAtomicAdd(row + lane + 64 * q, v[q]);
+}
 
 constexpr int D2V_TOP = 1024;       // cumulative table, first level: the last entry of each of <= 1024 equal buckets, in LDS (round 5: the bisection in memory was 13-16 dependent round trips a position;
                                     // now ~5: PV-DM 61.5 -> 55.2 ms a pass.  Fetching a unit's six syn1neg rows up front instead of one by one was tried with it: 95 ms - the registers cost two waves per SIMD)
 
-// the negative-sampling unit: input x (registers), predicted word `word`; returns `work` in w[], adds g x to the rows of syn1neg it touches
-template <int NV>
-__device__ __forceinline__ void d2v_unit(const D2vArgs& a, const uint32_t* __restrict__ top, int top_n, int top_s, const float (&x)[NV], int word, float alpha, int64_t doc, int pos, int unit,
-                                         int lane, float (&w)[NV], float& lsum, float& lcnt) {
+// what both kernels begin with: the first table level into LDS (buckets of top_s entries; top[k] = the last entry of bucket k) and the items of this wave: first, first + stride, ..
+// (one item after the other by wave 0 of block 0 when `serial`).  false: this wave has nothing to do.  Every thread of the block calls it
+__device__ __forceinline__ bool d2v_prologue(const uint32_t* cum_table, int64_t n_vocab, int serial, uint32_t* s_top, int& top_s, int& top_n, int64_t& first, int64_t& stride) {
+    top_s = (int)((n_vocab + D2V_TOP - 1) / D2V_TOP); top_n = (int)((n_vocab + top_s - 1) / top_s);
+    for (int k = threadIdx.x; k < top_n; k += blockDim.x) s_top[k] = cum_table[min((int64_t)(k + 1) * top_s, n_vocab) - 1];
+    __syncthreads();
+    const int wv_id = threadIdx.x >> 6;
+    first = serial ? 0 : (int64_t)blockIdx.x * 4 + wv_id;
+    stride = serial ? 1 : (int64_t)gridDim.x * 4;
+    return !(serial && (blockIdx.x != 0 || wv_id != 0));
+}
+
+// words that survive the frequent-word subsampling (sample_int >= draw), in order: compacted by ballot into a RING, 64 raw words per step, filled until `need` words are
+// kept - just far enough ahead of position i for its window (need = i + window + 1) - so a document of any length needs 1 024 slots (round 3 held the whole kept list in
+// LDS and silently cut documents at 1 024 kept words; gensim's cap is 10 000: embtype member / skillmember on gith, uspt).  words: the document's L raw words;
+// K, base: kept words compacted so far (<= D2V_MAX_DOC), raw words scanned so far
+__device__ __forceinline__ void d2v_fill_ring(int* kept, const int32_t* words, int L, const uint32_t* sample_int, uint32_t k0, uint32_t k1, int64_t doc, int need, int lane, int& K, int& base) {
+    while (K < need && base < L && K < D2V_MAX_DOC) {
+        const int p = base + lane;
+        int wd = 0; bool keep = false;
+        if (p < L) { wd = words[p]; keep = sample_int[wd] >= d2v_draw(k0, k1, doc, p, 0, SLOT_KEEP).x; }
+        const unsigned long long m = __ballot(keep);
+        const int at = K + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep && at < D2V_MAX_DOC) kept[at & (D2V_RING - 1)] = wd;         // (slots older than i - window are dead: K - (i - window) <= 2 window + 64 < D2V_RING)
+        K = min(K + (int)__popcll(m), D2V_MAX_DOC);
+        base += 64;
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// PV-DM's input l1: the mean of the doc vector and the word vectors of the kept positions [lo, hi) without i
+template <int NV, bool FROZEN>
+__device__ __forceinline__ void d2v_dm_mean(const float* wv, int d, const int* kept, int lo, int hi, int i, const float (&dreg)[NV], int lane, float (&l1)[NV]) {
+#pragma unroll
+    for (int q = 0; q < NV; ++q) l1[q] = dreg[q];
+    for (int m = lo; m < hi; ++m) {
+        if (m == i) continue;
+        const float* r = d2v_row(wv, d, kept, m);
+#pragma unroll
+        for (int q = 0; q < NV; ++q) l1[q] += d2v_ld<FROZEN>(r + lane + 64 * q);
+    }
+    const float inv = 1.f / (float)(hi - lo);               // (hi - lo - 1) window words + the doc tag
+#pragma unroll
+    for (int q = 0; q < NV; ++q) l1[q] *= inv;
+}
+
+// bisect_left(cum_table, r % cum_table[-1]): the bucket through the LDS level (the first bucket whose last entry is >= v holds the answer), then inside it
+__device__ __forceinline__ int d2v_table_search(const uint32_t* cum_table, int64_t n_vocab, const uint32_t* __restrict__ top, int top_n, int top_s, uint32_t rk) {
+    const uint32_t v = rk % cum_table[n_vocab - 1];
+    int blo = 0, bhi = top_n;
+    while (blo < bhi) { const int mid = (blo + bhi) >> 1; if (top[mid] < v) blo = mid + 1; else bhi = mid; }
+    int64_t lo = (int64_t)blo * top_s, hi = min((int64_t)(blo + 1) * top_s, n_vocab);
+    if (blo >= top_n) { lo = n_vocab; hi = n_vocab; }        // (v is below cum_table[-1]: never taken)
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (cum_table[mid] < v) lo = mid + 1; else hi = mid; }
+    return (int)lo;
+}
+
+// the negative-sampling unit of both kernels (Args: D2vArgs or D2vInferArgs): input x (registers), predicted word `word`, Philox key (k0, k1); returns `work` in w[].
+// The trainer's adds g x to the rows of syn1neg it touches and sums the loss terms; FROZEN (inference) has the same draws, targets, order of operations and skips,
+// reads syn1neg with plain loads, never writes it and leaves lsum / lcnt alone
+template <int NV, bool FROZEN = false, class Args>
+__device__ __forceinline__ void d2v_unit(const Args& a, uint32_t k0, uint32_t k1, const uint32_t* __restrict__ top, int top_n, int top_s, const float (&x)[NV], int word, float alpha, int64_t doc,
+                                         int pos, int unit, int lane, float (&w)[NV], float& lsum, float& lcnt) {
 #pragma unroll
     for (int k = 0; k < NV; ++k) w[k] = 0.f;
     // lane k < 8 holds draw k: two Philox words of four draws each
-    const uint4 r4 = d2v_draw(a, doc, pos, unit, SLOT_NEG0 + ((lane >> 2) & 1));
+    const uint4 r4 = d2v_draw(k0, k1, doc, pos, unit, SLOT_NEG0 + ((lane >> 2) & 1));
     const uint32_t rk = (lane & 3) == 0 ? r4.x : (lane & 3) == 1 ? r4.y : (lane & 3) == 2 ? r4.z : r4.w;
-    // bisect_left(cum_table, r % cum_table[-1]): the bucket through the LDS level (the first bucket whose last entry is >= v holds the answer), then inside it
-    int tgt;
-    {
-        const uint32_t v = rk % a.cum_table[a.n_vocab - 1];
-        int blo = 0, bhi = top_n;
-        while (blo < bhi) { const int mid = (blo + bhi) >> 1; if (top[mid] < v) blo = mid + 1; else bhi = mid; }
-        int64_t lo = (int64_t)blo * top_s, hi = min((int64_t)(blo + 1) * top_s, a.n_vocab);
-        if (blo >= top_n) { lo = a.n_vocab; hi = a.n_vocab; }        // (v is below cum_table[-1]: never taken)
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.cum_table[mid] < v) lo = mid + 1; else hi = mid; }
-        tgt = (int)lo;
-    }
+    const int tgt = d2v_table_search(a.cum_table, a.n_vocab, top, top_n, top_s, rk);
     for (int k = 0; k <= a.negative; ++k) {
         const int t = __builtin_amdgcn_readfirstlane(k == 0 ? word : __shfl(tgt, k - 1, 64));      // (wave-uniform: row addresses in scalar registers)
         if (k > 0 && t == word) continue;
         const float label = k == 0 ? 1.f : 0.f;
-        float* row = a.syn1neg + (int64_t)t * a.d;
+        auto* row = a.syn1neg + (int64_t)t * a.d;
         float rv[NV], f = 0.f;
 #pragma unroll
-        for (int q = 0; q < NV; ++q) { rv[q] = d2v_ld(row + lane + 64 * q); f += x[q] * rv[q]; }
+        for (int q = 0; q < NV; ++q) { rv[q] = d2v_ld<FROZEN>(row + lane + 64 * q); f += x[q] * rv[q]; }
         f = wave_reduce_sum(f);
         if (f <= -D2V_MAX_EXP || f >= D2V_MAX_EXP) continue;
         const float s = d2v_sigmoid_table(f);
-        lsum -= logf(fmaxf(label != 0.f ? s : 1.f - s, 1e-30f)); lcnt += 1.f;
+        if constexpr (!FROZEN) { lsum -= logf(fmaxf(label != 0.f ? s : 1.f - s, 1e-30f)); lcnt += 1.f; }
         const float g = (label - s) * alpha;
 #pragma unroll
-        for (int q = 0; q < NV; ++q) { w[q] += g * rv[q]; unsafeAtomicAdd(row + lane + 64 * q, g * x[q]); }
+        for (int q = 0; q < NV; ++q) {
+            w[q] += g * rv[q];
+            if constexpr (!FROZEN) unsafeAtomicAdd(row + lane + 64 * q, g * x[q]);
+        }
     }
 }
 
@@ -121,24 +184,17 @@ template <int NV, int DW = 0>
 __global__ __launch_bounds__(256, DW > 0 ? 1 : (NV <= 2 ? 6 : 5)) void k_d2v_epoch(D2vArgs a, int dm) {
     __shared__ int s_kept[4][D2V_RING];
     __shared__ uint32_t s_top[D2V_TOP];
-    const int lane = threadIdx.x & 63, wv_id = threadIdx.x >> 6;
-    int* kept = s_kept[wv_id];
-    const int top_s = (int)((a.n_vocab + D2V_TOP - 1) / D2V_TOP), top_n = (int)((a.n_vocab + top_s - 1) / top_s);     // buckets of top_s entries; top[k] = the last entry of bucket k
-    for (int k = threadIdx.x; k < top_n; k += blockDim.x) s_top[k] = a.cum_table[min((int64_t)(k + 1) * top_s, a.n_vocab) - 1];
-    __syncthreads();
-    const int64_t first = a.serial ? 0 : (int64_t)blockIdx.x * 4 + wv_id;
-    const int64_t stride = a.serial ? 1 : (int64_t)gridDim.x * 4;
-    if (a.serial && (blockIdx.x != 0 || wv_id != 0)) return;
+    const int lane = threadIdx.x & 63;
+    int* kept = s_kept[threadIdx.x >> 6];
+    int top_s, top_n; int64_t first, stride;
+    if (!d2v_prologue(a.cum_table, a.n_vocab, a.serial, s_top, top_s, top_n, first, stride)) return;
     float lsum = 0.f, lcnt = 0.f;
     for (int64_t rank = first; rank < a.n_docs; rank += stride) {
         const int64_t doc = a.order ? a.order[rank] : rank;
         const float alpha = (float)(a.alpha_start - (a.alpha_start - a.alpha_end) * (a.progress ? a.progress[rank] : (double)rank / (double)a.n_docs));
         const int64_t p0 = a.doc_ptr[doc];
         const int L = (int)(a.doc_ptr[doc + 1] - p0);
-        // ---- words that survive the frequent-word subsampling (sample_int >= draw), in order: compacted by ballot into a RING, 64 raw words per step, filled just
-        //      far enough ahead of position i for its window (i + window) - a document of any length needs 1 024 slots (round 3 held the whole kept list in LDS and
-        //      silently cut documents at 1 024 kept words; gensim's cap is 10 000: embtype member / skillmember on gith, uspt)
-        int K = 0, base = 0;               // kept words compacted so far (<= D2V_MAX_DOC), raw words scanned so far
+        int K = 0, base = 0;               // d2v_fill_ring's: kept words compacted so far, raw words scanned so far
         float dreg[NV];
         float* drow = a.dv + doc * a.d;
 #pragma unroll
@@ -150,26 +206,12 @@ __global__ __launch_bounds__(256, DW > 0 ? 1 : (NV <= 2 ? 6 : 5)) void k_d2v_epo
         for (int j = 0; j < NPEND; ++j)
 #pragma unroll
             for (int q = 0; q < NV; ++q) pend[j][q] = 0.f;
-        auto flush_row = [&](int m, const float (&v)[NV]) {
-            float* r = a.wv + (int64_t)__builtin_amdgcn_readfirstlane(kept[m & (D2V_RING - 1)]) * a.d;
-#pragma unroll
-            for (int q = 0; q < NV; ++q) unsafeAtomicAdd(r + lane + 64 * q, v[q]);
-        };
+        auto flush_row = [&](int m, const float (&v)[NV]) { d2v_row_add(d2v_row(a.wv, a.d, kept, m), lane, v); };      // the word vector of kept position m += v
         int i = 0;
         for (;; ++i) {
-            while (K < i + a.window + 1 && base < L && K < D2V_MAX_DOC) {
-                const int p = base + lane;
-                int wd = 0; bool keep = false;
-                if (p < L) { wd = a.words[p0 + p]; keep = a.sample_int[wd] >= d2v_draw(a, doc, p, 0, SLOT_KEEP).x; }
-                const unsigned long long m = __ballot(keep);
-                const int at = K + __popcll(m & ((1ull << lane) - 1ull));
-                if (keep && at < D2V_MAX_DOC) kept[at & (D2V_RING - 1)] = wd;         // (slots older than i - window are dead: K - (i - window) <= 2 window + 64 < D2V_RING)
-                K = min(K + (int)__popcll(m), D2V_MAX_DOC);
-                base += 64;
-                __builtin_amdgcn_wave_barrier();
-            }
+            d2v_fill_ring(kept, a.words + p0, L, a.sample_int, a.k0, a.k1, doc, i + a.window + 1, lane, K, base);
             if (i >= K) break;
-            const int b = (int)(d2v_draw(a, doc, i, 0, SLOT_WINDOW).x % (uint32_t)a.window), word = __builtin_amdgcn_readfirstlane(kept[i & (D2V_RING - 1)]);
+            const int b = (int)(d2v_draw(a.k0, a.k1, doc, i, 0, SLOT_WINDOW).x % (uint32_t)a.window), word = __builtin_amdgcn_readfirstlane(kept[i & (D2V_RING - 1)]);
             // (K is final here whenever it bounds the window: K < i + window + 1 only once every raw word has been scanned or the cap is reached)
             const int lo = max(0, i - a.window + b), hi = min(K, i + a.window + 1 - b);
             float work[NV];
@@ -199,14 +241,14 @@ __global__ __launch_bounds__(256, DW > 0 ? 1 : (NV <= 2 ? 6 : 5)) void k_d2v_epo
                 for (int j = 0; j < NPEND; ++j) {
                     const int m = i - DW + j;
                     if (j == DW || m < lo || m >= hi) continue;
-                    const float* r = a.wv + (int64_t)__builtin_amdgcn_readfirstlane(kept[m & (D2V_RING - 1)]) * a.d;
+                    const float* r = d2v_row(a.wv, a.d, kept, m);
 #pragma unroll
                     for (int q = 0; q < NV; ++q) l1[q] += d2v_ld(r + lane + 64 * q) + pend[j][q];
                 }
-                const float inv = 1.f / (float)(hi - lo);               // (hi - lo - 1) window words + the doc tag
+                const float inv = 1.f / (float)(hi - lo);               // d2v_dm_mean's, over memory + pending (pend[j] stays in registers only under a compile-time j)
 #pragma unroll
                 for (int q = 0; q < NV; ++q) l1[q] *= inv;
-                d2v_unit<NV>(a, s_top, top_n, top_s, l1, word, alpha, doc, i, 0, lane, work, lsum, lcnt);
+                d2v_unit<NV>(a, a.k0, a.k1, s_top, top_n, top_s, l1, word, alpha, doc, i, 0, lane, work, lsum, lcnt);
 #pragma unroll
                 for (int q = 0; q < NV; ++q) dreg[q] += work[q];
 #pragma unroll
@@ -228,40 +270,25 @@ __global__ __launch_bounds__(256, DW > 0 ? 1 : (NV <= 2 ? 6 : 5)) void k_d2v_epo
                 for (int q = 0; q < NV; ++q) pend[NPEND - 1][q] = 0.f;
             } else if (dm) {
                 float l1[NV];
-#pragma unroll
-                for (int q = 0; q < NV; ++q) l1[q] = dreg[q];
-                for (int m = lo; m < hi; ++m) {
-                    if (m == i) continue;
-                    const float* r = a.wv + (int64_t)__builtin_amdgcn_readfirstlane(kept[m & (D2V_RING - 1)]) * a.d;
-#pragma unroll
-                    for (int q = 0; q < NV; ++q) l1[q] += d2v_ld(r + lane + 64 * q);
-                }
-                const float inv = 1.f / (float)(hi - lo);               // (hi - lo - 1) window words + the doc tag
-#pragma unroll
-                for (int q = 0; q < NV; ++q) l1[q] *= inv;
-                d2v_unit<NV>(a, s_top, top_n, top_s, l1, word, alpha, doc, i, 0, lane, work, lsum, lcnt);
+                d2v_dm_mean<NV, false>(a.wv, a.d, kept, lo, hi, i, dreg, lane, l1);
+                d2v_unit<NV>(a, a.k0, a.k1, s_top, top_n, top_s, l1, word, alpha, doc, i, 0, lane, work, lsum, lcnt);
 #pragma unroll
                 for (int q = 0; q < NV; ++q) dreg[q] += work[q];
-                for (int m = lo; m < hi; ++m) {
-                    if (m == i) continue;
-                    float* r = a.wv + (int64_t)__builtin_amdgcn_readfirstlane(kept[m & (D2V_RING - 1)]) * a.d;
-#pragma unroll
-                    for (int q = 0; q < NV; ++q) unsafeAtomicAdd(r + lane + 64 * q, work[q]);
-                }
+                for (int m = lo; m < hi; ++m)
+                    if (m != i) flush_row(m, work);
             } else {
                 int u = 0;
                 for (int m = lo; m < hi; ++m) {
                     if (m == i) continue;
-                    float* r = a.wv + (int64_t)__builtin_amdgcn_readfirstlane(kept[m & (D2V_RING - 1)]) * a.d;
+                    float* r = d2v_row(a.wv, a.d, kept, m);
                     float x[NV];
 #pragma unroll
                     for (int q = 0; q < NV; ++q) x[q] = d2v_ld(r + lane + 64 * q);
-                    d2v_unit<NV>(a, s_top, top_n, top_s, x, word, alpha, doc, i, 1 + u, lane, work, lsum, lcnt);
-#pragma unroll
-                    for (int q = 0; q < NV; ++q) unsafeAtomicAdd(r + lane + 64 * q, work[q]);
+                    d2v_unit<NV>(a, a.k0, a.k1, s_top, top_n, top_s, x, word, alpha, doc, i, 1 + u, lane, work, lsum, lcnt);
+                    d2v_row_add(r, lane, work);
                     ++u;
                 }
-                d2v_unit<NV>(a, s_top, top_n, top_s, dreg, word, alpha, doc, i, 0, lane, work, lsum, lcnt);
+                d2v_unit<NV>(a, a.k0, a.k1, s_top, top_n, top_s, dreg, word, alpha, doc, i, 0, lane, work, lsum, lcnt);
 #pragma unroll
                 for (int q = 0; q < NV; ++q) dreg[q] += work[q];
             }
@@ -289,7 +316,7 @@ __host__ __device__ inline void d2v_key(uint64_t seed, uint64_t epoch, uint32_t&
 
 // ---- infer_vector (src/mdl/emb/d2v.py:96-98): the vector of a document that was not in the corpus, trained against FROZEN tables.  gensim's infer_vector is train() on one
 // document with learn_words = learn_hidden = False and train_words = False: the doc vector is the only thing that moves, so every query is independent of every other - no
-// atomics, no store to a table, plain cached loads (d2v_ld's agent scope is for rows other waves add to), and the result is a pure function of (words, id, initial vector,
+// atomics, no store to a table, plain cached loads (d2v_ld<true>: the agent scope is for rows other waves add to), and the result is a pure function of (words, id, initial vector,
 // tables, seed) whatever wave runs it.  One wave per query, the vector in registers from the initial row to the final store across ALL epochs of the call.
 struct D2vInferArgs {
     int64_t n, n_vocab; int d, window, negative, serial, dm, epochs;
@@ -299,57 +326,19 @@ struct D2vInferArgs {
     uint64_t seed;
 };
 
-// d2v_unit's two-level search of the cumulative table (bisect_left(cum_table, r % cum_table[-1]) through the LDS level), as a function of its own: folding the trainer's copy
-// into it changes the trainer's register allocation, and the trainer's code is to stay as measured
-__device__ __forceinline__ int d2v_table_search(const uint32_t* cum_table, int64_t n_vocab, const uint32_t* __restrict__ top, int top_n, int top_s, uint32_t rk) {
-    const uint32_t v = rk % cum_table[n_vocab - 1];
-    int blo = 0, bhi = top_n;
-    while (blo < bhi) { const int mid = (blo + bhi) >> 1; if (top[mid] < v) blo = mid + 1; else bhi = mid; }
-    int64_t lo = (int64_t)blo * top_s, hi = min((int64_t)(blo + 1) * top_s, n_vocab);
-    if (blo >= top_n) { lo = n_vocab; hi = n_vocab; }        // (v is below cum_table[-1]: never taken)
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (cum_table[mid] < v) lo = mid + 1; else hi = mid; }
-    return (int)lo;
-}
-
-// d2v_unit's frozen twin: the same draws, targets, order of operations and skips; syn1neg is read, never written
-template <int NV>
-__device__ __forceinline__ void d2v_unit_frozen(const D2vInferArgs& a, uint32_t k0, uint32_t k1, const uint32_t* __restrict__ top, int top_n, int top_s, const float (&x)[NV], int word, float alpha,
-                                                int64_t doc, int pos, int lane, float (&w)[NV]) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) w[k] = 0.f;
-    const uint4 r4 = d2v_draw(k0, k1, doc, pos, 0, SLOT_NEG0 + ((lane >> 2) & 1));
-    const uint32_t rk = (lane & 3) == 0 ? r4.x : (lane & 3) == 1 ? r4.y : (lane & 3) == 2 ? r4.z : r4.w;
-    const int tgt = d2v_table_search(a.cum_table, a.n_vocab, top, top_n, top_s, rk);
-    for (int k = 0; k <= a.negative; ++k) {
-        const int t = __builtin_amdgcn_readfirstlane(k == 0 ? word : __shfl(tgt, k - 1, 64));
-        if (k > 0 && t == word) continue;
-        const float label = k == 0 ? 1.f : 0.f;
-        const float* __restrict__ row = a.syn1neg + (int64_t)t * a.d;
-        float rv[NV], f = 0.f;
-#pragma unroll
-        for (int q = 0; q < NV; ++q) { rv[q] = row[lane + 64 * q]; f += x[q] * rv[q]; }
-        f = wave_reduce_sum(f);
-        if (f <= -D2V_MAX_EXP || f >= D2V_MAX_EXP) continue;
-        const float g = (label - d2v_sigmoid_table(f)) * alpha;
-#pragma unroll
-        for (int q = 0; q < NV; ++q) w[q] += g * rv[q];
-    }
-}
-
+// The kernel shares the trainer's prologue, ring fill, PV-DM mean and unit (d2v_unit<NV, true>, d2v_dm_mean<NV, true>: the FROZEN forms); what is its own is the loop:
+// the epochs inside the kernel, around the positions.
 // (the trainer's plain-kernel bounds; a query is a chain of dependent row reads, so what hides the latency is waves per SIMD.  The compiler's report for NV = 1 / 2 / 3 / 4:
 //  63 / 67 / 71 / 72 VGPRs, no spill, no scratch, 20 KiB of LDS a workgroup - 8 / 7 / 7 / 7 waves a SIMD by registers, 8 workgroups a CU by LDS)
 template <int NV>
 __global__ __launch_bounds__(256, NV <= 2 ? 6 : 5) void k_d2v_infer(D2vInferArgs a) {
     __shared__ int s_kept[4][D2V_RING];
     __shared__ uint32_t s_top[D2V_TOP];
-    const int lane = threadIdx.x & 63, wv_id = threadIdx.x >> 6;
-    int* kept = s_kept[wv_id];
-    const int top_s = (int)((a.n_vocab + D2V_TOP - 1) / D2V_TOP), top_n = (int)((a.n_vocab + top_s - 1) / top_s);
-    for (int k = threadIdx.x; k < top_n; k += blockDim.x) s_top[k] = a.cum_table[min((int64_t)(k + 1) * top_s, a.n_vocab) - 1];
-    __syncthreads();
-    const int64_t first = a.serial ? 0 : (int64_t)blockIdx.x * 4 + wv_id;
-    const int64_t stride = a.serial ? 1 : (int64_t)gridDim.x * 4;
-    if (a.serial && (blockIdx.x != 0 || wv_id != 0)) return;
+    const int lane = threadIdx.x & 63;
+    int* kept = s_kept[threadIdx.x >> 6];
+    int top_s, top_n; int64_t first, stride;
+    if (!d2v_prologue(a.cum_table, a.n_vocab, a.serial, s_top, top_s, top_n, first, stride)) return;
+    float no_loss = 0.f;                       // (the FROZEN unit leaves its loss arguments alone)
     for (int64_t qi = first; qi < a.n; qi += stride) {
         const int64_t doc = a.ids ? a.ids[qi] : qi;          // what the draws are counted by: a query's vector does not depend on its place in the batch
         const int64_t p0 = a.q_ptr[qi];
@@ -363,39 +352,19 @@ __global__ __launch_bounds__(256, NV <= 2 ? 6 : 5) void k_d2v_infer(D2vInferArgs
             uint32_t k0, k1;
             d2v_key(a.seed, (uint64_t)e, k0, k1);
             const float alpha = (float)alpha_d;
-            int K = 0, base = 0;               // as in k_d2v_epoch: kept words compacted so far (<= D2V_MAX_DOC), raw words scanned so far
+            int K = 0, base = 0;               // d2v_fill_ring's: kept words compacted so far, raw words scanned so far
             for (int i = 0;; ++i) {
-                while (K < i + a.window + 1 && base < L && K < D2V_MAX_DOC) {
-                    const int p = base + lane;
-                    int wd = 0; bool keep = false;
-                    if (p < L) { wd = a.q_words[p0 + p]; keep = a.sample_int[wd] >= d2v_draw(k0, k1, doc, p, 0, SLOT_KEEP).x; }
-                    const unsigned long long m = __ballot(keep);
-                    const int at = K + __popcll(m & ((1ull << lane) - 1ull));
-                    if (keep && at < D2V_MAX_DOC) kept[at & (D2V_RING - 1)] = wd;
-                    K = min(K + (int)__popcll(m), D2V_MAX_DOC);
-                    base += 64;
-                    __builtin_amdgcn_wave_barrier();
-                }
+                d2v_fill_ring(kept, a.q_words + p0, L, a.sample_int, k0, k1, doc, i + a.window + 1, lane, K, base);
                 if (i >= K) break;
                 const int b = (int)(d2v_draw(k0, k1, doc, i, 0, SLOT_WINDOW).x % (uint32_t)a.window), word = __builtin_amdgcn_readfirstlane(kept[i & (D2V_RING - 1)]);
                 float work[NV];
                 if (a.dm) {
                     const int lo = max(0, i - a.window + b), hi = min(K, i + a.window + 1 - b);
                     float l1[NV];
-#pragma unroll
-                    for (int q = 0; q < NV; ++q) l1[q] = dreg[q];
-                    for (int m = lo; m < hi; ++m) {
-                        if (m == i) continue;
-                        const float* __restrict__ r = a.wv + (int64_t)__builtin_amdgcn_readfirstlane(kept[m & (D2V_RING - 1)]) * a.d;
-#pragma unroll
-                        for (int q = 0; q < NV; ++q) l1[q] += r[lane + 64 * q];
-                    }
-                    const float inv = 1.f / (float)(hi - lo);
-#pragma unroll
-                    for (int q = 0; q < NV; ++q) l1[q] *= inv;
-                    d2v_unit_frozen<NV>(a, k0, k1, s_top, top_n, top_s, l1, word, alpha, doc, i, lane, work);
+                    d2v_dm_mean<NV, true>(a.wv, a.d, kept, lo, hi, i, dreg, lane, l1);
+                    d2v_unit<NV, true>(a, k0, k1, s_top, top_n, top_s, l1, word, alpha, doc, i, 0, lane, work, no_loss, no_loss);
                 } else      // PV-DBOW: infer_vector leaves train_words = False - the window-word units do not run (and their draws are not taken)
-                    d2v_unit_frozen<NV>(a, k0, k1, s_top, top_n, top_s, dreg, word, alpha, doc, i, lane, work);
+                    d2v_unit<NV, true>(a, k0, k1, s_top, top_n, top_s, dreg, word, alpha, doc, i, 0, lane, work, no_loss, no_loss);
 #pragma unroll
                 for (int q = 0; q < NV; ++q) dreg[q] += work[q];
             }
@@ -405,6 +374,33 @@ __global__ __launch_bounds__(256, NV <= 2 ? 6 : 5) void k_d2v_infer(D2vInferArgs
 #pragma unroll
         for (int q = 0; q < NV; ++q) drow[lane + 64 * q] = dreg[q];
     }
+}
+
+// ---- the host side's checks and launch shape, once.  A check returns the text of what is wrong under the caller's prefix, or an empty string
+std::string d2v_param_error(const std::string& prefix, const char* window_note, int dm, int window, int negative) {
+    if (window < 1 || window > 255 || (!dm && 2 * window > 254)) return prefix + ": window outside 1..255 (dm = 0: 1..127" + window_note;
+    if (negative < 0 || negative > 8) return prefix + ": negative outside 0..8";
+    if (dm != 0 && dm != 1) return prefix + ": dm is 0 or 1";
+    return "";
+}
+// documents in CSR form: ptr (called `name` in the text) [n + 1] from 0 and monotone, words inside the vocabulary
+std::string d2v_csr_error(const std::string& prefix, const char* name, const int64_t* ptr, int64_t n, const int32_t* words, int64_t n_vocab) {
+    if (ptr[0] != 0) return prefix + ": " + name + "[0] != 0";
+    for (int64_t i = 0; i < n; ++i) if (ptr[i + 1] < ptr[i]) return prefix + ": " + name + " not monotone";
+    for (int64_t p = 0; p < ptr[n]; ++p) if (words[p] < 0 || words[p] >= n_vocab) return prefix + ": word index out of the vocabulary";
+    return "";
+}
+// n one-wave items.  Parallel: enough waves to fill the chip several times over, each striding through the items; serial: one wave
+struct D2vDims { dim3 grid, block; };
+D2vDims d2v_dims(int64_t n, bool serial) { return {dim3(serial ? 1u : (unsigned)std::min<int64_t>((n + 3) / 4, 256 * 16)), dim3(serial ? 64 : 256)}; }
+// ntf_d2v_get / ntf_d2v_set: the table `what` names and its rows, on the handle's device with its stream drained
+int d2v_table(ntf_d2v* h, const void* host, int what, float** table, int64_t* rows) {
+    if (!h || !host || what < 0 || what > 2) return NTF_EINVAL;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    *table = what == 0 ? h->dv : what == 1 ? h->wv : h->syn1neg;
+    *rows = what == 0 ? h->n_docs : h->n_vocab;
+    return NTF_OK;
 }
 
 }  // namespace
@@ -428,10 +424,9 @@ extern "C" int ntf_d2v_create(int device, int64_t n_docs, int64_t n_vocab, int32
     *out = nullptr;
     if (n_docs < 1 || n_vocab < 1 || d < 1 || d > 256 || !doc_ptr || !words || !sample_int || !cum_table || !init_wv || !init_dv) {
         g_d2v_create_error = "d2v: need n_docs >= 1, n_vocab >= 1, 1 <= d <= 256, the documents, the vocabulary tables and the initial vectors"; return NTF_EINVAL; }
-    if (doc_ptr[0] != 0) { g_d2v_create_error = "d2v: doc_ptr[0] != 0"; return NTF_EINVAL; }
-    for (int64_t i = 0; i < n_docs; ++i) if (doc_ptr[i + 1] < doc_ptr[i]) { g_d2v_create_error = "d2v: doc_ptr not monotone"; return NTF_EINVAL; }
+    const std::string bad = d2v_csr_error("d2v", "doc_ptr", doc_ptr, n_docs, words, n_vocab);
+    if (!bad.empty()) { g_d2v_create_error = bad; return NTF_EINVAL; }
     const int64_t nw = doc_ptr[n_docs];
-    for (int64_t p = 0; p < nw; ++p) if (words[p] < 0 || words[p] >= n_vocab) { g_d2v_create_error = "d2v: word index out of the vocabulary"; return NTF_EINVAL; }
     for (int64_t v = 1; v < n_vocab; ++v) if (cum_table[v] < cum_table[v - 1]) { g_d2v_create_error = "d2v: cum_table not monotone"; return NTF_EINVAL; }
     if (cum_table[n_vocab - 1] == 0) { g_d2v_create_error = "d2v: empty cum_table"; return NTF_EINVAL; }
     int ndev = 0;
@@ -466,9 +461,8 @@ extern "C" int ntf_d2v_create(int device, int64_t n_docs, int64_t n_vocab, int32
 extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32_t negative, double alpha_start, double alpha_end, uint64_t epoch, int32_t serial,
                                    const int64_t* order, const double* progress, double* mean_loss, double* device_ms) {
     if (!h) { g_d2v_create_error = "d2v train: the handle is NULL"; return NTF_EINVAL; }
-    if (window < 1 || window > 255 || (!dm && 2 * window > 254)) FAIL(h, NTF_EINVAL, "d2v train: window outside 1..255 (dm = 0: 1..127: the unit index 1 + u of a window word is 8 bits of the Philox counter)");
-    if (negative < 0 || negative > 8) FAIL(h, NTF_EINVAL, "d2v train: negative outside 0..8");
-    if (dm != 0 && dm != 1) FAIL(h, NTF_EINVAL, "d2v train: dm is 0 or 1");
+    const std::string bad = d2v_param_error("d2v train", ": the unit index 1 + u of a window word is 8 bits of the Philox counter)", dm, window, negative);
+    if (!bad.empty()) FAIL(h, NTF_EINVAL, bad);
     HIPCHK(h, hipSetDevice(h->device));
     if (order) {
         std::vector<char> seen((size_t)h->n_docs, 0);
@@ -487,22 +481,17 @@ extern "C" int ntf_d2v_train_epoch(ntf_d2v* h, int32_t dm, int32_t window, int32
     a.doc_ptr = h->doc_ptr; a.words = h->words; a.sample_int = h->sample_int; a.cum_table = h->cum_table; a.order = order ? h->order : nullptr; a.progress = progress ? h->progress : nullptr;
     a.dv = h->dv; a.wv = h->wv; a.syn1neg = h->syn1neg; a.alpha_start = alpha_start; a.alpha_end = alpha_end; a.loss = mean_loss ? h->d_loss : nullptr;
     d2v_key(h->seed, epoch, a.k0, a.k1);
-    // parallel: enough waves to fill the chip several times over, each striding through the documents
-    const int64_t want = (h->n_docs + 3) / 4;
-    const dim3 grid(serial ? 1u : (unsigned)std::min<int64_t>(want, 256 * 16)), block(serial ? 64 : 256);
-    if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
+    const D2vDims dims = d2v_dims(h->n_docs, serial != 0);
     // PV-DM at the reference's window (src/mdl/emb/__config__.yaml: w = 5): word-vector additions deferred to one per kept position (k_d2v_epoch<.., 5>); NTF_D2V_DEFER=0 (read per call): the plain kernel
     const char* defer_env = getenv("NTF_D2V_DEFER");
     const bool defer_ok = !(defer_env && atoi(defer_env) == 0);
-    if (dm && window == 5 && defer_ok && h->dp >= 128) {     // (d = 64: the rows are 256 B and the plain kernel's shorter chain wins - 45.7 against 49.4 ms; d = 128 / 192 / 256: 55 / 78 / 98 against 66 / 102 / 133)
-        with_nv<2>(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL((k_d2v_epoch<decltype(nv)::value, 5>), grid, block, 0, h->st, a, dm); });   // <1, 5> is never launched, so never built
-    } else
-        with_nv(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL(k_d2v_epoch<decltype(nv)::value>, grid, block, 0, h->st, a, dm); });
-    if (device_ms) HIPCHK(h, hipEventRecord(h->ev1, h->st));
-    hipError_t s = hipGetLastError();
-    if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("d2v kernel launch: ") + hipGetErrorString(s));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    if (device_ms) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
+    const int rc = timed_launch(h, device_ms, "d2v", [&] {
+        if (dm && window == 5 && defer_ok && h->dp >= 128) {     // (d = 64: the rows are 256 B and the plain kernel's shorter chain wins - 45.7 against 49.4 ms; d = 128 / 192 / 256: 55 / 78 / 98 against 66 / 102 / 133)
+            with_nv<2>(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL((k_d2v_epoch<decltype(nv)::value, 5>), dims.grid, dims.block, 0, h->st, a, dm); });   // <1, 5> is never launched, so never built
+        } else
+            with_nv(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL(k_d2v_epoch<decltype(nv)::value>, dims.grid, dims.block, 0, h->st, a, dm); });
+    });
+    if (rc != NTF_OK) return rc;
     if (mean_loss) {
         double l[2] = {0, 0};
         HIPCHK(h, hipMemcpy(l, h->d_loss, 16, hipMemcpyDeviceToHost));
@@ -516,15 +505,13 @@ extern "C" int ntf_d2v_infer(ntf_d2v* h, int64_t n, const int64_t* q_ptr, const 
     if (!h) { g_d2v_create_error = "d2v infer: the handle is NULL"; return NTF_EINVAL; }
     if (!q_ptr || !q_words || !init || !out) FAIL(h, NTF_EINVAL, "d2v infer: q_ptr, q_words, init and out are required");
     if (n < 1) FAIL(h, NTF_EINVAL, "d2v infer: n < 1");
-    if (window < 1 || window > 255 || (!dm && 2 * window > 254)) FAIL(h, NTF_EINVAL, "d2v infer: window outside 1..255 (dm = 0: 1..127), as ntf_d2v_train_epoch");
-    if (negative < 0 || negative > 8) FAIL(h, NTF_EINVAL, "d2v infer: negative outside 0..8");
-    if (dm != 0 && dm != 1) FAIL(h, NTF_EINVAL, "d2v infer: dm is 0 or 1");
+    std::string bad = d2v_param_error("d2v infer", "), as ntf_d2v_train_epoch", dm, window, negative);
+    if (!bad.empty()) FAIL(h, NTF_EINVAL, bad);
     if (epochs < 1) FAIL(h, NTF_EINVAL, "d2v infer: epochs < 1");
     if (!std::isfinite(alpha) || !std::isfinite(min_alpha)) FAIL(h, NTF_EINVAL, "d2v infer: alpha / min_alpha not finite");
-    if (q_ptr[0] != 0) FAIL(h, NTF_EINVAL, "d2v infer: q_ptr[0] != 0");
-    for (int64_t i = 0; i < n; ++i) if (q_ptr[i + 1] < q_ptr[i]) FAIL(h, NTF_EINVAL, "d2v infer: q_ptr not monotone");
+    bad = d2v_csr_error("d2v infer", "q_ptr", q_ptr, n, q_words, h->n_vocab);
+    if (!bad.empty()) FAIL(h, NTF_EINVAL, bad);
     const int64_t nw = q_ptr[n];
-    for (int64_t p = 0; p < nw; ++p) if (q_words[p] < 0 || q_words[p] >= h->n_vocab) FAIL(h, NTF_EINVAL, "d2v infer: word index out of the vocabulary");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->st));
     const int64_t dp = h->dp; const int d = h->d;
@@ -544,35 +531,23 @@ extern "C" int ntf_d2v_infer(ntf_d2v* h, int64_t n, const int64_t* q_ptr, const 
     a.q_ptr = h->q_ptr; a.q_words = h->q_words; a.ids = ids ? h->q_ids : nullptr; a.sample_int = h->sample_int; a.cum_table = h->cum_table;
     a.wv = h->wv; a.syn1neg = h->syn1neg; a.vec = h->q_vec;
     a.alpha = alpha; a.delta = (alpha - min_alpha) / (double)std::max(epochs - 1, 1); a.seed = seed;
-    const int64_t want = (n + 3) / 4;
-    const dim3 grid(serial ? 1u : (unsigned)std::min<int64_t>(want, 256 * 16)), block(serial ? 64 : 256);
-    if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
-    with_nv(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL(k_d2v_infer<decltype(nv)::value>, grid, block, 0, h->st, a); });
-    if (device_ms) HIPCHK(h, hipEventRecord(h->ev1, h->st));
-    hipError_t s = hipGetLastError();
-    if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("d2v infer kernel launch: ") + hipGetErrorString(s));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    if (device_ms) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
+    const D2vDims dims = d2v_dims(n, serial != 0);
+    const int rc = timed_launch(h, device_ms, "d2v infer", [&] { with_nv(h->dp / 64, [&](auto nv) { hipLaunchKernelGGL(k_d2v_infer<decltype(nv)::value>, dims.grid, dims.block, 0, h->st, a); }); });
+    if (rc != NTF_OK) return rc;
     HIPCHK(h, hipMemcpy2D(out, (size_t)d * 4, h->q_vec, (size_t)dp * 4, (size_t)d * 4, (size_t)n, hipMemcpyDeviceToHost));
     return NTF_OK;
 }
 
 extern "C" int ntf_d2v_get(ntf_d2v* h, int what, float* host) {   // what: 0 = doc vectors [n_docs, d], 1 = word vectors [n_vocab, d], 2 = syn1neg [n_vocab, d]
-    if (!h || !host || what < 0 || what > 2) return NTF_EINVAL;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    const float* src = what == 0 ? h->dv : what == 1 ? h->wv : h->syn1neg;
-    const int64_t rows = what == 0 ? h->n_docs : h->n_vocab;
+    float* src; int64_t rows;
+    if (const int rc = d2v_table(h, host, what, &src, &rows); rc != NTF_OK) return rc;
     HIPCHK(h, hipMemcpy2D(host, (size_t)h->d * 4, src, (size_t)h->dp * 4, (size_t)h->d * 4, (size_t)rows, hipMemcpyDeviceToHost));
     return NTF_OK;
 }
 
 extern "C" int ntf_d2v_set(ntf_d2v* h, int what, const float* host) {   // resume from a saved table (same `what` as ntf_d2v_get)
-    if (!h || !host || what < 0 || what > 2) return NTF_EINVAL;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    float* dst = what == 0 ? h->dv : what == 1 ? h->wv : h->syn1neg;
-    const int64_t rows = what == 0 ? h->n_docs : h->n_vocab;
+    float* dst; int64_t rows;
+    if (const int rc = d2v_table(h, host, what, &dst, &rows); rc != NTF_OK) return rc;
     HIPCHK(h, hipMemcpy2D(dst, (size_t)h->dp * 4, host, (size_t)h->d * 4, (size_t)h->d * 4, (size_t)rows, hipMemcpyHostToDevice));
     return NTF_OK;
 }

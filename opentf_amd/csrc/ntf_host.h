@@ -1,5 +1,5 @@
 // The host scaffold of every entry of the library, once: the check macros and allocators of a handle with an `err` string (ntf_engine, ntf_n2v, ntf_d2v,
-// ntf_knn, ntf_link), the RAII device buffer of the handle-less entries (ntf_metrics, ntf_auc, ntf_cooc), the upload of a host table into padded device rows and the dispatch of run-time widths and flags onto the kernels' template arguments.
+// ntf_knn, ntf_link), the RAII device buffer of the handle-less entries (ntf_metrics, ntf_auc, ntf_cooc), the timed launch of the stand-alone entries (ntf_d2v, ntf_knn), the upload of a host table into padded device rows and the dispatch of run-time widths and flags onto the kernels' template arguments.
 #pragma once
 #include "../../include/opentf_amd.h"
 #include <hip/hip_runtime.h>
@@ -35,6 +35,19 @@ template <class H, typename T> int dev_grow(H* h, T** p, int64_t* cap, int64_t n
     const int rc = dev_alloc(h, p, n);
     if (rc == NTF_OK) *cap = n;
     return rc;
+}
+
+// what `launch` puts on h->st, then the synchronize; device_ms (may be null): the device time between the handle's event pair ev0 / ev1, made on first use.
+// A launch error is "<what> kernel launch: <HIP's text>"
+template <class H, class F> int timed_launch(H* h, double* device_ms, const char* what, F&& launch) {
+    if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
+    launch();
+    if (device_ms) HIPCHK(h, hipEventRecord(h->ev1, h->st));
+    const hipError_t s = hipGetLastError();
+    if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string(what) + " kernel launch: " + hipGetErrorString(s));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    if (device_ms) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
+    return NTF_OK;
 }
 
 // a device buffer that lives as long as its owner; an empty request still allocates (16 bytes), so `p` is never null after a success

@@ -168,22 +168,19 @@ extern "C" int ntf_knn_query(ntf_knn* h, const float* queries, int64_t n, int32_
     HIPCHK(h, hipMemcpyAsync(&flag, h->flag, 4, hipMemcpyDeviceToHost, h->st));
     HIPCHK(h, hipStreamSynchronize(h->st));
     if (flag) FAIL(h, NTF_EINVAL, "knn query: the f32 squared norm of a query overflows");
-    if (device_ms) { if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); } HIPCHK(h, hipEventRecord(h->ev0, h->st)); }
-    for (int64_t g0 = 0; g0 < n; g0 += G) {
-        const int ng = (int)std::min<int64_t>(G, n - g0);
-        for (int64_t r0 = 0; r0 < N; r0 += R) {
-            const int rr = (int)std::min<int64_t>(R, N - r0);
-            launch_sims<SimCosine>(h->st, h->n_cu, plan.nqt_max, h->table, h->rinv, h->q + g0 * dp, h->q_rinv + g0, h->ws, r0, R, rr, ng, (int)dp);
-            hipLaunchKernelGGL(k_knn_select, dim3((unsigned)ng), dim3(1024), 0, h->st, h->ws, R, rr, r0, (int)topn, exclude ? h->q_excl + g0 : nullptr, h->run, r0 == 0 ? 1 : 0);
+    const int rc = timed_launch(h, device_ms, "knn", [&] {
+        for (int64_t g0 = 0; g0 < n; g0 += G) {
+            const int ng = (int)std::min<int64_t>(G, n - g0);
+            for (int64_t r0 = 0; r0 < N; r0 += R) {
+                const int rr = (int)std::min<int64_t>(R, N - r0);
+                launch_sims<SimCosine>(h->st, h->n_cu, plan.nqt_max, h->table, h->rinv, h->q + g0 * dp, h->q_rinv + g0, h->ws, r0, R, rr, ng, (int)dp);
+                hipLaunchKernelGGL(k_knn_select, dim3((unsigned)ng), dim3(1024), 0, h->st, h->ws, R, rr, r0, (int)topn, exclude ? h->q_excl + g0 : nullptr, h->run, r0 == 0 ? 1 : 0);
+            }
+            const int64_t ne = (int64_t)ng * topn;
+            hipLaunchKernelGGL(k_knn_finish, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->st, h->run, ne, h->o_idx + g0 * topn, h->o_sims + g0 * topn);
         }
-        const int64_t ne = (int64_t)ng * topn;
-        hipLaunchKernelGGL(k_knn_finish, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->st, h->run, ne, h->o_idx + g0 * topn, h->o_sims + g0 * topn);
-        const hipError_t s = hipGetLastError();
-        if (s != hipSuccess) FAIL(h, NTF_EHIP, std::string("knn kernel launch: ") + hipGetErrorString(s));
-    }
-    if (device_ms) HIPCHK(h, hipEventRecord(h->ev1, h->st));
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    if (device_ms) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1)); *device_ms = ms; }
+    });
+    if (rc != NTF_OK) return rc;
     HIPCHK(h, hipMemcpy(out_idx, h->o_idx, (size_t)n * topn * 4, hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(out_sims, h->o_sims, (size_t)n * topn * 4, hipMemcpyDeviceToHost));
     return NTF_OK;
