@@ -114,7 +114,6 @@ struct ntf_engine {
     // touched the output layer's parameters or the operand buffers (Wp, split planes); d_kl[2] / d_range[4] hold that step's KL and range flag until it starts
     int f32_copy_merged = 1;          // NTF_F32_COPY_MERGED=0: the conditional f32 copy of sigma * eps as a launch of its own in front of every step, as in round 4 (A/B runs)
     uint64_t f32_copy_step = 0;       // step + 1 whose copy job rode in the previous step's Adam launch
-    int merge_bias = 1;               // NTF_MERGE_BIAS=0: the next step's output-bias operand as k_head's bias workgroups in a launch of their own behind the bias Adam, as in round 4 (A/B runs)
     int dp_side_bwd = 1;              // NTF_DP_SIDE_BWD=0: a deferred-dW (data-parallel) step runs its hidden layers' backward on the main stream in front of the dW chunks, as in round 4 (A/B runs)
     int dp_ranges = 1;                // NTF_DP_RANGES=0: a data-parallel rank waits for every parameter all-gather before its step, as in round 4 (A/B runs, tests)
     int ep_head_prefetch = -1;        // NTF_EP_HEAD_PREFETCH: an expert shard's phase 3 issues the next batch's head behind its hidden backward, beside its dW kernel (phase 2).  -1 (default): when the
@@ -211,6 +210,11 @@ enum { T_EPS_W = 0, T_EPS_B = 1, T_S_IN = 2, T_S_OUT = 3, T_NEG = 4 };
 
 #define DM(e, p, n) do { int _r = dev_alloc(e, p, n); if (_r) return _r; } while (0)
 template <typename T> static void dfree(T*& p) { if (p) { hipFree(p); p = nullptr; } }
+static int d2h_sync(ntf_engine* e, void* dst, const void* src, size_t bytes) {      // a copy to the host that the caller reads right away
+    HIPCHK(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return NTF_OK;
+}
 
 extern "C" int ntf_abi_version(void) { return NTF_ABI_VERSION; }
 extern "C" const char* ntf_last_error(const ntf_engine* e) { return e ? e->err.c_str() : g_create_error.c_str(); }
@@ -247,7 +251,7 @@ extern "C" int ntf_engine_create(const ntf_config* cfg, ntf_engine** out) {
     if (const char* hp = getenv("NTF_HEAD_PREFETCH")) e->head_prefetch = atoi(hp);
     if (const char* pf = getenv("NTF_PREFETCH")) e->prefetch = atoi(pf);
     if (const char* hd = getenv("NTF_HEAD")) e->head = atoi(hd);
-    if (const char* mb = getenv("NTF_MERGE_BIAS")) e->merge_bias = atoi(mb);
+    if (const char* mb = getenv("NTF_MERGE_BIAS")) if (atoi(mb) == 0) { g_create_error = "NTF_MERGE_BIAS=0 (the next step's output-bias operand as a launch of its own behind the bias Adam) was retired: the bias Adam launch produces it, bit-identical; unset the variable"; delete e; return NTF_EINVAL; }
     if (const char* sw = getenv("NTF_L0_SWEEP")) e->l0_sweep = atoi(sw);
     if (const char* fp = getenv("NTF_FNN_PIPE")) e->fnn_pipe = atoi(fp);
     if (const char* mh = getenv("NTF_MH_HEAD")) e->mh_head = atoi(mh);
@@ -541,8 +545,7 @@ extern "C" int ntf_range_fallbacks(ntf_engine* e, int64_t* steps) {
     if (!e || !steps) return NTF_EINVAL;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int32_t dev = 0;
-    HIPCHK(e, hipMemcpyAsync(&dev, e->d_range + 1, 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (int r = d2h_sync(e, &dev, e->d_range + 1, 4)) return r;
     *steps = (int64_t)dev + e->range_fallbacks_host;
     return NTF_OK;
 }
@@ -606,9 +609,11 @@ static inline float dz_scale16(const ntf_engine* e, int global_B) {   // |dz| <=
 
 // the fused output layer has split-product (fp16x3) kernels: h[-1] of 32, 64 and 128 (96, 160, 192, 224 and 256 run on the exact-f32 kernels in every mfma mode)
 static bool split_products(const ntf_engine* e) { const int h = e->layers[e->L - 1].in; return h == 32 || h == 64 || h == 128; }
+// ... and the engine's arithmetic asks for them (ntf_config.mfma)
+static bool fp16x3_mode(const ntf_engine* e) { return e->cfg.mfma == NTF_MFMA_DEFAULT || e->cfg.mfma == NTF_MFMA_FP16X3; }
 // the range flag of the fp16x3 arithmetic, or null when this engine never multiplies in fp16x3
 static int32_t* range_ptr(const ntf_engine* e) {
-    return (fused_ok(e) && split_products(e) && (e->cfg.mfma == NTF_MFMA_DEFAULT || e->cfg.mfma == NTF_MFMA_FP16X3)) ? e->d_range : nullptr;
+    return (fused_ok(e) && split_products(e) && fp16x3_mode(e)) ? e->d_range : nullptr;
 }
 
 static int check_ready(ntf_engine* e, bool need_labels) {
@@ -790,42 +795,77 @@ static int side_stream(ntf_engine* e) {
     return NTF_OK;
 }
 
+// the fields of a FusedOut that do not depend on who launches it: the shape, the hidden activations, the fp16x3 scales, the step's sign keys
+static FusedOut fused_out_base(ntf_engine* e, const StepCtx& c) {
+    const LayerInfo& lo = e->layers[e->L - 1];
+    FusedOut f; f.B = c.B; f.H = lo.in; f.M = e->cfg.dims[e->L]; f.bayes = e->cfg.bayesian; f.h = e->act[e->L - 1]; f.w_scale = kW16Scale; f.h_scale = kH16Scale;
+    if (e->cfg.bayesian) { f.s_in = sign_spec(e, c, e->L - 1, T_S_IN, lo.in); f.s_out = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out); }
+    return f;
+}
+// The weight-operand producer (k_flipout_perturb over the output layer's rho_weight) of step c on e->st: sigma * eps and, as the site asks, its by-products
+struct WpOpts {
+    bool kl = true, f32 = true;  // the layer's KL term into the step's sum (a pass over mu too; off: weight 0, inference); the f32 copy of sigma * eps (Wp; off: a lean step reads the planes only)
+    bool split = true, planes_mu = true;   // the fp16 planes of sigma * eps (where the engine has them) with the range flag, and those of mu; split off: the exact-f32 arm of the inference
+    int64_t x0 = 0, nx = -1;     // experts [x0, x0 + nx) of the layer (-1: all of them), generator counters as the whole layer draws them
+    uint16_t* ring = nullptr;    // the planes of sigma * eps go here, not into the engine's image (a ring slot of infer_mc_fused)
+    PerturbChain chain;          // an evaluation chain's link (run_step); a lean one (raise_if) leaves the KL term and the planes of mu to the chain's first step
+    const int* only_if = nullptr;  // nothing but the f32 copy, and only if this device flag is raised (a step on prefetched operands that falls back to the exact-f32 kernels)
+};
+static void launch_out_weight_operand(ntf_engine* e, const StepCtx& c, const WpOpts& o = WpOpts()) {
+    const LayerInfo& lo = e->layers[e->L - 1];
+    const int64_t nx = o.nx < 0 ? lo.out : o.nx, o0 = o.x0 * lo.in, n = nx * lo.in;
+    const float* rho = e->P + lo.off[NTF_P_RHO_WEIGHT] + o0; const float* mu = e->P + lo.off[NTF_P_WEIGHT] + o0;
+    NormalSpec es = normal_spec(e, c, e->L - 1, T_EPS_W); es.qbase += o0 / 4;
+    if (o.only_if) { launch_flipout_perturb(e->st, rho, nullptr, n, es, e->Wp[e->L - 1] + o0, 0.0, nullptr, nullptr, nullptr, nullptr, 0, 1.f, nullptr, o.only_if); return; }
+    const bool lean = o.chain.raise_if != nullptr; const int64_t pl0 = o.x0 / 32 * 64 * lo.in;      // the planes of 32-expert tile x0 / 32 (fused_planes_elems layout)
+    uint16_t* const pl_w = !o.split ? nullptr : o.ring ? o.ring : e->pl_wp ? e->pl_wp + pl0 : nullptr;
+    launch_flipout_perturb(e->st, rho, o.kl && !lean ? mu : nullptr, n, es, o.f32 ? e->Wp[e->L - 1] + o0 : nullptr, o.kl ? 1.0 / ((double)e->Mg * lo.in) : 0.0, e->d_kl,
+                           pl_w, o.split && o.planes_mu && !lean && e->pl_wp ? e->pl_mu + pl0 : nullptr, mu, lo.in, kW16Scale, o.split ? range_ptr(e) : nullptr, nullptr, o.chain);
+}
+// ... and the bias-operand producer (k_flipout_perturb over its rho_bias): experts [x0, x0 + nx) into `to` (null: the engine's bp, at x0)
+static void launch_out_bias_operand(ntf_engine* e, const StepCtx& c, bool kl, int64_t x0 = 0, int64_t nx = -1, float* to = nullptr) {
+    const LayerInfo& lo = e->layers[e->L - 1];
+    NormalSpec es = normal_spec(e, c, e->L - 1, T_EPS_B); es.qbase += x0 / 4;
+    launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS] + x0, kl ? e->P + lo.off[NTF_P_BIAS] + x0 : nullptr, nx < 0 ? lo.out : nx, es, to ? to : e->bp[e->L - 1] + x0,
+                           kl ? 1.0 / (double)e->Mg : 0.0, e->d_kl);
+}
+
 // gather -> hidden layer -> operand images of one batch as ONE kernel (ntf_head.hip) into workspace `ws`; `want_planes`: also the dW kernel's h planes / s_in words.
 // kl == null: no KL terms (they are in the step's sum already); with_bias: the extra workgroups that produce the output layer's bias operand; rflag: where an
 // activation beyond the fp16 window is reported (this step's flag, or the next step's slot for a prefetched head).
 // the multi-hot input's head (round 6): no one-kernel form (the first layer is a gather-sum over 90 671 rows, not a 128-wide product) - the same chain of launches a step used to
 // issue inline, as a unit on stream `st` into workspace `ws`, so that it can be issued for the NEXT batch beside the dW kernel like k_head
 static bool mh_head_ok(const ntf_engine* e) {
-    return e->mh_head && e->head && e->L == 2 && e->cfg.input_mode == NTF_INPUT_MULTIHOT && e->cfg.bayesian && fused_ok(e) && e->layers[e->L - 1].in == 128 && e->pl_mu != nullptr &&
-           (e->cfg.mfma == NTF_MFMA_DEFAULT || e->cfg.mfma == NTF_MFMA_FP16X3);
+    return e->mh_head && e->head && e->L == 2 && e->cfg.input_mode == NTF_INPUT_MULTIHOT && e->cfg.bayesian && fused_ok(e) && e->layers[e->L - 1].in == 128 && e->pl_mu != nullptr && fp16x3_mode(e);
 }
-static void head_launch_multihot(ntf_engine* e, hipStream_t st, const StepCtx& c, char* ws, bool want_planes, double* kl, bool with_bias, int* rflag, bool rows_part, bool skip_w0) {
+// can this engine's steps take their head as one unit (k_head, or the multi-hot form on one GPU)?  run_step's use_head and the head prefetch both ask
+static bool head_ok(const ntf_engine* e) {
+    return (mh_head_ok(e) && !e->ep) || (e->head && e->L == 2 && e->cfg.input_mode != NTF_INPUT_MULTIHOT && head_supported(e->cfg.dims[0], e->cfg.dims[1]) && fp16x3_mode(e));
+}
+static void head_launch_multihot(ntf_engine* e, hipStream_t st, const StepCtx& c, char* ws, bool want_planes, double* kl, bool with_bias, int* rflag, bool skip_w0) {
     const LayerInfo& l0 = e->layers[0]; const LayerInfo& lo = e->layers[e->L - 1];
     const int M = e->cfg.dims[e->L];
     float* W0 = e->P + l0.off[NTF_P_WEIGHT]; float* b0 = e->P + l0.off[NTF_P_BIAS];
-    if (rows_part) {
-        // Flipout operands of the first layer (k_flipout_perturb: + its KL terms unless they are in the step's sum already); the weights' come out of the previous step's sweep
-        if (!skip_w0) launch_flipout_perturb(st, e->P + l0.off[NTF_P_RHO_WEIGHT], kl ? W0 : nullptr, l0.nw(), normal_spec(e, c, 0, T_EPS_W), e->Wp[0], 1.0 / (double)l0.nw(), kl);
-        launch_flipout_perturb(st, e->P + l0.off[NTF_P_RHO_BIAS], kl ? b0 : nullptr, l0.out, normal_spec(e, c, 0, T_EPS_B), e->bp[0], 1.0 / (double)l0.out, kl);
-        launch_multihot_fwd(st, c.rows_dev, c.B, l0.in, l0.out, e->s_indptr, e->s_indices, W0, b0, e->Wp[0], e->bp[0], sign_spec(e, c, 0, T_S_IN, l0.in), sign_spec(e, c, 0, T_S_OUT, l0.out), e->act[1]);
-        // zero-padded h, h * s_in, the s_in words and the fp16x3 range check (k_prep_h: phase 1 of the fused forward with the planes marked ready), then the dW kernel's h planes
-        FusedOut f;
-        f.B = c.B; f.H = lo.in; f.M = M; f.bayes = 1; f.train = 1; f.h = e->act[1]; f.ws = ws;
-        f.s_in = sign_spec(e, c, e->L - 1, T_S_IN, lo.in); f.s_out = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out);
-        f.split = 1; f.h_scale = kH16Scale; f.w_scale = kW16Scale; f.planes_ready = 1; f.h_ready = 0; f.rflag = rflag;
-        launch_fused_out_fwd(st, f, 1);
-        if (want_planes) launch_fused_prep_planes(st, c.B, lo.in, M, 1, ws, kH16Scale, nullptr, 0, 2);
-    }
-    if (with_bias) launch_flipout_perturb(st, e->P + lo.off[NTF_P_RHO_BIAS], kl ? e->P + lo.off[NTF_P_BIAS] : nullptr, lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1], 1.0 / (double)e->Mg, kl);
+    // Flipout operands of the first layer (k_flipout_perturb: + its KL terms unless they are in the step's sum already); the weights' come out of the previous step's sweep
+    if (!skip_w0) launch_flipout_perturb(st, e->P + l0.off[NTF_P_RHO_WEIGHT], kl ? W0 : nullptr, l0.nw(), normal_spec(e, c, 0, T_EPS_W), e->Wp[0], 1.0 / (double)l0.nw(), kl);
+    launch_flipout_perturb(st, e->P + l0.off[NTF_P_RHO_BIAS], kl ? b0 : nullptr, l0.out, normal_spec(e, c, 0, T_EPS_B), e->bp[0], 1.0 / (double)l0.out, kl);
+    launch_multihot_fwd(st, c.rows_dev, c.B, l0.in, l0.out, e->s_indptr, e->s_indices, W0, b0, e->Wp[0], e->bp[0], sign_spec(e, c, 0, T_S_IN, l0.in), sign_spec(e, c, 0, T_S_OUT, l0.out), e->act[1]);
+    // zero-padded h, h * s_in, the s_in words and the fp16x3 range check (k_prep_h: phase 1 of the fused forward with the planes marked ready), then the dW kernel's h planes
+    FusedOut f = fused_out_base(e, c);
+    f.train = 1; f.ws = ws; f.split = 1; f.planes_ready = 1; f.h_ready = 0; f.rflag = rflag;
+    launch_fused_out_fwd(st, f, 1);
+    if (want_planes) launch_fused_prep_planes(st, c.B, lo.in, M, 1, ws, kH16Scale, nullptr, 0, 2);
+    if (with_bias)      // (on `st`, into the caller's KL slot - launch_out_bias_operand takes neither: spelled out)
+        launch_flipout_perturb(st, e->P + lo.off[NTF_P_RHO_BIAS], kl ? e->P + lo.off[NTF_P_BIAS] : nullptr, lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1], 1.0 / (double)e->Mg, kl);
 }
 
-static void head_launch(ntf_engine* e, hipStream_t st, const StepCtx& c, char* ws, bool want_planes, double* kl, bool with_bias, int* rflag, bool rows_part = true, bool skip_w0 = false) {
-    if (e->cfg.input_mode == NTF_INPUT_MULTIHOT) { head_launch_multihot(e, st, c, ws, want_planes, kl, with_bias, rflag, rows_part, skip_w0); return; }
+static void head_launch(ntf_engine* e, hipStream_t st, const StepCtx& c, char* ws, bool want_planes, double* kl, bool with_bias, int* rflag, bool skip_w0 = false) {
+    if (e->cfg.input_mode == NTF_INPUT_MULTIHOT) { head_launch_multihot(e, st, c, ws, want_planes, kl, with_bias, rflag, skip_w0); return; }
     const LayerInfo& l0 = e->layers[0]; const LayerInfo& lo = e->layers[e->L - 1];
     const int M = e->cfg.dims[e->L];
     const FusedWsPtrs wp = fused_ws_ptrs(ws, c.B, lo.in, M);
     HeadArgs a;
-    a.B = c.B; a.Bpad = rows_part ? wp.Bpad : 0; a.D = l0.in; a.mode = e->cfg.input_mode == NTF_INPUT_DENSE ? 0 : 1; a.bayes = e->cfg.bayesian;
+    a.B = c.B; a.Bpad = wp.Bpad; a.D = l0.in; a.mode = e->cfg.input_mode == NTF_INPUT_DENSE ? 0 : 1; a.bayes = e->cfg.bayesian;
     a.rows = c.rows_dev; a.s_indptr = e->s_indptr; a.s_indices = e->s_indices; a.table = e->table; a.Xall = e->Xall;
     a.mu0 = e->P + l0.off[NTF_P_WEIGHT]; a.b0 = e->P + l0.off[NTF_P_BIAS];
     a.X = e->act[0]; a.act1 = e->act[1]; a.hz = wp.hz; a.hs = wp.hs; a.sinbits = wp.sinbits;
@@ -852,11 +892,14 @@ static void head_launch(ntf_engine* e, hipStream_t st, const StepCtx& c, char* w
 // and the forward kernel RANGE BY RANGE (up to four ranges of whole dW chunks), each behind its own chunks' all-gathers: while the forward kernel works on range j, RCCL
 // moves range j + 1.  fwd_ranges: number of ranges (0: the shape / arithmetic does not allow it); range j = dW chunks [k0, k1), 64-expert tiles [t_lo, t_hi) on `ncg`
 // column groups whose dh slabs / loss partials start at cg_off.
+// the output layer's dW kernel: one workgroup per tile of fused_dw_tile() experts, 256 tiles (a round of one workgroup per CU) a chunk
+static int dw_tiles(const ntf_engine* e) { return (e->cfg.dims[e->L] + fused_dw_tile() - 1) / fused_dw_tile(); }
+static int dw_chunks(const ntf_engine* e) { return (dw_tiles(e) + 255) / 256; }
 struct FwdRange { int k0, k1, t_lo, t_hi, ncg, cg_off; };
 static int fwd_ranges(const ntf_engine* e, int B, FwdRange* out, int* ncg_tot) {
     if (!fused_ok(e) || !e->cfg.bayesian || e->layers[e->L - 1].in != 128 || !e->pl_wp || !e->pl_mu || e->L < 2) return 0;
-    if (!(e->cfg.mfma == NTF_MFMA_DEFAULT || e->cfg.mfma == NTF_MFMA_FP16X3) || !(e->fwd_kernel < 0 || e->fwd_kernel == 5) || e->ep) return 0;
-    const int M = e->cfg.dims[e->L], tile = fused_dw_tile(), total = (M + tile - 1) / tile, nchunk = (total + 255) / 256;
+    if (!fp16x3_mode(e) || !(e->fwd_kernel < 0 || e->fwd_kernel == 5) || e->ep) return 0;
+    const int M = e->cfg.dims[e->L], nchunk = dw_chunks(e);
     const int nrb = fused_ldb(B) / 128;
     const int nf = std::min({4, nchunk, nrb});
     if (nf < 2) return 0;
@@ -883,6 +926,14 @@ static int join_side(ntf_engine* e) {
     if (e->join_pending) { HIPCHK(e, hipStreamWaitEvent(e->st, e->ev_join, 0)); e->join_pending = false; }
     return NTF_OK;
 }
+// Adam's constants (torch.optim.Adam's defaults) and the bias corrections of optimiser step t, as every Adam launch of the engine takes them
+struct AdamCoef { float b1, b2, eps, bc1, bc2_sqrt; };
+static AdamCoef adam_coef(const ntf_engine*, int64_t t) {
+    const double b1 = 0.9, b2 = 0.999, tt = (double)t;      // (the corrections in double, then the cast: what the float64 oracles of the Adam tests pin down)
+    return {(float)b1, (float)b2, 1e-8f, (float)(1.0 - std::pow(b1, tt)), (float)std::sqrt(1.0 - std::pow(b2, tt))};
+}
+// the context of a step that has not started: what the generators (step) and a head issued ahead of it (rows, B) need
+static StepCtx next_ctx(const ntf_engine*, uint64_t step, int B, const int64_t* rows) { StepCtx n; n.step = step; n.B = B; n.global_B = B; n.rows_dev = rows; n.train = true; return n; }
 static int prefetch_next_head(ntf_engine* e, const StepCtx& c, hipStream_t head_st, hipEvent_t aux_after) {
     int r;
     const LayerInfo& lo = e->layers[e->L - 1];
@@ -891,16 +942,16 @@ static int prefetch_next_head(ntf_engine* e, const StepCtx& c, hipStream_t head_
     e->st = head_st;
     {   // Adam of the hidden layers: [0, first float of the output layer) - apply_adam then leaves that range alone
         Scope t(e, F_ADAM);
-        const double b1 = 0.9, b2 = 0.999, tt = (double)(e->adam_t + 1);
+        const AdamCoef k = adam_coef(e, e->adam_t + 1);
         int64_t rg[4] = {0, lo.off[NTF_P_WEIGHT], 0, 0}; int nrg = 1;
         if (e->l0_swept) {      // (the first layer's weight / rho_weight segments took their update in launch_flipout_sweep: its bias up to rho_weight, and its rho_bias, remain - L == 2 here)
             const LayerInfo& l0 = e->layers[0];
             rg[0] = l0.off[NTF_P_BIAS]; rg[1] = l0.off[NTF_P_RHO_WEIGHT]; rg[2] = l0.off[NTF_P_RHO_BIAS]; rg[3] = lo.off[NTF_P_WEIGHT]; nrg = 2;
         }
-        launch_adam_ranges(e->st, e->P, e->G, e->M1, e->V2, rg, nrg, e->lr, (float)b1, (float)b2, 1e-8f, (float)(1.0 - std::pow(b1, tt)), (float)std::sqrt(1.0 - std::pow(b2, tt)));
+        launch_adam_ranges(e->st, e->P, e->G, e->M1, e->V2, rg, nrg, e->lr, k.b1, k.b2, k.eps, k.bc1, k.bc2_sqrt);
         e->hidden_adam_done = true;
     }
-    StepCtx n; n.rows_dev = e->hp_next_rows; n.B = e->hp_next_B; n.global_B = e->hp_next_B; n.step = c.step + 1; n.train = true; n.row0 = 0;
+    StepCtx n = next_ctx(e, c.step + 1, e->hp_next_B, e->hp_next_rows);
     char* ws_next = e->fws_set[n.step & 1];
     // the sampler and the s_out words need the rows and the sign key only: on the auxiliary stream, from the fork on (beside the hidden backward; beside the HBM-bound
     // dW kernel the 30 MB of k_sign_words_T take ~90 us instead of 19 - behind the hidden backward on ONE stream the chain ended 14 us before the dW kernel)
@@ -920,15 +971,13 @@ static int prefetch_next_head(ntf_engine* e, const StepCtx& c, hipStream_t head_
     }
     HIPCHK(e, hipEventRecord(e->ev_aux, e->st4));
     e->st = head_st;
-    { Scope t(e, F_GEMM_HIDDEN); head_launch(e, e->st, n, ws_next, true, e->d_kl + 2, false, range_ptr(e) ? e->d_range + 4 : nullptr, true, e->pre0_step == n.step); }
+    { Scope t(e, F_GEMM_HIDDEN); head_launch(e, e->st, n, ws_next, true, e->d_kl + 2, false, range_ptr(e) ? e->d_range + 4 : nullptr, e->pre0_step == n.step); }
     e->hp.valid = true; e->hp.step = n.step; e->hp.rows = n.rows_dev; e->hp.B = n.B; e->hp.ub = ub_next;
     return NTF_OK;
 }
 static bool head_prefetch_possible(const ntf_engine* e, const StepCtx& c, int B) {
-    const bool can_head = (mh_head_ok(e) && !e->ep) || (e->head && e->L == 2 && e->cfg.input_mode != NTF_INPUT_MULTIHOT && head_supported(e->cfg.dims[0], e->cfg.dims[1]) &&
-                          (e->cfg.mfma == NTF_MFMA_DEFAULT || e->cfg.mfma == NTF_MFMA_FP16X3));
     if (!e->cfg.bayesian && !e->fnn_pipe) return false;
-    return e->head_prefetch && can_head && c.fuse_adam && e->cfg.fuse_adam == 1 && e->pre_valid && e->pre_step == c.step + 1 && e->hp_next_B > 0 && !c.inj &&
+    return e->head_prefetch && head_ok(e) && c.fuse_adam && e->cfg.fuse_adam == 1 && e->pre_valid && e->pre_step == c.step + 1 && e->hp_next_B > 0 && !c.inj &&
            (e->cfg.nsd != NTF_NSD_UNIGRAM_B || e->hp_next_host != nullptr) && c.global_B == B;
 }
 
@@ -944,9 +993,7 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
     bool prod_side = false, aux = false, swt_aux = false, loss_side = false, use_pre = false;
     // one kernel for gather -> hidden layer -> operand images (ntf_head.hip): one hidden layer of 128 units over a dense / mean-pooled input, native generators, fp16x3 planes
     // (round 6: the multi-hot input's head is such a unit too - head_launch_multihot - on one GPU)
-    const bool use_head = fused && c.part <= 1 && !c.inj &&
-                          ((mh_head_ok(e) && !e->ep) || (e->head && e->L == 2 && e->cfg.input_mode != NTF_INPUT_MULTIHOT && head_supported(e->cfg.dims[0], e->cfg.dims[1]) &&
-                                                         (e->cfg.mfma == NTF_MFMA_DEFAULT || e->cfg.mfma == NTF_MFMA_FP16X3)));
+    const bool use_head = fused && c.part <= 1 && !c.inj && head_ok(e);
     // the hidden layers' backward (and the loss reduction) of a whole train step run on the side stream beside the output layer's dW kernel, see `backward:`
     // (round 5: also of a deferred-dW step - a data-parallel rank's - whose dW chunks the host launches right behind this call: the join then waits behind the last chunk, join_side)
     // (Fnn: the chain alone is too short to pay - it goes to the side stream when the next batch's head follows it there, round 6)
@@ -954,10 +1001,15 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
                           e->hp_next_B > 0 && (e->cfg.nsd != NTF_NSD_UNIGRAM_B || e->hp_next_host != nullptr) && range_ptr(e) && e->pl_mu && lo.in == 128;
     const bool side = fused && (e->cfg.bayesian || fnn_side) && e->L > 1 && c.train && c.part == 0 && (!c.defer_dw || e->dp_side_bwd) && e->side_bwd && !(c.fuse_adam && e->cfg.fuse_adam == 2);
     bool hp_hit = false, hp_stale = false;
-    bool chain_ok = false, chain_lean = false, chain_fill = false, chain_nof32 = false; PerturbChain pch;
+    bool chain_ok = false, chain_lean = false, chain_fill = false, chain_nof32 = false; PerturbChain pch; WpOpts whole;
     FwdRange fr[4]; int fr_tot = 0;
     const int nfr = (c.chunk_cb && c.defer_dw && c.train && c.part == 0 && !c.inj && e->dp_ranges) ? fwd_ranges(e, B, fr, &fr_tot) : 0;      // > 0: producer + forward kernel range by range
     if (fused) e->fws = e->fws_set[c.step & 1];     // (every kernel of a step works in ONE of the two workspace sets: a prefetched head of step t + 1 fills the other beside step t's dW kernel)
+    const auto loss_finalize = [&]() {      // the step's loss from its partials, the fix-ups and the KL sum (on e->st: the main stream, or the side stream of a whole train step)
+        Scope t(e, F_LOSS);
+        launch_loss_finalize(e->st, e->partial, nslots, e->row_fix, B, inv_B, e->cfg.bayesian ? e->d_kl : nullptr, ((double)B / (double)c.global_B) / (double)c.global_B /*the KL term's scale*/, e->d_loss,
+                             accumulate_epoch ? e->d_acc : nullptr, e->d_acc_steps);
+    };
     if (c.part >= 2) goto backward;   // expert-sharded step, later phases
     // the Flipout operand producers add each layer's KL to d_kl[0]; the 4 bytes behind it are this step's fp16x3 range flag
     {
@@ -991,6 +1043,7 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
     if (e->cfg.bayesian || (range_ptr(e) && e->fnn_pipe)) { if (!(use_pre && e->pre_rotated)) launch_step_scalars(e->st, e->d_kl, use_pre ? 1 : 0, chain_lean ? e->d_chain : nullptr); }
     else if (range_ptr(e)) HIPCHK(e, hipMemsetAsync(e->d_range, 0, 4, e->st));
     e->pre_rotated = false;
+    whole.f32 = !chain_nof32; whole.chain = pch;      // the whole layer's weight operand with its planes and KL term, as this step's producer launch makes it (side or main stream)
     if (fused && e->side_bwd && !hp_hit) {
         // Three streams through the step's head (round 3; profiles/r3_step_timeline.md).  What precedes the forward kernel is a chain of small latency-bound
         // launches and one HBM-bound pass, and most links of it do not depend on each other:
@@ -1003,17 +1056,13 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
         if (e->cfg.bayesian && !use_pre && !nfr) {
             HIPCHK(e, hipStreamWaitEvent(e->st3, e->ev_fork, 0));
             e->st = e->st3;
-            { Scope t(e, F_FLIPOUT_OPERAND);
-              launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT], chain_lean ? nullptr : e->P + lo.off[NTF_P_WEIGHT], lo.nw(), normal_spec(e, c, e->L - 1, T_EPS_W), chain_nof32 ? nullptr : e->Wp[e->L - 1],
-                                     1.0 / out_nw, e->d_kl, e->pl_wp, (e->pl_wp && !chain_lean) ? e->pl_mu : nullptr, e->P + lo.off[NTF_P_WEIGHT], lo.in, kW16Scale, range_ptr(e), nullptr, pch); }
+            { Scope t(e, F_FLIPOUT_OPERAND); launch_out_weight_operand(e, c, whole); }
             HIPCHK(e, hipEventRecord(e->ev_join, e->st3));
             prod_side = true;
         }
         HIPCHK(e, hipStreamWaitEvent(e->st4, e->ev_fork, 0));
         e->st = e->st4;
-        if (e->cfg.bayesian && !use_head) { Scope t(e, F_FLIPOUT_OPERAND);
-            launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS], e->P + lo.off[NTF_P_BIAS], lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1],
-                                   1.0 / out_nb, e->d_kl); }
+        if (e->cfg.bayesian && !use_head) { Scope t(e, F_FLIPOUT_OPERAND); launch_out_bias_operand(e, c, true); }
         if ((r = sample_negatives(e, c))) return r;
         if (c.train && e->cfg.bayesian && e->cfg.mfma != NTF_MFMA_F32 && lo.in == 128 && e->pl_mu != nullptr) {
             const SignSpec so = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out), si = sign_spec(e, c, e->L - 1, T_S_IN, lo.in);
@@ -1035,28 +1084,20 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
         const bool skip_w0 = e->use_pre0;      // (the multi-hot head below takes the same decision forward_layers does)
         if (!use_head && (r = forward_layers(e, c, false, true))) { e->use_pre0 = false; return r; }
         e->use_pre0 = false;
-        FusedOut f;
-        f.B = B; f.H = lo.in; f.M = M; f.bayes = e->cfg.bayesian; f.train = c.train;
-        f.h = e->act[e->L - 1];
+        FusedOut f = fused_out_base(e, c); f.train = c.train;
         f.mu = e->P + lo.off[NTF_P_WEIGHT]; f.mu_b = e->P + lo.off[NTF_P_BIAS];
         f.tnw = e->cfg.tnw; f.tpw = e->cfg.tpw; f.inv_B = inv_B;
         f.dzT = e->dZout; f.dh_slab = e->dh_slab; f.ws = e->fws;
         f.dh = e->L > 1 ? e->dAct[(e->L - 1) & 1] : nullptr;
         f.h_mask = e->L > 1 ? e->act[e->L - 1] : nullptr;
         if (e->cfg.bayesian) {
-            if (!prod_side && !use_pre && !nfr) { Scope t(e, F_FLIPOUT_OPERAND);
-              launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT], chain_lean ? nullptr : f.mu, lo.nw(), normal_spec(e, c, e->L - 1, T_EPS_W), chain_nof32 ? nullptr : e->Wp[e->L - 1],
-                                     1.0 / out_nw, e->d_kl, e->pl_wp, (e->pl_wp && !chain_lean) ? e->pl_mu : nullptr, f.mu, lo.in, kW16Scale, range_ptr(e), nullptr, pch); }   // + the split planes of Wp and mu
-            if (!aux && !use_head) { Scope t(e, F_FLIPOUT_OPERAND);
-              launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS], f.mu_b, lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1],
-                                     1.0 / out_nb, e->d_kl); }
+            if (!prod_side && !use_pre && !nfr) { Scope t(e, F_FLIPOUT_OPERAND); launch_out_weight_operand(e, c, whole); }   // + the split planes of Wp and mu
+            if (!aux && !use_head) { Scope t(e, F_FLIPOUT_OPERAND); launch_out_bias_operand(e, c, true); }
             f.planes_ready = e->pl_wp != nullptr;
             f.wp = e->Wp[e->L - 1]; f.bp = e->bp[e->L - 1];
-            f.s_in = sign_spec(e, c, e->L - 1, T_S_IN, lo.in); f.s_out = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out);
         }
         if (!e->cfg.bayesian && use_pre) f.planes_ready = 1;      // (Fnn, round 6: the previous step's dW epilogue wrote the planes of the updated mu)
-        f.split = e->pl_mu != nullptr; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp;
-        f.w_scale = kW16Scale; f.h_scale = kH16Scale; f.dz_scale = dz_scale16(e, c.global_B);
+        f.split = e->pl_mu != nullptr; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp; f.dz_scale = dz_scale16(e, c.global_B);
         f.rflag = range_ptr(e);
         if (e->fwd_kernel >= 0) f.wide = e->fwd_kernel;   // A/B runs: NTF_FWD_KERNEL = 0, 1, 2 (ntf_fused.h), read when the engine is created
         f.eval_kernel = e->eval_kernel;
@@ -1065,7 +1106,7 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
         if (use_head) {
             Scope t(e, F_GEMM_HIDDEN);
             // (hp_hit: this batch's head ran beside the previous step's dW kernel; hp_stale: a head ran for another batch - redo it here, without the KL terms and the bias operand)
-            if (!hp_hit) head_launch(e, e->st, c, e->fws, c.train && e->cfg.mfma != NTF_MFMA_F32, hp_stale ? nullptr : e->d_kl, !hp_stale, f.rflag, true, skip_w0);
+            if (!hp_hit) head_launch(e, e->st, c, e->fws, c.train && e->cfg.mfma != NTF_MFMA_F32, hp_stale ? nullptr : e->d_kl, !hp_stale, f.rflag, skip_w0);
             f.h_ready = 1;
             if (!f.planes_ready) launch_fused_out_fwd(e->st, f, 1);   // (Fnn: the split planes of mu are made per step)
             if (c.train && e->cfg.mfma != NTF_MFMA_F32 && split_products(e) && !swt_aux && !hp_hit) {   // (one stream: the s_out words were not made beside the head)
@@ -1090,8 +1131,7 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
             // this step's operands came from the previous step's dW epilogue, which (lean) left no f32 copy of sigma * eps: only a step that falls back to the exact-f32 kernels
             // reads one, and makes it here - a capped grid that exits at once unless the range flag is raised (behind the head: k_head may still raise it)
             Scope t(e, F_FLIPOUT_OPERAND);
-            launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT], nullptr, lo.nw(), normal_spec(e, c, e->L - 1, T_EPS_W), e->Wp[e->L - 1], 0.0, nullptr,
-                                   nullptr, nullptr, nullptr, 0, 1.f, nullptr, range_ptr(e));
+            WpOpts copy; copy.only_if = range_ptr(e); launch_out_weight_operand(e, c, copy);
         }
         if (nfr) {
             // range by range: the caller's callback orders this stream behind the all-gathers of the range's parameter chunks; then its operands (eps, sigma eps, the
@@ -1099,12 +1139,8 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
             f.planes_ready = 1; f.split_fallback = 1; f.chunk_ncg_tot = fr_tot;
             for (int j = 0; j < nfr; ++j) {
                 if (c.chunk_cb(j, c.chunk_user) != 0) FAIL(e, NTF_ESTATE, "step_staged_deferred_cb: the chunk callback reported a failure");
-                const int64_t r0 = (int64_t)fr[j].t_lo * 64, r1 = std::min<int64_t>((int64_t)fr[j].t_hi * 64, M), o0 = r0 * lo.in, n0 = (r1 - r0) * lo.in;
-                { Scope t(e, F_FLIPOUT_OPERAND);
-                  NormalSpec es = normal_spec(e, c, e->L - 1, T_EPS_W); es.qbase += o0 / 4;
-                  const int64_t pl0 = r0 / 32 * 64 * lo.in;      // the planes of 32-expert tile r0 / 32 (fused_planes_elems layout)
-                  launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT] + o0, f.mu + o0, n0, es, e->Wp[e->L - 1] + o0, 1.0 / out_nw, e->d_kl,
-                                         e->pl_wp + pl0, e->pl_mu + pl0, f.mu + o0, lo.in, kW16Scale, range_ptr(e)); }
+                WpOpts part; part.x0 = (int64_t)fr[j].t_lo * 64; part.nx = std::min<int64_t>((int64_t)fr[j].t_hi * 64, M) - part.x0;
+                { Scope t(e, F_FLIPOUT_OPERAND); launch_out_weight_operand(e, c, part); }
                 f.chunk_t_lo = fr[j].t_lo; f.chunk_t_hi = fr[j].t_hi; f.chunk_cg_off = fr[j].cg_off; f.chunk_ncg = fr[j].ncg;
                 { Scope t(e, F_OUT_FUSED_FWD); launch_fused_out_fwd(e->st, f, 2); }
             }
@@ -1123,12 +1159,7 @@ static int run_step(ntf_engine* e, const StepCtx& c, bool accumulate_epoch) {
                             c.train ? e->dZout : nullptr, e->row_fix);
     }
     loss_side = side;   // a whole train step: the loss reduction is not on the way to the dW kernel - it goes first on the side stream, beside it
-    if (!loss_side) {
-        Scope t(e, F_LOSS);
-        const double kl_scale = ((double)B / (double)c.global_B) / (double)c.global_B;
-        launch_loss_finalize(e->st, e->partial, nslots, e->row_fix, B, inv_B, e->cfg.bayesian ? e->d_kl : nullptr, kl_scale, e->d_loss,
-                             accumulate_epoch ? e->d_acc : nullptr, e->d_acc_steps);
-    }
+    if (!loss_side) loss_finalize();
     if (!c.train || c.part == 1) return NTF_OK;
 
 backward:
@@ -1142,10 +1173,7 @@ backward:
         HIPCHK(e, hipStreamWaitEvent(e->st3, e->ev_fork, 0));
         if (loss_side) {
             e->st = e->st3;
-            { Scope t(e, F_LOSS);
-              const double kl_scale = ((double)B / (double)c.global_B) / (double)c.global_B;
-              launch_loss_finalize(e->st, e->partial, nslots, e->row_fix, B, inv_B, e->cfg.bayesian ? e->d_kl : nullptr, kl_scale, e->d_loss,
-                                   accumulate_epoch ? e->d_acc : nullptr, e->d_acc_steps); }
+            loss_finalize();
             e->st = restore.main;
         }
     }
@@ -1175,7 +1203,7 @@ backward:
             if (f.dz_packed && !c.defer_dw && !(c.fuse_adam && e->cfg.fuse_adam == 2)) {
                 // few expert tiles (a narrow expert shard under a wide minibatch, or a small model) leave most CUs idle at one workgroup per 256 experts:
                 // split every tile's K (batch) range over several workgroups.  Scratch: the dense-logits buffer of the generic path, idle in a fused step.
-                const int tiles = (M + fused_dw_tile() - 1) / fused_dw_tile(), nib = fused_ldb(B) / 32;
+                const int tiles = dw_tiles(e), nib = fused_ldb(B) / 32;
                 int ks = e->dw_ksplit > 0 ? e->dw_ksplit : (tiles <= 128 ? std::min({256 / tiles, 8, std::max(1, nib / 4)}) : 1);
                 while (ks > 1 && fused_dw_part_floats(M, li.in, ks) > (int64_t)e->cfg.max_batch * M) --ks;
                 if (ks > 1) { f.ksplit = ks; f.part = e->Zout; }
@@ -1183,17 +1211,15 @@ backward:
             // (launch_fused_prep_planes - the h planes and the transposed s_out words this kernel reads - ran in the step's head)
             if (e->cfg.bayesian) { f.rho = e->P + li.off[NTF_P_RHO_WEIGHT]; f.wp = e->Wp[l]; f.klw = kl_share / ((float)out_nw * (float)c.global_B); f.cur_eps = normal_spec(e, c, l, T_EPS_W); }
             if (c.defer_dw) {
-                const int tile = fused_dw_tile(), total = (M + tile - 1) / tile;
-                e->pend = f; e->pend_valid = true; e->pend_chunks = (total + 255) / 256;
+                e->pend = f; e->pend_valid = true; e->pend_chunks = dw_chunks(e);
                 if (e->cfg.bayesian) { e->pend_eps_b = normal_spec(e, c, l, T_EPS_B); e->pend_klw_b = kl_share / ((float)out_nb * (float)c.global_B); }
                 continue;  // its bias-gradient finalisation follows the last chunk
             }
             if (c.fuse_adam && e->cfg.fuse_adam == 2) {
                 // chunked: dW of expert chunk k on the main stream, Adam of chunk k on the side stream while dW of chunk k+1 runs
                 if (!e->st2) { HIPCHK(e, hipStreamCreateWithFlags(&e->st2, hipStreamNonBlocking)); HIPCHK(e, hipEventCreateWithFlags(&e->ev_chunk, hipEventDisableTiming)); HIPCHK(e, hipEventCreateWithFlags(&e->ev_side, hipEventDisableTiming)); }
-                const double b1 = 0.9, b2 = 0.999, tt = (double)(e->adam_t + 1);
-                const float bc1 = (float)(1.0 - std::pow(b1, tt)), bc2s = (float)std::sqrt(1.0 - std::pow(b2, tt));
-                const int tile = fused_dw_tile(), total = (M + tile - 1) / tile, chunk = 256;   // one workgroup per CU per round
+                const AdamCoef k = adam_coef(e, e->adam_t + 1);
+                const int tile = fused_dw_tile(), total = dw_tiles(e), chunk = 256;   // one workgroup per CU per round
                 Scope t(e, F_OUT_FUSED_DW);
                 for (int w0 = 0; w0 < total; w0 += chunk) {
                     f.wg_begin = w0; f.wg_count = chunk;
@@ -1204,7 +1230,7 @@ backward:
                     for (int kind : {NTF_P_WEIGHT, NTF_P_RHO_WEIGHT}) {
                         if (kind == NTF_P_RHO_WEIGHT && !e->cfg.bayesian) continue;
                         const int64_t o = li.off[kind] + lo;
-                        launch_adam(e->st2, e->P + o, e->G + o, e->M1 + o, e->V2 + o, hi - lo, e->lr, (float)b1, (float)b2, 1e-8f, bc1, bc2s);
+                        launch_adam(e->st2, e->P + o, e->G + o, e->M1 + o, e->V2 + o, hi - lo, e->lr, k.b1, k.b2, k.eps, k.bc1, k.bc2_sqrt);
                     }
                 }
                 HIPCHK(e, hipEventRecord(e->ev_side, e->st2));
@@ -1213,17 +1239,14 @@ backward:
                 goto dw_done;
             }
             if (c.fuse_adam) {
-                const double b1 = 0.9, b2 = 0.999;
-                const double tt = (double)(e->adam_t + 1);
-                const double bc1 = 1.0 - std::pow(b1, tt), bc2 = 1.0 - std::pow(b2, tt);
-                f.adam = 1; f.lr_over_bc1 = e->lr / (float)bc1; f.b1 = (float)b1; f.b2 = (float)b2; f.eps = 1e-8f; f.bc2_sqrt = (float)std::sqrt(bc2);
+                const AdamCoef k = adam_coef(e, e->adam_t + 1);
+                f.adam = 1; f.lr_over_bc1 = e->lr / k.bc1; f.b1 = k.b1; f.b2 = k.b2; f.eps = k.eps; f.bc2_sqrt = k.bc2_sqrt;
                 f.w_mu = e->P + li.off[NTF_P_WEIGHT]; f.m_mu = e->M1 + li.off[NTF_P_WEIGHT]; f.v_mu = e->V2 + li.off[NTF_P_WEIGHT];
                 if (e->cfg.bayesian) { f.w_rho = e->P + li.off[NTF_P_RHO_WEIGHT]; f.m_rho = e->M1 + li.off[NTF_P_RHO_WEIGHT]; f.v_rho = e->V2 + li.off[NTF_P_RHO_WEIGHT]; }
                 e->adam_in_dw = true;
                 if (e->prefetch && e->cfg.bayesian && f.dz_packed && e->pl_wp && e->pl_mu && range_ptr(e)) {
                     // the Adam epilogue holds the updated mu / rho: it is also the operand producer of step + 1 (FusedDw.produce)
-                    StepCtx nx; nx.step = c.step + 1;
-                    f.produce = 1; f.lean = e->lean; f.nx_eps = normal_spec(e, nx, l, T_EPS_W); f.nx_wp = e->Wp[l]; f.nx_pl_wp = e->pl_wp; f.nx_pl_mu = e->pl_mu; f.nx_pscale = kW16Scale;
+                    f.produce = 1; f.lean = e->lean; f.nx_eps = normal_spec(e, next_ctx(e, c.step + 1, 0, nullptr), l, T_EPS_W); f.nx_wp = e->Wp[l]; f.nx_pl_wp = e->pl_wp; f.nx_pl_mu = e->pl_mu; f.nx_pscale = kW16Scale;
                     f.nx_klw = 1.0 / out_nw; f.nx_kl = e->d_kl + 2; f.nx_rflag = e->d_range + 4;
                     e->pre_valid = true; e->pre_step = c.step + 1;
                 }
@@ -1295,11 +1318,10 @@ backward:
                 a.mu = e->P + li.off[NTF_P_WEIGHT]; a.rho = e->P + li.off[NTF_P_RHO_WEIGHT]; a.g_mu = gW; a.g_rho = gRW;
                 a.m_mu = e->M1 + li.off[NTF_P_WEIGHT]; a.v_mu = e->V2 + li.off[NTF_P_WEIGHT]; a.m_rho = e->M1 + li.off[NTF_P_RHO_WEIGHT]; a.v_rho = e->V2 + li.off[NTF_P_RHO_WEIGHT];
                 a.n = li.nw(); a.eps = normal_spec(e, c, l, T_EPS_W); a.klw = kl_share / ((float)li.nw() * (float)c.global_B);
-                const double b1 = 0.9, b2 = 0.999, tt = (double)(e->adam_t + 1);
-                a.lr = e->lr; a.b1 = (float)b1; a.b2 = (float)b2; a.adam_eps = 1e-8f; a.bc1 = (float)(1.0 - std::pow(b1, tt)); a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, tt));
-                StepCtx nx; nx.step = c.step + 1;
+                const AdamCoef k = adam_coef(e, e->adam_t + 1);
+                a.lr = e->lr; a.b1 = k.b1; a.b2 = k.b2; a.adam_eps = k.eps; a.bc1 = k.bc1; a.bc2_sqrt = k.bc2_sqrt;
                 const bool produce = e->pre_valid && e->pre_step == c.step + 1;      // (the dW epilogue produced the output layer's operands for that step: same protocol, same slot)
-                a.nx_eps = normal_spec(e, nx, l, T_EPS_W); a.nx_wp = e->Wp[l]; a.nx_klw = 1.0 / (double)li.nw(); a.nx_kl = produce ? e->d_kl + 2 : nullptr;
+                a.nx_eps = normal_spec(e, next_ctx(e, c.step + 1, 0, nullptr), l, T_EPS_W); a.nx_wp = e->Wp[l]; a.nx_klw = 1.0 / (double)li.nw(); a.nx_kl = produce ? e->d_kl + 2 : nullptr;
                 a.touched = e->l0_touched; a.H = li.out;
                 launch_flipout_sweep(e->st, a);
                 e->l0_swept = true; e->g0_clean = true;
@@ -1349,9 +1371,8 @@ backward:
 static int apply_adam(ntf_engine* e) {
     Scope t(e, F_ADAM);
     e->adam_t += 1;
-    const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - std::pow(b1, (double)e->adam_t), bc2 = 1.0 - std::pow(b2, (double)e->adam_t);
-    if (!e->adam_in_dw) { e->pre_valid = false; launch_adam(e->st, e->P, e->G, e->M1, e->V2, e->n_params, e->lr, (float)b1, (float)b2, 1e-8f, (float)bc1, (float)std::sqrt(bc2)); return NTF_OK; }
+    const AdamCoef k = adam_coef(e, e->adam_t);
+    if (!e->adam_in_dw) { e->pre_valid = false; launch_adam(e->st, e->P, e->G, e->M1, e->V2, e->n_params, e->lr, k.b1, k.b2, k.eps, k.bc1, k.bc2_sqrt); return NTF_OK; }
     // the output layer's weight (and rho_weight) segments were updated inside the dW kernel: one launch over the rest
     e->adam_in_dw = false;
     const LayerInfo& lo = e->layers[e->L - 1];
@@ -1367,35 +1388,28 @@ static int apply_adam(ntf_engine* e) {
     } else
     if (!e->hidden_adam_done) { rg[2 * n] = 0; rg[2 * n + 1] = w0; ++n; }      // (head prefetch: the hidden layers' Adam ran on the side stream, in front of the next batch's head)
     e->hidden_adam_done = false; e->l0_swept = false;
-    if (e->cfg.bayesian) { const int64_t r0 = lo.off[NTF_P_RHO_WEIGHT], r1 = lo.off[NTF_P_RHO_BIAS];
+    if (e->cfg.bayesian) { const int64_t r1 = lo.off[NTF_P_RHO_BIAS];
         // the live lo.out floats of the two bias segments, not their 256-byte padding: a finalised range would push the KL gradient into the padding of rho_bias
         // (p = 0, g = 0 there) and read an injected eps_b past its lo.out floats
-        (void)r0;
         rg[2 * n] = w1; rg[2 * n + 1] = w1 + lo.out; fin[n] = e->fin_pend ? 1 : 0; ++n; rg[2 * n] = r1; rg[2 * n + 1] = r1 + lo.out; fin[n] = e->fin_pend ? 2 : 0; ++n; }
     else { rg[2 * n] = w1; rg[2 * n + 1] = w1 + lo.out; ++n; }
     const bool rotate = (e->cfg.bayesian || e->fnn_pipe) && e->pre_valid && e->pre_step == e->step;   // this step's dW epilogue left the next step's KL / range flag behind the current ones
     // the prefetched head of the next step left out what depends on the output layer's biases, which this launch updates: their Flipout operand sigma_b eps_b and KL of
-    // the next step.  Round 5: produced by this very launch from the updated values it holds (round 4: k_head's bias workgroups alone in a launch behind it)
-    const bool bias_nx = e->cfg.bayesian && e->hp.valid && rotate && e->hp.step == e->step && e->merge_bias;
-    NormalSpec nx_eps;
-    if (bias_nx) { StepCtx nx; nx.step = e->hp.step; nx.B = e->hp.B; nx.global_B = e->hp.B; nx_eps = normal_spec(e, nx, e->L - 1, T_EPS_B); }
+    // the next step.  Produced by this very launch from the updated values it holds
+    const bool bias_nx = e->cfg.bayesian && e->hp.valid && rotate && e->hp.step == e->step;
+    const StepCtx nx = next_ctx(e, e->hp.step, e->hp.B, e->hp.rows);
+    const NormalSpec nx_eps = normal_spec(e, nx, e->L - 1, T_EPS_B);
     // ... and, as extra workgroups of the same launch, the f32 copy of the next step's sigma * eps that only a step falling back to the exact-f32 kernels reads (lean: the dW
     // epilogue wrote none) - round 4 issued it as a launch of its own in front of every step, a no-op in all but the rarest.  *only_if: the NEXT step's range flag, still in
     // its slot behind the current one (this launch's last workgroup rotates it) and complete: the dW epilogue and the prefetched head are behind this launch
     F32CopyJob f32c; const bool with_copy = bias_nx && e->lean && e->f32_copy_merged && range_ptr(e) != nullptr;
     if (with_copy) {
-        StepCtx nx; nx.step = e->hp.step; nx.B = e->hp.B; nx.global_B = e->hp.B;
         f32c.rho = e->P + lo.off[NTF_P_RHO_WEIGHT]; f32c.out = e->Wp[e->L - 1]; f32c.n = lo.nw(); f32c.eps = normal_spec(e, nx, e->L - 1, T_EPS_W); f32c.only_if = e->d_range + 4;
         e->f32_copy_step = e->hp.step + 1;      // (+ 1: 0 = never)
     }
-    launch_adam_ranges(e->st, e->P, e->G, e->M1, e->V2, rg, n, e->lr, (float)b1, (float)b2, 1e-8f, (float)bc1, (float)std::sqrt(bc2), fin, &e->fin_eps, e->fin_klw,
+    launch_adam_ranges(e->st, e->P, e->G, e->M1, e->V2, rg, n, e->lr, k.b1, k.b2, k.eps, k.bc1, k.bc2_sqrt, fin, &e->fin_eps, e->fin_klw,
                        rotate ? e->d_kl : nullptr, bias_nx ? e->bp[e->L - 1] : nullptr, bias_nx ? &nx_eps : nullptr, 1.0 / (double)e->Mg, with_copy ? &f32c : nullptr);
     e->pre_rotated = rotate; e->fin_pend = false;
-    if (e->cfg.bayesian && e->hp.valid && rotate && e->hp.step == e->step && !bias_nx) {
-        StepCtx nx; nx.step = e->hp.step; nx.B = e->hp.B; nx.global_B = e->hp.B; nx.rows_dev = e->hp.rows; nx.train = true;
-        Scope t2(e, F_FLIPOUT_OPERAND);
-        head_launch(e, e->st, nx, e->fws_set[nx.step & 1], false, e->d_kl, true, nullptr, false);
-    }
     return NTF_OK;
 }
 
@@ -1406,70 +1420,86 @@ static int apply_adam_ranges(ntf_engine* e, const int64_t* lo_hi, int n) {
     Scope t(e, F_ADAM);
     e->adam_t += 1;
     e->adam_in_dw = false; e->pre_valid = false;
-    const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - std::pow(b1, (double)e->adam_t), bc2 = 1.0 - std::pow(b2, (double)e->adam_t);
     for (int k = 0; k < n; ++k) {
         const int64_t lo = lo_hi[2 * k], hi = lo_hi[2 * k + 1];
         if (lo < 0 || hi > e->n_params || lo > hi || (lo & 3)) FAIL(e, NTF_EINVAL, "apply_ranges: a range outside the flat buffers, reversed, or not 16-byte aligned");
     }
-    launch_adam_ranges(e->st, e->P, e->G, e->M1, e->V2, lo_hi, n, e->lr, (float)b1, (float)b2, 1e-8f, (float)bc1, (float)std::sqrt(bc2));
+    const AdamCoef k = adam_coef(e, e->adam_t);
+    launch_adam_ranges(e->st, e->P, e->G, e->M1, e->V2, lo_hi, n, e->lr, k.b1, k.b2, k.eps, k.bc1, k.bc2_sqrt);
     return NTF_OK;
 }
 
-static int read_loss(ntf_engine* e, float* loss_out) {
-    if (!loss_out) return NTF_OK;
-    HIPCHK(e, hipMemcpyAsync(loss_out, e->d_loss, 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
+static int read_loss(ntf_engine* e, float* loss_out) { return loss_out ? d2h_sync(e, loss_out, e->d_loss, 4) : NTF_OK; }
+static int launch_check(ntf_engine* e) {      // an entry point's last word: a launch that failed somewhere in the call
+    if (const hipError_t s = hipGetLastError()) FAIL(e, NTF_EHIP, std::string("kernel launch: ") + hipGetErrorString(s));
     return NTF_OK;
 }
+// nsd = unigram_b: the alias table of step c's batch - the one the previous step's head prefetch staged for THIS batch beside its dW kernel (same_batch: the table is a
+// function of the batch's rows alone), else made from the n host row ids through the other slot
+static int pick_batch_unigram(ntf_engine* e, StepCtx& c, const int64_t* host_rows, int n, bool same_batch) {
+    if (same_batch && e->hp.valid && e->hp.ub >= 0 && e->hp.step == c.step && e->hp.rows == c.rows_dev && e->hp.B == c.B) c.ub = e->hp.ub;
+    else { c.ub = (e->ub_slot ^= 1); if (int r = set_batch_unigram(e, host_rows, n, c.ub, e->st)) return r; }
+    e->ub_slot = c.ub; return NTF_OK;
+}
 
-static int step_common(ntf_engine* e, const int64_t* rows, int32_t B, int32_t global_B, const ntf_inject* inj, float* loss_out, bool train,
-                       bool apply, bool rows_on_device, const int64_t* global_rows_host, int n_global, bool defer_dw = false, uint32_t row0 = 0) {
+struct StepReq {      // what one call of a step entry point asks of step_common
+    const int64_t* rows = nullptr; int32_t B = 0, global_B = 0;      // this shard's rows (host ids, or on the device: rows_on_device) of a minibatch of global_B
+    const ntf_inject* inj = nullptr; float* loss_out = nullptr; bool train = false, apply = false, rows_on_device = false, defer_dw = false;
+    const int64_t* global_rows_host = nullptr; int n_global = 0; uint32_t row0 = 0;      // the whole minibatch's row ids on the host (unigram_b); StepCtx.row0
+};
+static int step_common(ntf_engine* e, const StepReq& q) {
     if (!e) return NTF_EINVAL;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int r;
+    const int32_t B = q.B, global_B = q.global_B;
     if ((r = check_ready(e, true))) return r;
     if (global_B < B) FAIL(e, NTF_EINVAL, "global_B < B");
-    if (train && e->ep && e->ep_world > 1)
+    if (q.train && e->ep && e->ep_world > 1)
         FAIL(e, NTF_ESTATE, "expert-sharded engine: a train step needs the sum of d(hidden) over the shards - use ntf_step_staged_ep");
     if (e->ep && global_B != B) FAIL(e, NTF_EINVAL, "expert-sharded engine: every shard steps the whole minibatch (global_B == B)");
     if (e->ep_open == 2 && e->ep_side) HIPCHK(e, hipStreamWaitEvent(e->st, e->ev_join, 0));
     e->ep_open = 0;
     if ((r = join_side(e))) return r;       // (an abandoned deferred step's side-stream chain still orders before this one)
-    StepCtx c; c.B = B; c.global_B = global_B; c.inj = inj; c.train = train; c.step = e->step++;
-    c.fuse_adam = train && apply && e->cfg.fuse_adam && global_B == B && fused_ok(e);
-    c.chain = !train && e->eval_chain != 0 && !inj;
-    c.defer_dw = defer_dw && train && !apply && fused_ok(e);
-    c.row0 = row0;
+    StepCtx c; c.B = B; c.global_B = global_B; c.inj = q.inj; c.train = q.train; c.step = e->step++;
+    c.fuse_adam = q.train && q.apply && e->cfg.fuse_adam && global_B == B && fused_ok(e);
+    c.chain = !q.train && e->eval_chain != 0 && !q.inj;
+    c.defer_dw = q.defer_dw && q.train && !q.apply && fused_ok(e);
+    c.row0 = q.row0;
     if (c.defer_dw) { c.chunk_cb = e->cb_fn; c.chunk_user = e->cb_user; }
     e->pend_valid = false;
-    if ((r = stage_rows(e, rows, B, rows_on_device, &c.rows_dev))) return r;
+    if ((r = stage_rows(e, q.rows, B, q.rows_on_device, &c.rows_dev))) return r;
     if ((r = stage_all_inj(e, c))) return r;
-    if (e->cfg.nsd == NTF_NSD_UNIGRAM_B && e->cfg.ns > 0 && !(inj && inj->neg_idx)) {
-        if (!global_rows_host) FAIL(e, NTF_EINVAL, "unigram_b needs the batch rows on the host");
-        // the previous step's head prefetch may have staged THIS batch's table already (beside its dW kernel): the table is a function of the batch's rows alone
-        if (e->hp.valid && e->hp.ub >= 0 && e->hp.step == c.step && e->hp.rows == c.rows_dev && e->hp.B == B && global_B == B) c.ub = e->hp.ub;
-        else { c.ub = (e->ub_slot ^= 1); if ((r = set_batch_unigram(e, global_rows_host, n_global, c.ub, e->st))) return r; }
-        e->ub_slot = c.ub;
+    if (e->cfg.nsd == NTF_NSD_UNIGRAM_B && e->cfg.ns > 0 && !(q.inj && q.inj->neg_idx)) {
+        if (!q.global_rows_host) FAIL(e, NTF_EINVAL, "unigram_b needs the batch rows on the host");
+        if ((r = pick_batch_unigram(e, c, q.global_rows_host, q.n_global, global_B == B))) return r;
     }
     if ((r = run_step(e, c, true))) return r;
     e->last_B = B; e->last_global_B = global_B; e->neg_step = c.step;
-    if (train && apply && (r = apply_adam(e))) return r;
-    if (loss_out && (r = join_side(e))) return r;      // (the loss reduction of a deferred step runs on the side stream)
-    if ((r = read_loss(e, loss_out))) return r;
-    hipError_t s = hipGetLastError();
-    if (s != hipSuccess) FAIL(e, NTF_EHIP, std::string("kernel launch: ") + hipGetErrorString(s));
-    return NTF_OK;
+    if (q.train && q.apply && (r = apply_adam(e))) return r;
+    if (q.loss_out && (r = join_side(e))) return r;      // (the loss reduction of a deferred step runs on the side stream)
+    if ((r = read_loss(e, q.loss_out))) return r;
+    return launch_check(e);
+}
+// an evaluation step on host row ids (the caller's own minibatch, of which they are all unless global_B says otherwise: ntf_backward)
+static StepReq host_step(const int64_t* rows, int32_t B, int32_t global_B, const ntf_inject* inj, float* loss_out) {
+    StepReq q; q.rows = rows; q.B = B; q.global_B = global_B; q.inj = inj; q.loss_out = loss_out; q.global_rows_host = rows; q.n_global = B; return q;
+}
+// ... and a step on rows [offset, offset + B) of the staged order, a shard of the minibatch [global_offset, global_offset + global_B)
+static StepReq staged_step(ntf_engine* e, int64_t offset, int32_t B, int64_t global_offset, int32_t global_B, float* loss_out) {
+    StepReq q; q.rows = e->d_order + offset; q.B = B; q.global_B = global_B; q.loss_out = loss_out; q.rows_on_device = true;
+    q.global_rows_host = e->h_order.data() + global_offset; q.n_global = global_B; q.row0 = (uint32_t)(offset - global_offset); return q;
 }
 
 extern "C" int ntf_train_step(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, float* loss_out) {
-    return step_common(e, rows, B, B, inj, loss_out, true, true, false, rows, B);
+    StepReq q = host_step(rows, B, B, inj, loss_out); q.train = q.apply = true;
+    return step_common(e, q);
 }
 extern "C" int ntf_eval_step(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, float* loss_out) {
-    return step_common(e, rows, B, B, inj, loss_out, false, false, false, rows, B);
+    return step_common(e, host_step(rows, B, B, inj, loss_out));
 }
 extern "C" int ntf_backward(ntf_engine* e, const int64_t* rows, int32_t B, int32_t global_B, const ntf_inject* inj, float* loss_out) {
-    return step_common(e, rows, B, global_B, inj, loss_out, true, false, false, rows, B);
+    StepReq q = host_step(rows, B, global_B, inj, loss_out); q.train = true;
+    return step_common(e, q);
 }
 extern "C" int ntf_apply(ntf_engine* e) {
     if (!e) return NTF_EINVAL;
@@ -1497,31 +1527,43 @@ extern "C" int ntf_stage_order(ntf_engine* e, const int64_t* order, int64_t n) {
     HIPCHK(e, hipStreamSynchronize(e->st));
     return NTF_OK;
 }
+// rows [offset, offset + B) lie inside the minibatch [global_offset, global_offset + global_B), which lies inside the staged order
+static int staged_span_ok(ntf_engine* e, const char* who, int64_t offset, int32_t B, int64_t global_offset, int32_t global_B) {
+    const int64_t n = (int64_t)e->h_order.size();
+    if (offset < 0 || B < 1 || offset + B > n || global_offset < 0 || global_offset + global_B > n || offset < global_offset || offset + B > global_offset + global_B)
+        FAIL(e, NTF_EINVAL, std::string(who) + ": shard / batch outside the staged order");
+    return NTF_OK;
+}
+// the batch that follows [offset, offset + B) in the staged order (an epoch walks it front to back, src/mdl/fnn.py:118): what the head prefetch works for
+static void clear_next_batch(ntf_engine* e) { e->hp_next_B = 0; e->hp_next_host = nullptr; }
+static void note_next_batch(ntf_engine* e, int64_t offset, int32_t B) {
+    const int64_t n = (int64_t)e->h_order.size(), no = offset + B; const int nB = (int)std::min<int64_t>(B, n - no);
+    if (nB >= 1) { e->hp_next_rows = e->d_order + no; e->hp_next_B = nB; e->hp_next_host = e->h_order.data() + no; }
+    else clear_next_batch(e);
+}
 extern "C" int ntf_step_staged(ntf_engine* e, int64_t offset, int32_t B, int64_t global_offset, int32_t global_B, int32_t train, int32_t apply,
                                float* loss_out) {
     if (!e) return NTF_EINVAL;
-    const int64_t n = (int64_t)e->h_order.size();
-    if (offset < 0 || B < 1 || offset + B > n || global_offset < 0 || global_offset + global_B > n || offset < global_offset ||
-        offset + B > global_offset + global_B)
-        FAIL(e, NTF_EINVAL, "step_staged: shard / batch outside the staged order");
-    // the batch that follows in the staged order (an epoch walks it front to back, src/mdl/fnn.py:118): what the head prefetch works for
-    const int64_t no = offset + B; const int nB = (int)std::min<int64_t>(B, n - no);
-    if (train && apply && global_offset == offset && global_B == B && nB >= 1) { e->hp_next_rows = e->d_order + no; e->hp_next_B = nB; e->hp_next_host = e->h_order.data() + no; }
-    else { e->hp_next_B = 0; e->hp_next_host = nullptr; }
-    const int rc = step_common(e, e->d_order + offset, B, global_B, nullptr, loss_out, train != 0, apply != 0, true, e->h_order.data() + global_offset, global_B,
-                               false, (uint32_t)(offset - global_offset));
-    e->hp_next_B = 0; e->hp_next_host = nullptr;
+    if (int r = staged_span_ok(e, "step_staged", offset, B, global_offset, global_B)) return r;
+    if (train && apply && global_offset == offset && global_B == B) note_next_batch(e, offset, B); else clear_next_batch(e);
+    StepReq q = staged_step(e, offset, B, global_offset, global_B, loss_out); q.train = train != 0; q.apply = apply != 0;
+    const int rc = step_common(e, q);
+    clear_next_batch(e);
     return rc;
 }
 
-extern "C" int ntf_step_staged_deferred(ntf_engine* e, int64_t offset, int32_t B, int64_t global_offset, int32_t global_B, float* loss_out) {
+// a data-parallel rank's step: the output layer's dW kernel is left to ntf_dw_chunk; cb (may be null): called in front of every forward range (fwd_ranges)
+static int staged_deferred(ntf_engine* e, const char* who, int64_t offset, int32_t B, int64_t global_offset, int32_t global_B, float* loss_out, int (*cb)(int32_t, void*), void* user) {
     if (!e) return NTF_EINVAL;
-    const int64_t n = (int64_t)e->h_order.size();
-    if (offset < 0 || B < 1 || offset + B > n || global_offset < 0 || global_offset + global_B > n || offset < global_offset ||
-        offset + B > global_offset + global_B)
-        FAIL(e, NTF_EINVAL, "step_staged_deferred: shard / batch outside the staged order");
-    return step_common(e, e->d_order + offset, B, global_B, nullptr, loss_out, true, false, true, e->h_order.data() + global_offset, global_B, true,
-                       (uint32_t)(offset - global_offset));
+    if (int r = staged_span_ok(e, who, offset, B, global_offset, global_B)) return r;
+    e->cb_fn = cb; e->cb_user = user;
+    StepReq q = staged_step(e, offset, B, global_offset, global_B, loss_out); q.train = true; q.defer_dw = true;
+    const int rc = step_common(e, q);
+    e->cb_fn = nullptr; e->cb_user = nullptr;
+    return rc;
+}
+extern "C" int ntf_step_staged_deferred(ntf_engine* e, int64_t offset, int32_t B, int64_t global_offset, int32_t global_B, float* loss_out) {
+    return staged_deferred(e, "step_staged_deferred", offset, B, global_offset, global_B, loss_out, nullptr, nullptr);
 }
 // ---- data-parallel pipelining of the head (see fwd_ranges): the ranges, and the deferred step with a callback in front of every range
 extern "C" int ntf_fwd_ranges(ntf_engine* e, int32_t B, int32_t* n_ranges, int32_t* k0_k1 /* nullable: 2 x 4 ints, dW chunks [k0, k1) of each range */) {
@@ -1534,21 +1576,12 @@ extern "C" int ntf_fwd_ranges(ntf_engine* e, int32_t B, int32_t* n_ranges, int32
 }
 extern "C" int ntf_step_staged_deferred_cb(ntf_engine* e, int64_t offset, int32_t B, int64_t global_offset, int32_t global_B, float* loss_out,
                                            int (*before_range)(int32_t range, void* user), void* user) {
-    if (!e) return NTF_EINVAL;
-    const int64_t n = (int64_t)e->h_order.size();
-    if (offset < 0 || B < 1 || offset + B > n || global_offset < 0 || global_offset + global_B > n || offset < global_offset ||
-        offset + B > global_offset + global_B)
-        FAIL(e, NTF_EINVAL, "step_staged_deferred_cb: shard / batch outside the staged order");
-    e->cb_fn = before_range; e->cb_user = user;
-    const int rc = step_common(e, e->d_order + offset, B, global_B, nullptr, loss_out, true, false, true, e->h_order.data() + global_offset, global_B, true,
-                               (uint32_t)(offset - global_offset));
-    e->cb_fn = nullptr; e->cb_user = nullptr;
-    return rc;
+    return staged_deferred(e, "step_staged_deferred_cb", offset, B, global_offset, global_B, loss_out, before_range, user);
 }
 static int dw_chunk_span(ntf_engine* e, int k, int64_t& off_w, int64_t& off_r, int64_t& cnt, int& wg_begin) {
     const LayerInfo& li = e->layers[e->L - 1];
-    const int tile = fused_dw_tile(), M = li.out, total = (M + tile - 1) / tile, n = (total + 255) / 256;
-    if (!fused_ok(e) || k < 0 || k >= n) FAIL(e, NTF_EINVAL, "dw_chunk: bad chunk index (or the fused output-layer path does not apply to this shape)");
+    const int tile = fused_dw_tile(), M = li.out;
+    if (!fused_ok(e) || k < 0 || k >= dw_chunks(e)) FAIL(e, NTF_EINVAL, "dw_chunk: bad chunk index (or the fused output-layer path does not apply to this shape)");
     wg_begin = k * 256;
     const int64_t lo = (int64_t)wg_begin * tile * li.in, hi = std::min<int64_t>((int64_t)(wg_begin + 256) * tile, M) * li.in;
     off_w = li.off[NTF_P_WEIGHT] + lo; cnt = hi - lo;
@@ -1557,8 +1590,7 @@ static int dw_chunk_span(ntf_engine* e, int k, int64_t& off_w, int64_t& off_r, i
 }
 extern "C" int ntf_dw_chunks(ntf_engine* e, int32_t* n_chunks) {
     if (!e || !n_chunks) return NTF_EINVAL;
-    const int tile = fused_dw_tile(), total = (e->layers[e->L - 1].out + tile - 1) / tile;
-    *n_chunks = fused_ok(e) ? (total + 255) / 256 : 0;
+    *n_chunks = fused_ok(e) ? dw_chunks(e) : 0;
     return NTF_OK;
 }
 extern "C" int ntf_dw_chunk_range(ntf_engine* e, int32_t k, int64_t* off_weight, int64_t* off_rho, int64_t* count) {
@@ -1586,9 +1618,7 @@ extern "C" int ntf_dw_chunk(ntf_engine* e, int32_t k) {
         e->pend_valid = false;
         if ((r = join_side(e))) return r;       // the hidden layers' gradients (side stream, beside the chunks) are complete for whatever the caller queues next on this stream
     }
-    hipError_t s = hipGetLastError();
-    if (s != hipSuccess) FAIL(e, NTF_EHIP, std::string("kernel launch: ") + hipGetErrorString(s));
-    return NTF_OK;
+    return launch_check(e);
 }
 // One train step of an expert-sharded engine in three phases (include/opentf_amd.h): the host sums d(hidden) over the shards between phases 1 and 3,
 // while phase 2 (this shard's output-layer backward, the longest kernel after the forward) runs.
@@ -1606,17 +1636,11 @@ extern "C" int ntf_step_staged_ep(ntf_engine* e, int64_t offset, int32_t B, int3
         if (e->ep_open == 2 && e->ep_side) HIPCHK(e, hipStreamWaitEvent(e->st, e->ev_join, 0));   // an abandoned step's side-stream kernel still orders before this one
         e->pend_valid = false; e->ep_open = 0;
         if ((r = stage_rows(e, e->d_order + offset, B, true, &c.rows_dev))) return r;
-        if (e->cfg.nsd == NTF_NSD_UNIGRAM_B && e->cfg.ns > 0) {
-            // (phase 3 of the previous step may have staged THIS batch's table beside its dW kernel, as step_common's head prefetch does)
-            if (e->hp.valid && e->hp.ub >= 0 && e->hp.step == c.step && e->hp.rows == c.rows_dev && e->hp.B == B) c.ub = e->hp.ub;
-            else { c.ub = (e->ub_slot ^= 1); if ((r = set_batch_unigram(e, e->h_order.data() + offset, B, c.ub, e->st))) return r; }
-            e->ub_slot = c.ub;
-        }
+        // (phase 3 of the previous step may have staged THIS batch's table beside its dW kernel, as step_common's head prefetch does)
+        if (e->cfg.nsd == NTF_NSD_UNIGRAM_B && e->cfg.ns > 0 && (r = pick_batch_unigram(e, c, e->h_order.data() + offset, B, true))) return r;
         if ((r = run_step(e, c, true))) return r;
         e->last_B = B; e->last_global_B = B; e->neg_step = c.step;
-        // the batch that follows in the staged order: what phase 3's head prefetch works for
-        { const int64_t no = offset + B; const int nB = (int)std::min<int64_t>(B, n - no);
-          if (nB >= 1) { e->hp_next_rows = e->d_order + no; e->hp_next_B = nB; e->hp_next_host = e->h_order.data() + no; } else { e->hp_next_B = 0; e->hp_next_host = nullptr; } }
+        note_next_batch(e, offset, B);      // what phase 3's head prefetch works for
         e->ep_ctx = c; e->ep_open = 1;
         // phase 2 (this shard's dW kernel) on the side stream, beside the exchange and phase 3: one rank of 2 runs 1.684 -> 1.626 ms, of 4 1.605 -> 1.584, of 8
         // unchanged (its split-K dW launch is a single round: no idle tail to fill)
@@ -1636,14 +1660,12 @@ extern "C" int ntf_step_staged_ep(ntf_engine* e, int64_t offset, int32_t B, int3
             HIPCHK(e, hipEventRecord(e->ev_join, e->st3));
         } else if ((r = run_step(e, c, false))) return r;
         if (phase == 3) {
-            e->hp_next_B = 0; e->hp_next_host = nullptr;
+            clear_next_batch(e);
             if (e->ep_side) HIPCHK(e, hipStreamWaitEvent(e->st, e->ev_join, 0));
             if ((r = apply_adam(e))) return r;
         }
     } else FAIL(e, NTF_EINVAL, "step_staged_ep: phase must be 1, 2 or 3");
-    hipError_t s = hipGetLastError();
-    if (s != hipSuccess) FAIL(e, NTF_EHIP, std::string("kernel launch: ") + hipGetErrorString(s));
-    return NTF_OK;
+    return launch_check(e);
 }
 // where phase 1 leaves this shard's partial d(hidden) and phase 3 expects the sum: [B, h[-1]] floats (null when there is no hidden layer)
 extern "C" int ntf_dh_buffer(ntf_engine* e, void** dev_ptr, int64_t* n_floats) {
@@ -1693,24 +1715,48 @@ extern "C" int ntf_epoch_loss(ntf_engine* e, double* sum, int64_t* steps) {
 }
 
 // ------------------------------------------------------------------------------------------ inference
-static int infer_pass(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, StepCtx& c) {
+// the head of an inference pass: the next step number, the rows and the injected tensors (all but the negatives) staged, X gathered
+static int infer_begin(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, StepCtx& c) {
     int r;
     if ((r = check_ready(e, false))) return r;
     c.B = B; c.global_B = B; c.inj = inj; c.train = false; c.step = e->step++;
     if ((r = stage_rows(e, rows, B, false, &c.rows_dev))) return r;
-    StepCtx ci = c;
-    ntf_inject noneg;
+    StepCtx ci = c; ntf_inject noneg;
     if (inj) { noneg = *inj; noneg.neg_idx = nullptr; ci.inj = &noneg; }
     if ((r = stage_all_inj(e, ci))) return r;
-    if ((r = make_input(e, c))) return r;
-    return forward_layers(e, c, true, false);  // logits (post leaky_relu) in dZout
+    return make_input(e, c);
 }
+// ... and a pass on the generic chain: logits (post leaky_relu) in dZout
+static int infer_pass(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, StepCtx& c) { const int r = infer_begin(e, rows, B, inj, c); return r ? r : forward_layers(e, c, true, false); }
 
 static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, int pass, int passes, bool want_unc, bool logits, bool split);
-static int range_raised(ntf_engine* e, bool& raised);
+// fp16x3 inference: did an operand of the passes just queued leave the fp16 window?  (one 4-byte read; the caller synchronises for its outputs anyway)
+static int range_raised(ntf_engine* e, bool& raised) {
+    raised = false;
+    if (!range_ptr(e)) return NTF_OK;
+    int32_t v = 0;
+    if (int r = d2h_sync(e, &v, e->d_range, 4)) return r;
+    raised = v != 0;
+    if (raised) e->range_fallbacks_host += 1;
+    return NTF_OK;
+}
 // inference on the fused kernels: the split-product one where its planes exist (H = 128, default arithmetic), else - and behind a raised range flag - the exact-f32 one
 static bool infer_split(const ntf_engine* e) { return fused_ok(e) && e->pl_mu != nullptr; }
 static bool infer_fused(const ntf_engine* e) { return fused_ok(e) && (e->infer_f32 || e->pl_mu != nullptr); }
+// The two arms of such a call.  run(split) queues its passes, first on the split-product kernel; behind a raised range flag e->step goes back to the call's first step (the same
+// generator keys), redo() clears what the passes accumulated, and the exact-f32 kernel runs them once.  done = false: NTF_INFER_F32=0 behind a raised flag - the caller's generic chain
+template <class Run, class Redo> static int infer_arms(ntf_engine* e, bool& done, Run run, Redo redo) {
+    const uint64_t step0 = e->step;
+    bool split = infer_split(e); done = false;
+    for (int arm = 0; arm < 2 && !done; ++arm) {
+        if (split && range_ptr(e)) HIPCHK(e, hipMemsetAsync(e->d_range, 0, 4, e->st));
+        int r = run(split); if (r) return r;
+        bool raised = false; if (split && (r = range_raised(e, raised))) return r;
+        done = !raised;
+        if (raised) { e->step = step0; split = false; if ((r = redo())) return r; if (!e->infer_f32) break; }
+    }
+    return NTF_OK;
+}
 
 extern "C" int ntf_logits(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, float* logits_host) {
     if (!e || !logits_host) return NTF_EINVAL;
@@ -1719,25 +1765,12 @@ extern "C" int ntf_logits(ntf_engine* e, const int64_t* rows, int32_t B, const n
     if (infer_fused(e)) {
         // the kernel the inference ships (k_out_fwd_b6 / k_out_probs), storing leaky_relu(z) instead of its sigmoid
         if (!e->Pbuf) DM(e, &e->Pbuf, (int64_t)e->cfg.max_batch * M);
-        const uint64_t step0 = e->step;
-        bool split = infer_split(e), done = false;
-        for (int arm = 0; arm < 2 && !done; ++arm) {      // the split-product kernel; behind a raised range flag (or without planes) the exact-f32 one, same generator keys
-            if (split && range_ptr(e)) HIPCHK(e, hipMemsetAsync(e->d_range, 0, 4, e->st));
-            int r = infer_pass_fused(e, rows, B, inj, 0, 1, false, true, split); if (r) return r;
-            bool raised = false; if (split && (r = range_raised(e, raised))) return r;
-            done = !raised;
-            if (raised) { e->step = step0; split = false; if (!e->infer_f32) break; }
-        }
-        if (done) {
-            HIPCHK(e, hipMemcpyAsync(logits_host, e->Pbuf, (size_t)B * M * 4, hipMemcpyDeviceToHost, e->st));
-            HIPCHK(e, hipStreamSynchronize(e->st));
-            return NTF_OK;
-        }
+        bool done;
+        if (int r = infer_arms(e, done, [&](bool split) { return infer_pass_fused(e, rows, B, inj, 0, 1, false, true, split); }, [] { return (int)NTF_OK; })) return r;
+        if (done) return d2h_sync(e, logits_host, e->Pbuf, (size_t)B * M * 4);
     }
     StepCtx c; int r = infer_pass(e, rows, B, inj, c); if (r) return r;
-    HIPCHK(e, hipMemcpyAsync(logits_host, e->dZout, (size_t)B * M * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return NTF_OK;
+    return d2h_sync(e, logits_host, e->dZout, (size_t)B * M * 4);
 }
 
 extern "C" int ntf_get_negatives(ntf_engine* e, int64_t* host, int64_t count) {
@@ -1747,9 +1780,7 @@ extern "C" int ntf_get_negatives(ntf_engine* e, int64_t* host, int64_t count) {
     if (count != (int64_t)B * ns) FAIL(e, NTF_EINVAL, "negatives: count != B * ns of the last step");
     HIPCHK(e, hipSetDevice(e->cfg.device));
     if (e->st4) HIPCHK(e, hipStreamSynchronize(e->st4));
-    HIPCHK(e, hipMemcpyAsync(host, e->d_neg_set[e->neg_step & 1], (size_t)count * 8, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return NTF_OK;
+    return d2h_sync(e, host, e->d_neg_set[e->neg_step & 1], (size_t)count * 8);
 }
 
 // d loss / d z of the output layer as the last backward left it (fused path: transposed dzT; generic path: [B, M]) -> host [B, M]
@@ -1766,41 +1797,29 @@ extern "C" int ntf_get_dlogits(ntf_engine* e, float* host, int64_t count) {
         float inv = 0.f;
         if (e->last_dz_packed_scale > 0.f) {
             int32_t raised = 0;
-            HIPCHK(e, hipMemcpyAsync(&raised, e->d_range, 4, hipMemcpyDeviceToHost, e->st));
-            HIPCHK(e, hipStreamSynchronize(e->st));
+            if (int r = d2h_sync(e, &raised, e->d_range, 4)) return r;
             if (!raised) inv = 1.f / e->last_dz_packed_scale;
         }
         launch_fused_probs_finish(e->st, B, e->layers[e->L - 1].in, M, e->fws, e->dZout, e->Pbuf, nullptr, 1.f, true, inv);
         src = e->Pbuf;
     }
-    HIPCHK(e, hipMemcpyAsync(host, src, (size_t)B * M * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    return NTF_OK;
+    return d2h_sync(e, host, src, (size_t)B * M * 4);
 }
 
 // one MC pass of the inference through the fused forward kernel: probabilities accumulate in the transposed buffer dZout
 // split: the split-product kernel on the fp16 planes (H = 128), range-checked; else the exact-f32 kernel on mu / sigma * eps themselves (any fused width)
 static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const ntf_inject* inj, int pass, int passes, bool want_unc, bool logits, bool split) {
     int r;
-    if ((r = check_ready(e, false))) return r;
-    StepCtx c; c.B = B; c.global_B = B; c.inj = inj; c.train = false; c.step = e->step++;
-    if ((r = stage_rows(e, rows, B, false, &c.rows_dev))) return r;
-    StepCtx ci = c;
-    ntf_inject noneg;
-    if (inj) { noneg = *inj; noneg.neg_idx = nullptr; ci.inj = &noneg; }
-    if ((r = stage_all_inj(e, ci))) return r;
-    if ((r = make_input(e, c))) return r;
+    StepCtx c;
+    if ((r = infer_begin(e, rows, B, inj, c))) return r;
     if ((r = forward_layers(e, c, true, true))) return r;   // hidden layers only
     const int M = e->cfg.dims[e->L];
     const LayerInfo& lo = e->layers[e->L - 1];
-    FusedOut f;
-    f.B = B; f.H = lo.in; f.M = M; f.bayes = e->cfg.bayesian; f.train = 0;
-    f.h = e->act[e->L - 1];
+    FusedOut f = fused_out_base(e, c); f.train = 0;
     f.mu = e->P + lo.off[NTF_P_WEIGHT]; f.mu_b = e->P + lo.off[NTF_P_BIAS];
     f.tnw = e->cfg.tnw; f.tpw = e->cfg.tpw; f.inv_B = 1.f / (float)B;
     f.dzT = e->dZout; f.dh_slab = e->dh_slab; f.ws = e->fws;
-    f.split = split; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp;
-    f.w_scale = kW16Scale; f.h_scale = kH16Scale; f.dz_scale = 1.f;
+    f.split = split; f.mu_pl = e->pl_mu; f.wp_pl = e->pl_wp; f.dz_scale = 1.f;
     int32_t* const rflag = split ? range_ptr(e) : nullptr;
     if (e->cfg.bayesian) {
         e->pre_valid = false;   // this pass's operands overwrite any prefetched ones
@@ -1811,29 +1830,16 @@ static int infer_pass_fused(ntf_engine* e, const int64_t* rows, int32_t B, const
         const bool nof32 = split && e->lean && !inj && e->pl_wp && rflag;
         { Scope t(e, F_FLIPOUT_OPERAND);
           // (the planes of mu are the first pass's: the passes of one call run back to back on unchanged parameters, and the range flag they share is read behind the last)
-          launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT], nullptr, lo.nw(), normal_spec(e, c, e->L - 1, T_EPS_W), nof32 ? nullptr : e->Wp[e->L - 1], 0.0, e->d_kl,
-                                 split ? e->pl_wp : nullptr, split && pass == 0 ? e->pl_mu : nullptr, f.mu, lo.in, kW16Scale, rflag);
-          launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS], nullptr, lo.out, normal_spec(e, c, e->L - 1, T_EPS_B), e->bp[e->L - 1], 0.0, e->d_kl); }
+          WpOpts o; o.kl = false; o.f32 = !nof32; o.split = split; o.planes_mu = pass == 0;
+          launch_out_weight_operand(e, c, o);
+          launch_out_bias_operand(e, c, false); }
         f.wp = e->Wp[e->L - 1]; f.bp = e->bp[e->L - 1];
-        f.s_in = sign_spec(e, c, e->L - 1, T_S_IN, lo.in); f.s_out = sign_spec(e, c, e->L - 1, T_S_OUT, lo.out);
         f.planes_ready = 1;
     }
     f.probs = 1; f.pacc = pass > 0; f.pscale = 1.0f / (float)passes; f.plogit = logits; f.rflag = rflag;
     { Scope t(e, F_OUT_FUSED_AUX); launch_fused_out_fwd(e->st, f, 1); }
     { Scope t(e, F_OUT_FUSED_FWD); launch_fused_out_fwd(e->st, f, 2); }
     { Scope t(e, F_INFER); launch_fused_probs_finish(e->st, B, lo.in, M, e->fws, e->dZout, e->Pbuf, want_unc ? e->ent_mc : nullptr, 1.0f / (float)passes, pass == passes - 1); }
-    return NTF_OK;
-}
-
-// fp16x3 inference: did an operand of the passes just queued leave the fp16 window?  (one 4-byte read; the caller synchronises for its outputs anyway)
-static int range_raised(ntf_engine* e, bool& raised) {
-    raised = false;
-    if (!range_ptr(e)) return NTF_OK;
-    int32_t v = 0;
-    HIPCHK(e, hipMemcpyAsync(&v, e->d_range, 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
-    raised = v != 0;
-    if (raised) e->range_fallbacks_host += 1;
     return NTF_OK;
 }
 
@@ -1906,11 +1912,9 @@ static int infer_mc_fused(ntf_engine* e, const int64_t* rows, int32_t B, int pas
             const int64_t pl0 = c_lo / 32 * 64 * H;      // the planes of 32-expert tile c_lo / 32 (fused_planes_elems layout)
             { Scope t(e, F_FLIPOUT_OPERAND);
               for (int q = 0; q < np; ++q) {
-                  NormalSpec ew = normal_spec(e, cs[q], e->L - 1, T_EPS_W), eb = normal_spec(e, cs[q], e->L - 1, T_EPS_B);
-                  ew.qbase += c_lo * H / 4; eb.qbase += c_lo / 4;
-                  launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_WEIGHT] + c_lo * H, nullptr, (c_hi - c_lo) * H, ew, nullptr, 0.0, e->d_kl,
-                                         e->mc_ring + q * slot_pl, p0 == 0 && q == 0 ? e->pl_mu + pl0 : nullptr, e->P + lo.off[NTF_P_WEIGHT] + c_lo * H, H, kW16Scale, rflag);
-                  launch_flipout_perturb(e->st, e->P + lo.off[NTF_P_RHO_BIAS] + c_lo, nullptr, c_hi - c_lo, eb, e->mc_bp + q * e->mc_range, 0.0, e->d_kl);
+                  WpOpts o; o.kl = false; o.f32 = false; o.planes_mu = p0 == 0 && q == 0; o.x0 = c_lo; o.nx = c_hi - c_lo; o.ring = e->mc_ring + q * slot_pl;
+                  launch_out_weight_operand(e, cs[q], o);
+                  launch_out_bias_operand(e, cs[q], false, c_lo, c_hi - c_lo, e->mc_bp + q * e->mc_range);
               } }
             f.c_lo = (int)c_lo; f.c_hi = (int)c_hi; f.mu_pl = e->pl_mu + pl0;
             { Scope t(e, F_OUT_FUSED_FWD); launch_fused_probs_mc(e->st, f); }
@@ -1929,25 +1933,20 @@ static int infer_probs(ntf_engine* e, const int64_t* rows, int32_t B, int32_t nm
     const int passes = e->cfg.bayesian ? std::max(1, nmc) : 1;
     if (want_unc) HIPCHK(e, hipMemsetAsync(e->ent_mc, 0, (size_t)B * 4, e->st));
     if (infer_fused(e)) {     // fused forward kernel: no dense logits, MC mean accumulated on the fly
-        const uint64_t step0 = e->step;
-        bool split = infer_split(e);      // the split-product kernel (H = 128); without planes, and behind a raised range flag, the exact-f32 one
-        // NTF_INFER_MC=1: the passes of a Flipout call inside k_out_probs_mc (injected noise, one pass, Fnn and every other width / arithmetic: the per-pass loop)
-        bool mc = e->infer_mc && split && e->cfg.bayesian && passes > 1 && !inj_per_mc && e->pl_wp && range_ptr(e);
-        for (int arm = 0; arm < 2; ++arm) {
-            if (split && range_ptr(e)) HIPCHK(e, hipMemsetAsync(e->d_range, 0, 4, e->st));
-            if (mc) { int r = infer_mc_fused(e, rows, B, passes, want_unc); if (r) return r; }
-            else for (int p = 0; p < passes; ++p) { int r = infer_pass_fused(e, rows, B, inj_per_mc ? &inj_per_mc[p] : nullptr, p, passes, want_unc, false, split); if (r) return r; }
-            bool raised = false; if (split) { int r = range_raised(e, raised); if (r) return r; }
-            if (!raised) {
-                if (mc) e->mc_fused_passes += passes;
-                if (want_unc) { Scope t(e, F_INFER); launch_row_entropy(e->st, e->Pbuf, B, M, e->ent_mean); }
-                return NTF_OK;
-            }
-            mc = false;
-            e->step = step0;   // an operand left the fp16 window: the same passes (same generator keys) again on the exact-f32 kernel (NTF_INFER_F32=0: the generic chain below)
-            split = false;
-            if (want_unc) HIPCHK(e, hipMemsetAsync(e->ent_mc, 0, (size_t)B * 4, e->st));
-            if (!e->infer_f32) break;
+        // NTF_INFER_MC=1: the passes of a Flipout call inside k_out_probs_mc, on the split-product arm (injected noise, one pass, Fnn and every other width / arithmetic: the per-pass loop)
+        const bool mc_ok = e->infer_mc && e->cfg.bayesian && passes > 1 && !inj_per_mc && e->pl_wp && range_ptr(e);
+        bool mc = false, done;
+        int r = infer_arms(e, done, [&](bool split) {
+            mc = mc_ok && split;
+            if (mc) return infer_mc_fused(e, rows, B, passes, want_unc);
+            for (int p = 0; p < passes; ++p) { int rp = infer_pass_fused(e, rows, B, inj_per_mc ? &inj_per_mc[p] : nullptr, p, passes, want_unc, false, split); if (rp) return rp; }
+            return (int)NTF_OK;
+        }, [&]() -> int { if (want_unc) HIPCHK(e, hipMemsetAsync(e->ent_mc, 0, (size_t)B * 4, e->st)); return NTF_OK; });
+        if (r) return r;
+        if (done) {
+            if (mc) e->mc_fused_passes += passes;
+            if (want_unc) { Scope t(e, F_INFER); launch_row_entropy(e->st, e->Pbuf, B, M, e->ent_mean); }
+            return NTF_OK;
         }
     }
     for (int p = 0; p < passes; ++p) {
@@ -1974,8 +1973,7 @@ extern "C" int ntf_forward(ntf_engine* e, const int64_t* rows, int32_t B, int32_
     if (!e || !probs_host) return NTF_EINVAL;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     int r = infer_probs(e, rows, B, nmc, inj_per_mc, pred_unc || model_unc); if (r) return r;
-    HIPCHK(e, hipMemcpyAsync(probs_host, e->Pbuf, (size_t)B * e->cfg.dims[e->L] * 4, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipStreamSynchronize(e->st));
+    if ((r = d2h_sync(e, probs_host, e->Pbuf, (size_t)B * e->cfg.dims[e->L] * 4))) return r;
     return copy_unc(e, B, pred_unc, model_unc);
 }
 

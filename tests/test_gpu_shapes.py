@@ -308,6 +308,18 @@ def test_nine_layers_are_refused_at_creation():
     assert b"n_layers" in libntf.lib().ntf_last_error(None)
 
 
+def test_retired_merge_bias_arm_is_refused_at_creation(monkeypatch):
+    """NTF_MERGE_BIAS=0 (the next step's output-bias operand as a launch of its own) is retired like the old NTF_FWD_KERNEL forms: ntf_engine_create fails with
+    NTF_EINVAL and says why; unset, or at its former default 1, the engine is created"""
+    monkeypatch.setenv("NTF_MERGE_BIAS", "0")
+    with pytest.raises(libntf.NtfError, match=r"ntf_engine_create failed \(-1\): NTF_MERGE_BIAS=0 .* was retired"):
+        libntf.Engine([16, 8], max_batch=4)
+    monkeypatch.setenv("NTF_MERGE_BIAS", "1")
+    libntf.Engine([16, 8], max_batch=4).close()
+    monkeypatch.delenv("NTF_MERGE_BIAS")
+    libntf.Engine([16, 8], max_batch=4).close()
+
+
 # ------------------------------------------------------------------------------------------ B. the batch sizes of expert-parallel ranks
 B_M = 4500
 B_PARAMS = [pytest.param(B, bay, mode, id=f"B{B}-{'bnn' if bay else 'fnn'}-{mode}")
