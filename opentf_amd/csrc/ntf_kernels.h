@@ -143,11 +143,14 @@ void launch_score_pos_keys_dense(hipStream_t st, const float* P, int B, int M, c
 void launch_score_pos_keys_topk(hipStream_t st, const float* vals, const int32_t* idx, int64_t n, int K, const int64_t* rows, const int64_t* t_indptr,
                                 const int32_t* t_indices, const int64_t* slot, uint32_t* keys, uint32_t* nan_flag);
 // micro-averaged ROC AUC over n * M scores (ntf_auc.hip): key table of the positives -> any number of count passes over device-resident scores -> integer finish.
-// All three return NTF_* codes; auc_free releases the state (after auc_finish too).
+// All three return NTF_* codes; auc_free releases the state (after auc_finish too).  minima: the count passes also keep every gap's smallest key (k_roc_count), and
+// roc_finish (in place of auc_finish) lists the ROC curve's corners of include/opentf_amd_roc.h beside the same integers.
 struct AucState;
-int auc_open(hipStream_t st, const uint32_t* pos_keys, size_t n_pos, int64_t n, int64_t M, AucState** out);
+int auc_open(hipStream_t st, const uint32_t* pos_keys, size_t n_pos, int64_t n, int64_t M, AucState** out, bool minima = false);
 int auc_count(AucState* s, hipStream_t st, const float* x /*16-byte aligned*/, int64_t L);
 int auc_finish(AucState* s, hipStream_t st, uint64_t implicit_zeros, uint64_t out_counts[3], double* out_auc);
+int roc_finish(AucState* s, hipStream_t st, uint64_t implicit_zeros, int64_t cap, uint64_t* fps, uint64_t* tps, float* thr, int64_t* n_points,
+               uint64_t out_counts[3], double* out_auc);
 void auc_free(AucState* s);
 
 // test hooks for the device generators

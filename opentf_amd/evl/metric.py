@@ -4,7 +4,9 @@ Same function names, arguments and returned DataFrames as the reference (`calcul
 44-73); the reference builds python dicts for pytrec_eval row by row, here the ranked top-K lists go through
 `ntf_rank_metrics` / `ntf_skill_coverage` of libopentf_amd.so.  `calculate_auc_roc` takes the host routes by default (sklearn as in the reference for dense
 predictions, `micro_auc_sparse` for sparse ones); with a device ordinal - `score_predictions` passes one when NTF_AUC_DEVICE=1 - the micro-averaged AUC is
-`micro_auc_device`: one streaming pass over the scores on the GPU (`ntf_auc_micro_dense` / `ntf_auc_micro_csr`), exact in integers.  The curve stays sklearn.
+`micro_auc_device`: one streaming pass over the scores on the GPU (`ntf_auc_micro_dense` / `ntf_auc_micro_csr`), exact in integers.  The curve of `aucroc+` is
+sklearn's by default; with `curve_device` - `score_predictions` passes one when NTF_ROC_DEVICE=1 - curve and AUC come from one such pass (`micro_roc_device`:
+`ntf_roc_micro_dense` / `ntf_roc_micro_csr`, include/opentf_amd_roc.h): the corner list of the same curve, not sklearn's `drop_intermediate=True` point list.
 `score_engine` (NTF_EVAL_ENGINE=1 in `Ntf.evaluate`) returns `score_predictions`' tables without a prediction matrix at all: the model's engine infers the rows and scores them
 where they are (`Engine.score_rows`, `ntf_score_rows`).
 Ties in the scores are ranked by ascending expert id (trec_eval: descending document name) — irrelevant for real-valued model
@@ -128,6 +130,27 @@ def micro_auc_sparse(Y, Y_):
     return U / (float(P) * float(total - P))
 
 
+def _auc_inputs(Y, Y_, who):
+    """what the AUC and the curve entries take: (truth indptr, truth indices, n, M, scores) with scores a (indptr, indices, values) triple for a scipy sparse `Y_`
+    and a contiguous f32 array for a dense one.  Raises as sklearn does for one class only, TypeError for a dense dtype other than f32 / f16."""
+    assert Y.shape == Y_.shape, f"Shape mismatch between truth Y {Y.shape} vs preds Y_ {Y_.shape}!"
+    if not sp.issparse(Y_):
+        Y_ = np.asarray(Y_)
+        if Y_.dtype not in (np.float32, np.float16):
+            raise TypeError(f"{who} takes dense scores as float32 or float16, not {Y_.dtype}: a cast could merge values that are distinct")
+    Yb = sp.csr_matrix(Y).copy(); Yb.data = (Yb.data != 0).astype(np.int8); Yb.eliminate_zeros(); Yb.sort_indices()
+    n, M = Yb.shape
+    if Yb.nnz == 0 or Yb.nnz == n * M:
+        raise ValueError(_ONE_CLASS)
+    ip, ix = np.ascontiguousarray(Yb.indptr, dtype=np.int64), np.ascontiguousarray(Yb.indices, dtype=np.int32)
+    if sp.issparse(Y_):
+        S = sp.csr_matrix(Y_).copy(); S.sum_duplicates(); S.sort_indices()
+        scores = (np.ascontiguousarray(S.indptr, dtype=np.int64), np.ascontiguousarray(S.indices, dtype=np.int32), np.ascontiguousarray(S.data, dtype=np.float32))
+    else:
+        scores = np.ascontiguousarray(Y_, dtype=np.float32)      # f16 -> f32 is exact
+    return ip, ix, n, M, scores
+
+
 def micro_auc_device(Y, Y_, device=0, chunk_bytes=0, return_counts=False):
     """Micro-averaged ROC AUC on the device: what `micro_auc_sparse` / sklearn's `roc_auc_score(Y.toarray(), Y_.toarray(), average='micro')`
     (src/evl/metric.py:36-41) compute, from one streaming pass over the scores (`ntf_auc_micro_csr` for a scipy sparse `Y_`, whose unstored entries
@@ -135,38 +158,59 @@ def micro_auc_device(Y, Y_, device=0, chunk_bytes=0, return_counts=False):
     P, N and U2 = sum over positives of (2 #negatives scored lower + #negatives scored equal); the AUC is U2 / (2 P N), one division in f64.  Dense
     input of any other dtype is refused: a cast to f32 could merge values that sklearn keeps apart.  `chunk_bytes`: device staging budget per upload
     (0: the library's default, NTF_AUC_CHUNK_BYTES).  return_counts: -> (auc, (P, N, U2)) with Python ints."""
-    assert Y.shape == Y_.shape, f"Shape mismatch between truth Y {Y.shape} vs preds Y_ {Y_.shape}!"
-    if not sp.issparse(Y_):
-        Y_ = np.asarray(Y_)
-        if Y_.dtype not in (np.float32, np.float16):
-            raise TypeError(f"micro_auc_device takes dense scores as float32 or float16, not {Y_.dtype}: a cast could merge values that are distinct")
-    Yb = sp.csr_matrix(Y).copy(); Yb.data = (Yb.data != 0).astype(np.int8); Yb.eliminate_zeros(); Yb.sort_indices()
-    n, M = Yb.shape
-    if Yb.nnz == 0 or Yb.nnz == n * M:
-        raise ValueError(_ONE_CLASS)
+    ip, ix, n, M, scores = _auc_inputs(Y, Y_, "micro_auc_device")
     from .. import libntf
-    ip, ix = np.ascontiguousarray(Yb.indptr, dtype=np.int64), np.ascontiguousarray(Yb.indices, dtype=np.int32)
     counts, auc = np.zeros(3, dtype=np.uint64), C.c_double()
-    if sp.issparse(Y_):
-        S = sp.csr_matrix(Y_).copy(); S.sum_duplicates(); S.sort_indices()
-        sip, six = np.ascontiguousarray(S.indptr, dtype=np.int64), np.ascontiguousarray(S.indices, dtype=np.int32)
-        sv = np.ascontiguousarray(S.data, dtype=np.float32)
+    if isinstance(scores, tuple):
+        sip, six, sv = scores
         rc = libntf.lib().ntf_auc_micro_csr(int(device), _ptr(sip), _ptr(six), _ptr(sv), n, M, _ptr(ip), _ptr(ix), n, None, int(chunk_bytes), _ptr(counts), C.byref(auc))
         name = "ntf_auc_micro_csr"
     else:
-        D = np.ascontiguousarray(Y_, dtype=np.float32)      # f16 -> f32 is exact
-        rc = libntf.lib().ntf_auc_micro_dense(int(device), _ptr(D), n, M, M, _ptr(ip), _ptr(ix), n, None, int(chunk_bytes), _ptr(counts), C.byref(auc))
+        rc = libntf.lib().ntf_auc_micro_dense(int(device), _ptr(scores), n, M, M, _ptr(ip), _ptr(ix), n, None, int(chunk_bytes), _ptr(counts), C.byref(auc))
         name = "ntf_auc_micro_dense"
     if rc != 0:
         raise libntf.NtfError(f"{name} failed ({rc})" + (": a NaN score, or an argument outside the contract" if rc == libntf.NTF_EINVAL else ""))
     return (auc.value, tuple(int(c) for c in counts)) if return_counts else auc.value
 
 
-def calculate_auc_roc(Y, Y_, curve=False, device=None):
+def micro_roc_device(Y, Y_, device=0, chunk_bytes=0, return_counts=False):
+    """Micro-averaged ROC curve on the device, from the one streaming pass `micro_auc_device` makes (`ntf_roc_micro_csr` / `ntf_roc_micro_dense`,
+    include/opentf_amd_roc.h): -> (fpr, tpr, thresholds), f64, f64 and f32, first point (0, 0, inf), last (1, 1); with return_counts also (P, N, U2) as Python ints,
+    the integers `micro_auc_device` returns for the same input (AUC = U2 / (2 P N) = the polyline's own trapezoid).  fpr = fps / N and tpr = tps / P, one f64 division
+    each.  The points are the corners of sklearn's `roc_curve(Y.toarray().ravel(), Y_.toarray().ravel())`: the same piecewise-linear curve, each point one of
+    `roc_curve(..., drop_intermediate=False)`; not the `drop_intermediate=True` list, which keeps further points inside the horizontal runs.  Inputs as
+    `micro_auc_device`: scipy sparse (unstored entries score 0) or dense f32 / f16, other dtypes refused."""
+    ip, ix, n, M, scores = _auc_inputs(Y, Y_, "micro_roc_device")
+    from .. import libntf
+    P = len(ix)
+    cap = 2 * P + 2
+    fps, tps, thr = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.float32)
+    npts, counts, auc = C.c_int64(), np.zeros(3, dtype=np.uint64), C.c_double()
+    tail = (int(chunk_bytes), cap, _ptr(fps), _ptr(tps), _ptr(thr), C.byref(npts), _ptr(counts), C.byref(auc))
+    if isinstance(scores, tuple):
+        sip, six, sv = scores
+        rc = libntf.lib().ntf_roc_micro_csr(int(device), _ptr(sip), _ptr(six), _ptr(sv), n, M, _ptr(ip), _ptr(ix), n, None, *tail)
+        name = "ntf_roc_micro_csr"
+    else:
+        rc = libntf.lib().ntf_roc_micro_dense(int(device), _ptr(scores), n, M, M, _ptr(ip), _ptr(ix), n, None, *tail)
+        name = "ntf_roc_micro_dense"
+    if rc != 0:
+        raise libntf.NtfError(f"{name} failed ({rc})" + (": a NaN score, or an argument outside the contract" if rc == libntf.NTF_EINVAL else ""))
+    k = npts.value
+    Pn, Nn, U2 = (int(c) for c in counts)
+    curve = (fps[:k].astype(np.float64) / float(Nn), tps[:k].astype(np.float64) / float(Pn), thr[:k].copy())
+    return curve + ((Pn, Nn, U2),) if return_counts else curve
+
+
+def calculate_auc_roc(Y, Y_, curve=False, device=None, curve_device=None):
     """src/evl/metric.py:36-41.  Sparse predictions (the top-K `.pred` files) go through `micro_auc_sparse`; dense ones, and the curve
     itself, through sklearn as in the reference.  `device` (an ordinal; None: the host routes above): without the curve, sparse and dense
-    f32 predictions go through `micro_auc_device` instead."""
+    f32 predictions go through `micro_auc_device` instead.  `curve_device` (an ordinal; None: sklearn's curve, also with `device`): with the curve,
+    AUC (U2 / (2 P N)) and (fpr, tpr) of sparse and dense f32 predictions both come from the one device pass of `micro_roc_device` - the curve's corners, see there."""
     assert Y.shape == Y_.shape
+    if curve and curve_device is not None and (sp.issparse(Y_) or np.asarray(Y_).dtype == np.float32):
+        fpr, tpr, _, (P, N, U2) = micro_roc_device(Y, Y_, device=curve_device, return_counts=True)
+        return U2 / (2.0 * float(P) * float(N)), (fpr, tpr)
     if device is not None and not curve and (sp.issparse(Y_) or np.asarray(Y_).dtype == np.float32):
         return micro_auc_device(Y, Y_, device=device), None
     if sp.issparse(Y_) and not curve:
@@ -235,7 +279,8 @@ def score_predictions(teamsvecs, rows, Y_, spec, device=0):
         inst_parts.append(df); mean_parts.append(df_mean)
     if spec.auc:
         on_device = os.environ.get("NTF_AUC_DEVICE", "0") == "1"      # read per call; off: the host routes, as before the device entry existed
-        auc, roc = calculate_auc_roc(Y, Y_, curve=(spec.auc == "aucroc+"), device=device if on_device else None)
+        roc_on_device = os.environ.get("NTF_ROC_DEVICE", "0") == "1"  # likewise; only aucroc+ (the curve) reads it
+        auc, roc = calculate_auc_roc(Y, Y_, curve=(spec.auc == "aucroc+"), device=device if on_device else None, curve_device=device if roc_on_device else None)
         mean_parts.append(pd.DataFrame({"mean": [auc]}, index=pd.Index(["aucroc"], name="metrics")))
     if spec.skc:
         X = teamsvecs["skill"] if sp.issparse(teamsvecs["skill"]) else teamsvecs["original_skill"]

@@ -156,6 +156,13 @@ LINK_SYMBOLS = {
     "ntf_link_dense": (C.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P]),
 }
 
+# every symbol declared in include/opentf_amd_roc.h (the micro ROC curve beside the AUC: the third side header, NTF_ABI_VERSION unchanged): the AUC entries'
+# arguments up to chunk_bytes, then cap_points, fps, tps, thresholds, n_points, out_counts, out_auc
+ROC_SYMBOLS = {
+    "ntf_roc_micro_dense": (C.c_int, [C.c_int, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "ntf_roc_micro_csr": (C.c_int, [C.c_int, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -170,7 +177,7 @@ def lib():
         for name, (res, args) in SYMBOLS.items():
             fn = getattr(l, name)  # AttributeError if the library does not export a declared symbol
             fn.restype, fn.argtypes = res, args
-        for table in (FAIR_SYMBOLS, LINK_SYMBOLS):
+        for table in (FAIR_SYMBOLS, LINK_SYMBOLS, ROC_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = res, args
