@@ -2,7 +2,8 @@
 D2v.nearest_teams) against numpy in f64 on the same f32 inputs, s* = (T64 @ q64) / |T64 rows| / |q64|, within E(d) = (2 d + 16) * 2^-24 a sim (derived in
 tests/test_knn_host.py, which also holds the reference and the table generators).
 
-Largest |sim - s*| / E(d) seen over the parity cases on the device: 0.061 (N = 33, d = 64, Q = 31; 0.03 - 0.04 at d >= 100, 0.044 at d = 9)."""
+Largest |sim - s*| / E(d) seen over the parity cases on the device: 0.061 (N = 33, d = 64, Q = 31; 0.03 - 0.04 at d >= 100, 0.044 at d = 9).
+At N = 70 001 and 262 444 (tests/test_gpu_long_ranges.py: the sampled selection route, the block-stride loop of k_sims): 0.057 and 0.075."""
 import ctypes as C
 import functools
 

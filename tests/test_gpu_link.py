@@ -3,7 +3,8 @@ numpy in f64 on the same f32 inputs, x* = t64 . q64, within E(i, j) = (d + 2) * 
 returned x within (4 * 2^-24 + 2^-40) relative a probability (both derived in tests/test_link_host.py, which also holds the reference and the generators).
 
 Largest |x - x*| / E seen over the parity cases on the device: 0.121 (d = 9, C = 33, one query; 0.06 - 0.09 at d >= 100).  Largest |p - p*| / p* over 98 998 logits in
-[-28.9, 29.5]: 2.204 * 2^-24 = 0.551 of the bound (profiles/link_parity.md has the table)."""
+[-28.9, 29.5]: 2.204 * 2^-24 = 0.551 of the bound (profiles/link_parity.md has the table).
+At C = 70 001 and 131 073 (tests/test_gpu_long_ranges.py: the sampled selection route, the block-stride loop of k_sims): 0.147 (d = 80), 0.067 (d = 256)."""
 import ctypes as C
 import functools
 import os
