@@ -1,7 +1,8 @@
 """The fair stage of the reference's pipeline (cmd=[train,test,eval,fair]) on the MI355X: fairness-aware re-ranking of ranked expert lists (DetGreedy, DetCons,
-DetRelaxed) and the NDKL / skew measures of a ranked list, after Geyik, Ambler and Kenthapadi, "Fairness-aware ranking in search and recommendation systems",
-KDD 2019.  The per-row work goes through `ntf_fair_rerank` / `ntf_fair_metrics` of libopentf_amd.so (include/opentf_amd_fair.h); this module prepares their inputs
-- the protected attribute of every expert and the target distribution - and shapes their outputs.
+DetRelaxed, DetConstSort) and the NDKL / skew / infeasible measures of a ranked list, after Geyik, Ambler and Kenthapadi, "Fairness-aware ranking in search and
+recommendation systems", KDD 2019.  The per-row work goes through `ntf_fair_rerank` / `ntf_fair_metrics` (include/opentf_amd_fair.h) and `ntf_fair_constsort` /
+`ntf_fair_infeasible` (include/opentf_amd_fairsort.h) of libopentf_amd.so; this module prepares their inputs - the protected attribute of every expert and the
+target distribution - and shapes their outputs.
 
 The reference's own stage lives in a git submodule (src/Adila) that is absent from it, so three things here are unpinned choices, each kept in ONE function:
 the popularity rule (`popularity_groups`), the keys of the stage's config (`FairSpec.from_cfg`) and the names of the files it leaves (`fair_stem`); INTEGRATION.md
@@ -61,8 +62,10 @@ def target_distribution(notion, group, G, Y=None):
 
 def rerank(ranked_idx, ranked_val, group, p, algorithm, k_max, device=0):
     """-> (idx [n, k_max] int32, val [n, k_max] f32 or None): the first k_max ranks of every row of ranked_idx [n, K] (best first) re-ranked by `algorithm`
-    ('det_greedy', 'det_cons', 'det_relaxed') towards the target p ([1, G] or [n, G]); the k-th largest score goes to the k-th re-ranked expert"""
+    ('det_greedy', 'det_cons', 'det_relaxed', 'det_const_sort') towards the target p ([1, G] or [n, G]); the k-th largest score goes to the k-th re-ranked expert"""
     from .. import libntf
+    if algorithm == libntf.FAIR_CONST_SORT:
+        return libntf.fair_constsort(ranked_idx, ranked_val, group, p, k_out=int(k_max), device=device)
     return libntf.fair_rerank(ranked_idx, ranked_val, group, p, algorithm, k_out=int(k_max), device=device)
 
 
@@ -83,23 +86,42 @@ def fair_metrics(ranked_idx, group, p, cutoffs, device=0, names=None):
     return df, df.mean().to_frame("mean").rename_axis("metrics")
 
 
+def fair_infeasible(ranked_idx, group, p, cutoffs, device=0):
+    """-> (per-instance DataFrame, mean DataFrame) with the columns infeasible_index_{c} and infeasible_count_{c} over the cutoffs c: the ranks k <= c at which some
+    group holds fewer than floor(k p_g) of the first k entries, and those shortfalls counted per group (InfeasibleIndex / InfeasibleCount of the paper)"""
+    import pandas as pd
+    from .. import libntf
+    cuts = [int(c) for c in cutoffs]
+    index, count = libntf.fair_infeasible(ranked_idx, group, p, cuts, device=device)
+    cols = {f"infeasible_index_{c}": index[:, q] for q, c in enumerate(cuts)}
+    cols.update({f"infeasible_count_{c}": count[:, q] for q, c in enumerate(cuts)})
+    df = pd.DataFrame(cols)
+    return df, df.mean().to_frame("mean").rename_axis("metrics")
+
+
 class FairSpec:
-    """what a fair config asks for, parsed once.  THE keys of the stage's config (unpinned): algorithm, notion, attribute, k_max, cutoffs"""
-    def __init__(self, algorithm="det_greedy", notion="dp", attribute="popularity", k_max=100, cutoffs=(2, 5, 10)):
+    """what a fair config asks for, parsed once.  THE keys of the stage's config (unpinned): algorithm, notion, attribute, k_max, cutoffs, infeasible"""
+    def __init__(self, algorithm="det_greedy", notion="dp", attribute="popularity", k_max=100, cutoffs=(2, 5, 10), infeasible=False):
         from .. import libntf
-        if algorithm not in libntf.FAIR_ALGORITHMS:
-            raise ValueError(f"unknown fair algorithm {algorithm!r}: one of {sorted(libntf.FAIR_ALGORITHMS)}")
+        algorithms = sorted(libntf.FAIR_ALGORITHMS) + [libntf.FAIR_CONST_SORT]
+        if algorithm not in algorithms:
+            raise ValueError(f"unknown fair algorithm {algorithm!r}: one of {algorithms}")
         if notion not in ("dp", "eo"):
             raise ValueError(f"unknown fairness notion {notion!r}: 'dp' or 'eo'")
         self.algorithm, self.notion, self.attribute, self.k_max = str(algorithm), str(notion), str(attribute), int(k_max)
         self.cutoffs = [int(c) for c in (cutoffs.split(",") if isinstance(cutoffs, str) else cutoffs)]
+        if isinstance(infeasible, str):                  # a hand-written config may carry the word, and bool("false") is True
+            if infeasible.strip().lower() not in ("true", "false"):
+                raise ValueError(f"infeasible must be true or false, got {infeasible!r}")
+            infeasible = infeasible.strip().lower() == "true"
+        self.infeasible = bool(infeasible)
 
     @classmethod
     def from_cfg(cls, faircfg):
         from ..mdl.ntf import cfg_get
         d = cls()
         return cls(cfg_get(faircfg, "algorithm") or d.algorithm, cfg_get(faircfg, "notion") or d.notion, cfg_get(faircfg, "attribute") or d.attribute,
-                   cfg_get(faircfg, "k_max") or d.k_max, cfg_get(faircfg, "cutoffs") or d.cutoffs)
+                   cfg_get(faircfg, "k_max") or d.k_max, cfg_get(faircfg, "cutoffs") or d.cutoffs, cfg_get(faircfg, "infeasible") or d.infeasible)
 
     def attribute_name(self):
         return "popularity" if self.attribute == "popularity" else os.path.splitext(os.path.basename(self.attribute))[0]
@@ -144,6 +166,8 @@ def fair_predictions(teamsvecs, rows, Y_, spec, group, names, device=0):
     p = target_distribution(spec.notion, group, len(names), Y)
     idx, val = rerank(ranked, vals, group, p, spec.algorithm, k_max, device=device)
     fair = _before_after(fair_metrics(ranked, group, p, cuts, device=device, names=names)[1], fair_metrics(idx, group, p, cuts, device=device, names=names)[1])
+    if spec.infeasible:
+        fair = pd.concat([fair, _before_after(fair_infeasible(ranked, group, p, cuts, device=device)[1], fair_infeasible(idx, group, p, cuts, device=device)[1])])
     ks = ",".join(str(c) for c in cuts)
     trec = [f"{f}_{ks}" for f in ("P", "recall", "ndcg_cut", "map_cut")]
     parts = []

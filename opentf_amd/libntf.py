@@ -163,6 +163,14 @@ ROC_SYMBOLS = {
     "ntf_roc_micro_csr": (C.c_int, [C.c_int, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
 }
 
+# every symbol declared in include/opentf_amd_fairsort.h (DetConstSort and the infeasible measures of the fair stage: the fourth side header, NTF_ABI_VERSION
+# unchanged): ntf_fair_rerank's arguments without the algorithm plus out_tail; ntf_fair_metrics' arguments with two int32 outputs
+FAIR_CONST_SORT = "det_const_sort"
+FAIRSORT_SYMBOLS = {
+    "ntf_fair_constsort": (C.c_int, [C.c_int, _P, _P, _I64, _I32, _P, _I64, _I32, _P, _I64, _I32, _P, _P, _P, _P]),
+    "ntf_fair_infeasible": (C.c_int, [C.c_int, _P, _I64, _I32, _P, _I64, _I32, _P, _I64, _P, _I32, _P, _P]),
+}
+
 _lib = None
 
 
@@ -177,7 +185,7 @@ def lib():
         for name, (res, args) in SYMBOLS.items():
             fn = getattr(l, name)  # AttributeError if the library does not export a declared symbol
             fn.restype, fn.argtypes = res, args
-        for table in (FAIR_SYMBOLS, LINK_SYMBOLS, ROC_SYMBOLS):
+        for table in (FAIR_SYMBOLS, LINK_SYMBOLS, ROC_SYMBOLS, FAIRSORT_SYMBOLS):
             for name, (res, args) in table.items():
                 fn = getattr(l, name)
                 fn.restype, fn.argtypes = res, args
@@ -254,6 +262,40 @@ def fair_metrics(idx, group, p, cutoffs, device=0, ndkl=True, skew=True):
     if rc != 0:
         raise NtfError(f"ntf_fair_metrics failed ({rc})" + (": an argument outside the contract of include/opentf_amd_fair.h" if rc == NTF_EINVAL else ""))
     return out_n, out_s
+
+
+def fair_constsort(cand_idx, cand_val, group, p, k_out=None, device=0, want_pos=False, want_tail=False):
+    """ntf_fair_constsort (include/opentf_amd_fairsort.h), arguments as fair_rerank's without the algorithm.  -> (out_idx [n, k_out] int32, out_val [n, k_out] f32 or
+    None[, out_pos [n, k_out] int32][, out_tail [n] int32: the ranks the tail rule filled])"""
+    idx, group, p = _fair_inputs(cand_idx, group, p)
+    val = None if cand_val is None else _f32(cand_val)
+    if val is not None and val.shape != idx.shape:
+        raise NtfError(f"cand_val {val.shape} does not match cand_idx {idx.shape}")
+    n, K = idx.shape
+    k_out = K if k_out is None else int(k_out)
+    shape = (n, max(k_out, 0))
+    out_idx = np.empty(shape, dtype=np.int32)
+    out_val = None if val is None else np.empty(shape, dtype=np.float32)
+    out_pos = np.empty(shape, dtype=np.int32) if want_pos else None
+    out_tail = np.empty(n, dtype=np.int32) if want_tail else None
+    rc = lib().ntf_fair_constsort(int(device), _ptr(idx), _ptr(val), n, K, _ptr(group), len(group), p.shape[1], _ptr(p), p.shape[0], k_out,
+                                  _ptr(out_idx), _ptr(out_val), _ptr(out_pos), _ptr(out_tail))
+    if rc != 0:
+        raise NtfError(f"ntf_fair_constsort failed ({rc})" + (": an argument outside the contract of include/opentf_amd_fairsort.h" if rc == NTF_EINVAL else ""))
+    return (out_idx, out_val) + ((out_pos,) if want_pos else ()) + ((out_tail,) if want_tail else ())
+
+
+def fair_infeasible(idx, group, p, cutoffs, device=0, index=True, count=True):
+    """ntf_fair_infeasible (include/opentf_amd_fairsort.h) of the ranked ids idx [n, K]: -> (InfeasibleIndex [n, n_cut] int32 or None, InfeasibleCount likewise)"""
+    idx, group, p = _fair_inputs(idx, group, p)
+    cu = np.ascontiguousarray(np.asarray(cutoffs, dtype=np.int32).reshape(-1))
+    n, K = idx.shape
+    out_i = np.empty((n, len(cu)), dtype=np.int32) if index else None
+    out_c = np.empty((n, len(cu)), dtype=np.int32) if count else None
+    rc = lib().ntf_fair_infeasible(int(device), _ptr(idx), n, K, _ptr(group), len(group), p.shape[1], _ptr(p), p.shape[0], _ptr(cu), len(cu), _ptr(out_i), _ptr(out_c))
+    if rc != 0:
+        raise NtfError(f"ntf_fair_infeasible failed ({rc})" + (": an argument outside the contract of include/opentf_amd_fairsort.h" if rc == NTF_EINVAL else ""))
+    return out_i, out_c
 
 
 class DeviceView:

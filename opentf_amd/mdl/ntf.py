@@ -235,10 +235,11 @@ class Ntf:
 
     def adila(self, teamsvecs, splits, faircfg):
         """Fair stage (the reference's src/mdl/ntf.py:108-134 hands it to a submodule it does not ship): every test-set prediction file `_pred_jobs` lists is ranked
-        `k_max` deep, re-ranked on the device towards the target distribution of the protected attribute (`evl.fair`: DetGreedy / DetCons / DetRelaxed) and both
-        lists are scored for fairness and utility.  Beside each prediction file, with `stem = evl.fair.fair_stem(file, spec)`: `stem.rerank.pred` ({'y_pred': sparse
+        `k_max` deep, re-ranked on the device towards the target distribution of the protected attribute (`evl.fair`: DetGreedy / DetCons / DetRelaxed /
+        DetConstSort) and both lists are scored for fairness and utility.  Beside each prediction file, with `stem = evl.fair.fair_stem(file, spec)`: `stem.rerank.pred` ({'y_pred': sparse
         COO of the re-ranked ids with their values, 'ranked': the ids in rank order, int32 [n, k_max], 'uncertainty': None}), `stem.faireval.csv` and
-        `stem.utileval.csv` (before / after columns).  faircfg keys: algorithm, notion, attribute, k_max, cutoffs (`evl.fair.FairSpec`).  File names, keys and the
+        `stem.utileval.csv` (before / after columns).  faircfg keys: algorithm (det_greedy, det_cons, det_relaxed, det_const_sort), notion, attribute, k_max, cutoffs,
+        infeasible (default false; true adds the rows infeasible_index_{c} / infeasible_count_{c} to faireval.csv) (`evl.fair.FairSpec`).  File names, keys and the
         popularity rule are this package's own; mounted in the reference tree the plugin inherits the reference's adila() instead."""
         import torch
         from ..evl import fair
